@@ -1,6 +1,6 @@
 """bench.py — end-to-end PPO throughput of the device-resident engine on BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is ONE pass of the hot path over one batch: clean_pufferl.evaluate() (128-step rollout of 4096 Squared
 envs per GPU: env step + MLP forward + sample + store) followed by clean_pufferl.train() (GAE + 4 epochs x 4
@@ -9,7 +9,10 @@ configs[1] ("squared env, 4096 envs, 64-dim flat obs, MLP policy, 1xMI355X"); wi
 workload on its own env shard (weak scaling, configs[4] at N = 8) and all-reduces one flat gradient bucket per
 optimizer step over RCCL.  Inputs are synthetic by construction (the env IS the generator) and resident in HBM.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+A plain run sets up, runs W warm-up and K timed steps and prints ONE JSON line on rank 0 with the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...), the section timers of the timed region (profile_ms_per_step) and, with N > 1, the
+ranks' transport and affinity.  --dump-outputs DIR writes what the last timed step handed its caller (dump_outputs below).
+--full adds everything else this file measures and checks, each in passes of its own after the timed steps:
   roofline     dominant kernel ppo_mlp_grad (fp32 MFMA bound): algorithmic FLOPs per launch / average launch
                duration measured with HIP events on the launch stream over the timed region (every 17th launch
                bracketed: the event packets serialise the queue)
@@ -17,6 +20,8 @@ Prints ONE JSON line on rank 0 with the contract fields plus
                with_reference.sh (profiles/r06_reference_cpu_on_gpu_box.json; used when the box fingerprint matches), with the
                live timing of the CPU oracle port (C env + torch-fp32 policy/update, oracle/) on a bounded sample of the same
                workload on this box's host cores riding along (`port_live`; it IS the baseline when no record matches)
+  and the per-kernel breakdown, the sustained leg, the deferred-readback leg, the oracle self-checks, the per-transport A/B of
+  N > 1 and the side workloads (extra_workloads).
 """
 import argparse
 import ctypes as C
@@ -574,7 +579,7 @@ def pmc_mfma_utilisation(kernel, waves_per_simd=2):
 def extra_workload(flags, timeout_s=600):
     """A short run of one of the side workloads (BASELINE configs[2] / configs[3]) as its own process; its JSON line, trimmed."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), '--no-breakdown', '--no-extra'] + flags
+    cmd = [sys.executable, os.path.abspath(__file__), '--full', '--no-breakdown', '--no-extra'] + flags
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s)
         line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith('{')][-1]
@@ -583,6 +588,64 @@ def extra_workload(flags, timeout_s=600):
                                   'profile_ms_per_step', 'self_check', 'kernel_ms_per_step') if k in d}
     except Exception as e:  # a side workload never takes the headline line down with it
         return dict(flags=flags, error=f'{type(e).__name__}: {e}')
+
+
+DUMP_SAMPLE = 1 << 20        # an array of more elements is dumped as a fixed, seeded sample of this many flat indices (at most)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, stats, data, pol):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST timed step, one DIR/<name>.npy per array:
+      experience.<field>   the env-major rollout the step's evaluate() filled and its train() used (obs, actions, logprobs, values,
+                           rewards, dones, advantages, returns)
+      policy...            the policy's state_dict after the step's update
+      losses.<name>        train()'s losses;  stats.<name>  evaluate()'s episode statistics
+    float32 (float64 for integer data and the host-side scalars).  An array of more than DUMP_SAMPLE elements is written as
+    <name>.sample.npy: its flat elements at the indices np.random.default_rng(0) draws (the same for every run of the same shape),
+    fewer of them where the whole dump would otherwise exceed DUMP_MAX_BYTES; nothing is written before the total is known.
+    The inputs are fixed by the arguments (seeded policy init, env and action noise), so two builds compare output for output."""
+    import numpy as np
+    import torch
+    from pufferlib_amd import readback
+    arrays = {}
+    exp = data.experience
+    for f in ('obs', 'actions', 'logprobs', 'values', 'rewards', 'dones', 'advantages', 'returns'):
+        arrays['experience.' + f] = getattr(exp, f)
+    for k, v in pol.state_dict().items():
+        arrays[k] = v
+    for k, v in data.losses.items():
+        arrays['losses.' + k] = torch.tensor(float(v), dtype=torch.float64)
+    for k, v in readback.materialize(stats).items():
+        try:
+            arrays['stats.' + k] = torch.as_tensor(np.asarray(v, dtype=np.float64))
+        except (TypeError, ValueError):
+            pass                                     # a non-numeric entry is not an array a caller computes with
+    # the whole dump is sized before anything is written: arrays of up to DUMP_SAMPLE elements whole, the larger ones sampled, each
+    # sample shrunk where needed so that the total stays within DUMP_MAX_BYTES
+    items = []
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        items.append((name, t, dt, 4 if dt == torch.float32 else 8))
+    whole = sum(t.numel() * size for _, t, _, size in items if t.numel() <= DUMP_SAMPLE)
+    big = [t for _, t, _, _ in items if t.numel() > DUMP_SAMPLE]
+    if whole > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: the unsampled arrays alone take {whole >> 20} MB, more than {DUMP_MAX_BYTES >> 20} MB')
+    share = (DUMP_MAX_BYTES - whole) // max(len(big), 1)
+    out = []
+    for name, t, dt, size in items:
+        if t.numel() <= DUMP_SAMPLE:
+            out.append((name, t.to(dt).cpu().numpy()))
+            continue
+        n = min(DUMP_SAMPLE, share // size)
+        idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), n, dtype=np.int64))
+        out.append((name + '.sample', t.reshape(-1)[torch.as_tensor(idx, device=t.device)].to(dt).cpu().numpy()))
+    total = sum(a.nbytes for _, a in out)
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out:
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return total
 
 
 def main():
@@ -610,9 +673,21 @@ def main():
     ap.add_argument('--no-breakdown', action='store_true', help='skip the extra (untimed) per-kernel breakdown pass')
     ap.add_argument('--no-transport-ab', action='store_true', help='N > 1: skip the extra K-step legs per transport (p2p fused / p2p launch / rccl)')
     ap.add_argument('--no-extra', action='store_true', help="skip the short configs[2] / configs[3] side runs appended to the N = 1 headline line")
-    ap.add_argument('--sustained-seconds', type=float, default=3.0,
-                    help='after the K timed steps: an extra leg of at least this many seconds of the same loop, reported as sustained_value (0 = skip)')
+    ap.add_argument('--sustained-seconds', type=float, default=None,
+                    help='after the K timed steps: an extra leg of at least this many seconds of the same loop, reported as sustained_value '
+                         '(0 = skip; default 3 with --full, else 0)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps: write what the last timed step computed as DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline figure: roofline, per-kernel breakdown, sustained and deferred-readback '
+                         'legs, cpu_baseline + oracle self-checks, the N > 1 transport A/B and the side workloads (each as passes of their own)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 (the timed region) and --warmup at least 0')
+    if not args.full:      # a plain run: set up, warm up, the K timed steps, the outputs, the line
+        args.no_cpu_baseline = args.no_breakdown = args.no_extra = args.no_transport_ab = True
+    if args.sustained_seconds is None:
+        args.sustained_seconds = 3.0 if args.full else 0.0
     if args.gpus > 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and 'RANK' not in os.environ:
         sys.exit(self_spawn(args))
 
@@ -667,6 +742,7 @@ def main():
     else:
         vec = vector.make(vector.make_squared, env_kwargs=dict(distance_to_target=D, num_targets=NT), num_envs=NUM_ENVS,
                           backend=vector.Squared, obs_stride=64)
+    torch.manual_seed(1)     # the policy's initial weights: the same in every run of the same arguments (create() seeds the rest)
     if args.workload == 'squared' and args.policy == 'mlp' and args.hidden != 128:
         args.policy = 'wide'
         pol = cleanrl.Policy(models.Default(vec.driver_env, hidden_size=args.hidden))
@@ -700,9 +776,10 @@ def main():
     # of a 20-step region; rounds 2-5 bracketed every 5th, which tools/step_times.py shows as ~20 us of every 1.27 ms step — the
     # same loop without the brackets, from a cold start); the conv update's launches differ in shape and are all bracketed.
     event_stride = 1 if (args.policy in ('cnn', 'wide') and not wide_fused) else 17
-    L.pfa_timing_stride(event_stride)
-    L.pfa_timing_reset()
-    L.pfa_timing_enable(1)   # dominant kernel only
+    if args.full:            # the roofline's launch times; a plain run leaves the timed loop without event packets
+        L.pfa_timing_stride(event_stride)
+        L.pfa_timing_reset()
+        L.pfa_timing_enable(1)   # dominant kernel only
     def profile_snapshot():
         # the reference's six section timers + the two wall timers (clean_pufferl.py:328-339), cumulative seconds
         pr, tm = data.profile, getattr(data, '_timers', {})
@@ -717,13 +794,15 @@ def main():
     prof0 = profile_snapshot()
     t0 = time.perf_counter()
     for _ in range(K):
-        clean_pufferl.evaluate(data)
+        stats, _ = clean_pufferl.evaluate(data)
         clean_pufferl.train(data)
     barrier()
     dt = time.perf_counter() - t0
     prof1 = profile_snapshot()
     peer_wait = pdist.wait_stats(reset=True) if (world > 1 and data.native_dp) else None
     L.pfa_timing_enable(0)
+    if args.dump_outputs and rank == 0:      # before any further pass moves the state on
+        dump_outputs(args.dump_outputs, stats, data, pol)
     # clean_pufferl.Profile's breakdown over the timed region, ms per step.  The section timers bracket kernel ENQUEUES (the device
     # runs asynchronously); eval_time / train_time are the wall timers of evaluate() / train(), each ending in one stream sync.
     names_ = dict(evaluate='eval_time', env='env_time', eval_forward='eval_forward_time', eval_misc='eval_misc_time', train='train_time',
@@ -774,7 +853,7 @@ def main():
     # containers that resolve on first access; opt-in because C-level dict consumers see an unresolved container as empty) — what the
     # two host round trips of the default mode cost, reported next to the headline, never as the headline
     deferred = None
-    if world == 1 and args.policy == 'mlp' and args.workload == 'squared' and args.sustained_seconds > 0:
+    if world == 1 and args.policy == 'mlp' and args.workload == 'squared' and args.sustained_seconds > 0 and args.full:
         saved_lazy = os.environ.get('PFA_LAZY_READBACK')
         os.environ['PFA_LAZY_READBACK'] = '1'
         for _ in range(2):
@@ -905,7 +984,7 @@ def main():
             step_flop = per_gpu * ((2 * Kp_ * Hh + 2 * Hh * NO_) * (1 + EPOCHS) + EPOCHS * 2 * NO_ * Hh)
             achieved = step_flop * K / (total_ms * 1e-3) / 1e12 if launches else 0.0
             flop_row, rows_per_launch = step_flop * K / max(launches, 1), 1
-        traffic, traffic_source = pmc_traffic(dominant)
+        traffic, traffic_source = pmc_traffic(dominant) if args.full else (None, None)
         wide_how = 'fused kernels of csrc/ppo_wide.hip + tile-kernel rollout' if wide_fused else 'GEMM path, general.py'
         roof_peak = PEAK_FP32_MFMA_TFLOPS if args.products == 'fp32' else PEAK_BF16_MFMA_TFLOPS / 6.0
         out = {
@@ -958,7 +1037,9 @@ def main():
             'profile_ms_per_step': profile_ms,
             'rank_ms_per_step': {'min': min(rank_ms), 'max': max(rank_ms), 'per_rank': [round(x, 4) for x in rank_ms]},
         }
-        if args.policy == 'mlp':
+        if not args.full:        # a plain run times no launch of its own: the roofline and the per-kernel breakdown are --full's
+            del out['roofline'], out['kernel_ms_per_step']
+        if args.policy == 'mlp' and args.full:
             # the MFMA instructions the instantiated kernel really issues per 16-row tile (csrc/ppo_update.hip: forward KKU x 8, heads
             # 32, dW2v 32, dh DHK x 8, dW1 KTM x 32): the padded SURVEY figure above is the contract's `frac`, this is the executed one
             import ctypes as _C

@@ -10,6 +10,7 @@ from the reference is copied: this script calls its public functions and records
 
 Fixtures written (all small, committed):
   gae.npz            c_gae.compute_gae (c_gae.pyx:11-32) on KAT / random / boundary inputs
+  c_gae_rs5.npz      the same on one 5000-step random batch (`make_golden.py c_gae`)
   squared_<tag>.npz  pufferlib.vector.Serial over ocean make_squared (vector.py:70-166,
                      ocean.py:406-513, emulation.py:124-234, postprocess.py:8-54): lock-step trajectories
   bandit.npz         pufferlib.vector.Serial over ocean make_bandit (ocean.py:8-63): numpy legacy randint + gauss
@@ -67,6 +68,16 @@ def gen_gae(compute_gae):
         out[k + '_adv'] = np.asarray(adv)
     np.savez_compressed(os.path.join(HERE, 'gae.npz'), **out)
     print('gae.npz', len(cases), 'cases')
+
+
+def gen_c_gae_rs5(compute_gae):
+    """c_gae_rs5.npz: c_gae.compute_gae on the 5000-step batch test_oracle_golden.test_ref_c_gae_agrees_when_built draws."""
+    rng = np.random.RandomState(5)
+    d = (rng.rand(5000) < .05).astype(np.float32)
+    v, r = rng.randn(5000).astype(np.float32), rng.randn(5000).astype(np.float32)
+    adv = np.asarray(compute_gae(d, v, r, .99, .95))
+    np.savez_compressed(os.path.join(HERE, 'c_gae_rs5.npz'), dones=d, values=v, rewards=r, gl=np.array([.99, .95]), adv=adv)
+    print('c_gae_rs5.npz', adv.dtype, adv.shape)
 
 
 def gen_squared(tag, num_envs, d, nt, seed, steps):
@@ -883,6 +894,9 @@ if __name__ == '__main__':
         gen_ppo('mlp_h256', use_rnn=False, hidden=256)
         sys.exit(0)
     import clean_pufferl  # builds c_gae through pyximport exactly as the reference does (clean_pufferl.py:24-27)
+    if len(sys.argv) > 1 and sys.argv[1] == 'c_gae':
+        gen_c_gae_rs5(clean_pufferl.compute_gae)
+        sys.exit(0)
     gen_gae(clean_pufferl.compute_gae)
     gen_squared('d3t1', 64, 3, 1, 1, 60)
     gen_squared('d1t4', 8, 1, -1, 42, 40)      # n=8 <= 21: pool-swap sampling, variable bit widths

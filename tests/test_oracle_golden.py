@@ -88,22 +88,24 @@ def test_gae_appendix_b():
 
 
 def test_ref_c_gae_agrees_when_built(golden_dir):
-    """oracle/_ref/c_gae*.so is the reference's own Cython kernel compiled from /root/reference."""
+    """The reference's own Cython kernel (c_gae.pyx) on a 5000-step random batch: its advantages, recorded in
+    tests/golden/c_gae_rs5.npz, bit for bit from the C oracle — and from oracle/_ref/c_gae*.so where build() compiled it."""
     import importlib.util
     import glob
-    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    so = glob.glob(os.path.join(here, 'oracle', '_ref', 'c_gae*.so'))
-    if not so:
-        pytest.skip('oracle/_ref not built (no /root/reference here)')
-    spec = importlib.util.spec_from_file_location('c_gae', so[0])
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    g = _load(golden_dir, 'c_gae_rs5.npz')
     rng = np.random.RandomState(5)
     d = (rng.rand(5000) < .05).astype(np.float32)
     v, r = rng.randn(5000).astype(np.float32), rng.randn(5000).astype(np.float32)
-    a = mod.compute_gae(d, v, r, .99, .95)
+    assert np.array_equal(d, g['dones']) and np.array_equal(v, g['values']) and np.array_equal(r, g['rewards'])
+    want = g['adv'].view(np.uint32)
     b = c_oracle.compute_gae(d, v, r, .99, .95)
-    assert np.array_equal(np.asarray(a).view(np.uint32), b.view(np.uint32))
+    assert np.array_equal(b.view(np.uint32), want)
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for so in glob.glob(os.path.join(here, 'oracle', '_ref', 'c_gae*.so')):
+        spec = importlib.util.spec_from_file_location('c_gae', so)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        assert np.array_equal(np.asarray(mod.compute_gae(d, v, r, .99, .95)).view(np.uint32), want)
 
 
 # ---------------------------------------------------------------- policy / PPO update

@@ -10,7 +10,7 @@ OUT=gpurun_out/${TAG}_ab_host.txt
 run() {  # label, env assignments...
   local label=$1; shift
   local line
-  line=$(env "$@" timeout 200 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-breakdown --no-extra --sustained-seconds 0 2>/dev/null | tail -1)
+  line=$(env "$@" timeout 200 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-breakdown --no-extra --sustained-seconds 0 2>/dev/null | tail -1)
   python - "$label" "$line" >> $OUT <<'PY'
 import json, sys
 label, line = sys.argv[1], sys.argv[2]
