@@ -44,7 +44,7 @@ from . import dist as pdist
 from .cleanrl import Policy, RecurrentPolicy
 from .models import FlatParams  # noqa: F401  (re-exported: callers of create() type-check the trainer's parameter buffer against it)
 from .namespace import namespace
-from .vector import Bandit, Frames, Memory, Multiagent, Spaces, Squared, Stochastic, Synthetic
+from .vector import Bandit, Frames, Memory, Multiagent, Spaces, Squared, Stochastic, Synthetic, _DeviceVecEnv
 
 
 def seed_everything(seed, torch_deterministic=True):
@@ -278,7 +278,7 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
     n_params = sum(p.numel() for p in policy.parameters())
     msg = f'Model Size: {n_params} parameters'
 
-    host_mode = not isinstance(vecenv, (Squared, Stochastic, Memory, Bandit, Multiagent, Spaces, Synthetic))   # anything else speaks the recv/send protocol on the host
+    host_mode = not isinstance(vecenv, _DeviceVecEnv)   # anything else speaks the recv/send protocol on the host
     if not isinstance(policy, (Policy, RecurrentPolicy)):
         from .models import find_lstm
         if find_lstm(policy) is not None:             # e.g. the reference's RecurrentPolicy(LSTMWrapper(Default))

@@ -2,7 +2,8 @@
 //   lstm_pack_kernel             Wcat = [W_ih | W_hh] -> per-wave A-fragment order (512 KB, once per weight version)
 //   lstm_policy_step_kernel      RecurrentPolicy.forward with action=None (frameworks/cleanrl.py:84-93 ->
 //                                models.py:86-111): encode -> one nn.LSTM step -> decode -> sample_logits, state in/out
-//   rollout_lstm_squared_kernel  clean_pufferl.evaluate (clean_pufferl.py:76-154) for a Squared vecenv and the
+//   rollout_lstm_kernel          clean_pufferl.evaluate (clean_pufferl.py:76-154) for a Squared / Memory / Synthetic vecenv
+//                                (one env adapter each) and the
 //                                recurrent policy: one persistent workgroup per 16 envs for all T steps; env state in
 //                                registers, observation grid / [xe | h] tile in LDS, c in registers, the gate matrix
 //                                streamed from L2 every step.  The LSTM state is carried across steps and across
@@ -117,18 +118,141 @@ __global__ void __launch_bounds__(kLstmThreads) lstm_policy_step_kernel(const fl
 }
 
 // ---------------------------------------------------------------------------------------------
-// fused persistent rollout (see the header comment); structure follows rollout_mlp_squared_kernel (rollout.hip)
+// fused persistent rollout (see the header comment); structure follows rollout_mlp_squared_kernel (rollout.hip).
+// The kernel is one skeleton over an env adapter: a plain struct that holds the env's state in registers of its owner
+// thread (lane 0 of the env's 16-lane sampling group) and supplies what differs per env family:
+//   View / view()   the device view of the vecenv state and how the entry point's config maps to it
+//   Shared          what the env keeps in LDS next to LstmLds (empty: costs nothing)
+//   load / store    owner thread: state in before the first step / out after the last one
+//   step            owner thread, after the scalars of row (e, t) are stored: reset from the tape or apply the sampled
+//                   action; writes `reward` / `terminal` of the next row and the env's LDS observation row
+//   refresh         all 16 lanes of the env, after the barrier that follows step, only where kRefresh (a second barrier
+//                   follows it)
 // ---------------------------------------------------------------------------------------------
-template <int DP>
-__global__ void __launch_bounds__(kLstmThreads) rollout_lstm_squared_kernel(SquaredView v, const float *params, int a,
-                                                                           const float4 *wpack, float *h, float *cell,
-                                                                           pfa_experience ex, const float *noise, uint64_t seed,
-                                                                           uint64_t step0, long long env_offset, float *live_obs,
-                                                                           float *live_rew, uint8_t *live_term,
-                                                                           uint8_t *live_trunc, uint8_t *live_mask) {
+struct SquaredRollEnv {
+    using View = SquaredView;
+    static View view(void *state, const pfa_squared_config &c) { return squared_view(state, c); }
+    static constexpr bool kRefresh = false;
+    struct Shared {
+        uint16_t tg[16 * kMaxTargets];   // target cells per env
+    };
+    SquaredEnv s;
+
+    __device__ __forceinline__ void load(const View &v, int e, int le, Shared &sh) {
+        squared_load(v, e, s);
+        for (int t = 0; t < v.nt; ++t) sh.tg[le * kMaxTargets + t] = v.tgt[(size_t)t * v.n + e];
+    }
+    __device__ __forceinline__ void step(const View &v, int e, int le, Shared &sh, float *grid, int action, float &reward,
+                                         bool &terminal) {
+        uint16_t *tc = sh.tg + le * kMaxTargets;
+        if (s.done) {
+            if ((long long)s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
+            const uint16_t *tr = v.tape + (size_t)(s.rounds % (uint32_t)v.tape_rounds) * v.nt * v.n;
+            squared_reset(v, e, s, grid, tr, tc, reward, terminal);
+            s.rounds += 1;
+        } else {
+            bool fin;
+            double fr, fs;
+            int fl;
+            squared_step(v, s, grid, tc, action, reward, terminal, fin, fr, fl, fs);
+        }
+    }
+    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
+    __device__ __forceinline__ void store(const View &v, int e, int le, Shared &sh) {
+        squared_store(v, e, s);
+        for (int t = 0; t < v.nt; ++t) v.tgt[(size_t)t * v.n + e] = sh.tg[le * kMaxTargets + t];
+        v.fin[e] = 0;
+    }
+};
+
+// ocean Memory (memory_env.hpp; observation rows of 16 floats, one real column): the env that NEEDS the recurrent state.
+struct MemoryRollEnv {
+    using View = MemoryView;
+    static View view(void *state, const pfa_memory_config &c) { return memory_view(state, c); }
+    static constexpr bool kRefresh = false;
+    struct Shared {};
+    MemoryEnv s = {};
+    int last_fin = 0;
+
+    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
+    __device__ __forceinline__ void step(const View &v, int e, int, Shared &, float *row, int action, float &reward, bool &terminal) {
+        float o;
+        last_fin = 0;
+        if (s.done) {   // auto-reset row (vector.py:144-151): the action is ignored, the next solution comes off the tape
+            if (s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
+            const uint32_t bits = v.tape[(size_t)(s.rounds % v.tape_rounds) * v.n + e];
+            const long long rounds = s.rounds + 1;
+            memory_begin_episode(s, bits, o, reward, terminal);
+            s.rounds = rounds;
+        } else {
+            double fr, fs;
+            int fl;
+            if (memory_step(v, s, action, o, reward, terminal, fr, fl, fs)) {
+                episode_account(v.fin[e], fr, fl, fs);
+                last_fin = 1;
+            }
+        }
+        row[0] = o;
+    }
+    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
+    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
+        v.env[e] = s;
+        v.fin[e].last_fin = last_fin;
+    }
+};
+
+// The synthetic byte-row env of BASELINE configs[2] (synth_env.hpp; rows of DP = obs_stride floats).  The 16 lanes of an env's
+// sampling group regenerate its observation row after the step, 16 values per lane (one Philox call each).
+struct SynthRollEnv {
+    using View = SynthView;
+    static View view(void *state, const pfa_synth_config &c) { return synth_view(state, c); }
+    static constexpr bool kRefresh = true;
+    struct Shared {
+        int tick[16], episode[16];   // the owner's (tick, episode) after the step, for the other lanes of the env
+    };
+    SynthEnv s = {};
+    int last_fin = 0;
+
+    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
+    __device__ __forceinline__ void step(const View &v, int e, int le, Shared &sh, float *row, int action, float &reward, bool &terminal) {
+        last_fin = 0;
+        if (s.done) {
+            synth_begin_episode(s, reward, terminal);
+        } else {
+            double fr, fs;
+            int fl;
+            if (synth_step(v, s, action, (int)row[0], reward, terminal, fr, fl, fs)) {
+                episode_account(v.fin[e], fr, fl, fs);
+                last_fin = 1;
+            }
+        }
+        sh.tick[le] = s.tick;
+        sh.episode[le] = s.episode;
+    }
+    __device__ __forceinline__ void refresh(const View &v, int e, int le, int lo, Shared &sh, float *row) {
+        if (lo * 16 < v.values) {   // the next observation row of this env, 16 values per lane
+            float vals[16];
+            synth_chunk(v, e, sh.episode[le], sh.tick[le], lo, vals);
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (lo * 16 + k < v.values) row[lo * 16 + k] = vals[k];
+        }
+    }
+    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
+        v.env[e] = s;
+        v.fin[e].last_fin = last_fin;
+    }
+};
+
+template <int DP, class Env>
+__global__ void __launch_bounds__(kLstmThreads) rollout_lstm_kernel(typename Env::View v, const float *params, int a,
+                                                                   const float4 *wpack, float *h, float *cell, pfa_experience ex,
+                                                                   const float *noise, uint64_t seed, uint64_t step0,
+                                                                   long long env_offset, float *live_obs, float *live_rew,
+                                                                   uint8_t *live_term, uint8_t *live_trunc, uint8_t *live_mask) {
     constexpr int XS = XTile<DP>::XS;
     __shared__ LstmLds<DP> L;
-    __shared__ uint16_t tg[16 * kMaxTargets];
+    __shared__ typename Env::Shared sh;
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15;  // sampling role: local env, output index
     const int e = blockIdx.x * 16 + le;
     const bool env_ok = e < v.n;
@@ -146,12 +270,11 @@ __global__ void __launch_bounds__(kLstmThreads) rollout_lstm_squared_kernel(Squa
     load_hstate(h, first, v.n, L.xh[0]);
     f32x4 cst[2];
     load_cstate(cell, first + c, first + c < v.n, cst);
-    SquaredEnv s;
+    Env env;
     float reward = 0.0f;
     bool terminal = false;
     if (owner) {
-        squared_load(v, e, s);
-        for (int t = 0; t < v.nt; ++t) tg[le * kMaxTargets + t] = v.tgt[(size_t)t * v.n + e];
+        env.load(v, e, le, sh);
         reward = live_rew[e];
         terminal = live_term[e] != 0;
     }
@@ -173,208 +296,17 @@ __global__ void __launch_bounds__(kLstmThreads) rollout_lstm_squared_kernel(Squa
             ex.actions[row] = sm.action;
             ex.logprobs[row] = sm.logprob;
             ex.values[row] = sm.value;
-            float *grid = L.xs + le * XS;
-            uint16_t *tc = tg + le * kMaxTargets;
-            if (s.done) {
-                if ((long long)s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
-                const uint16_t *tr = v.tape + (size_t)(s.rounds % (uint32_t)v.tape_rounds) * v.nt * v.n;
-                squared_reset(v, e, s, grid, tr, tc, reward, terminal);
-                s.rounds += 1;
-            } else {
-                bool fin;
-                double fr, fs;
-                int fl;
-                squared_step(v, s, grid, tc, sm.action, reward, terminal, fin, fr, fl, fs);
-            }
+            env.step(v, e, le, sh, L.xs + le * XS, sm.action, reward, terminal);
         }
         __syncthreads();
-    }
-
-    if (owner) {
-        squared_store(v, e, s);
-        for (int t = 0; t < v.nt; ++t) v.tgt[(size_t)t * v.n + e] = tg[le * kMaxTargets + t];
-        v.fin[e] = 0;
-        live_rew[e] = reward;
-        live_term[e] = terminal ? 1 : 0;
-        live_trunc[e] = 0;
-        live_mask[e] = 1;
-    }
-    lstm_unstage_obs<DP>(L.xs, live_obs, first, v.n, (size_t)DP);
-    store_cstate(cell, first + c, first + c < v.n, cst);
-    store_hstate(h, first, v.n, L.xh[T & 1]);
-}
-
-// The same persistent rollout over the ocean Memory vecenv (memory_env.hpp; observation rows of 16 floats, one real column):
-// the env that NEEDS the recurrent state.  Per step the owner thread of an env stores the scalars of the row, then either
-// starts the next episode from the solution tape (auto-reset row) or applies memory_step to the sampled action and rewrites
-// column 0 of the env's LDS observation row.
-__global__ void __launch_bounds__(kLstmThreads) rollout_lstm_memory_kernel(MemoryView v, const float *params, int a,
-                                                                          const float4 *wpack, float *h, float *cell,
-                                                                          pfa_experience ex, const float *noise, uint64_t seed,
-                                                                          uint64_t step0, long long env_offset, float *live_obs,
-                                                                          float *live_rew, uint8_t *live_term,
-                                                                          uint8_t *live_trunc, uint8_t *live_mask) {
-    constexpr int DP = kMemDP, XS = XTile<DP>::XS;
-    __shared__ LstmLds<DP> L;
-    const int le = threadIdx.x >> 4, lo = threadIdx.x & 15;
-    const int e = blockIdx.x * 16 + le;
-    const bool env_ok = e < v.n;
-    const bool owner = lo == 0 && env_ok;
-    const int T = ex.horizon_T;
-    const int c = lane_id() & 15;
-    const long long first = (long long)blockIdx.x * 16;
-
-    LstmFrags<DP> w;
-    w.load(params, a);
-    stage_gate_bias(params, DP, a, L.gbias);
-    const float4 *wp = wpack + (size_t)__builtin_amdgcn_readfirstlane(wave_id()) * 16 * 8 * 64;
-
-    lstm_stage_obs<DP>(live_obs, first, v.n, L.xs);
-    load_hstate(h, first, v.n, L.xh[0]);
-    f32x4 cst[2];
-    load_cstate(cell, first + c, first + c < v.n, cst);
-    MemoryEnv s = {};
-    float reward = 0.0f;
-    bool terminal = false;
-    int last_fin = 0;
-    if (owner) {
-        s = v.env[e];
-        reward = live_rew[e];
-        terminal = live_term[e] != 0;
-    }
-    __syncthreads();
-
-    for (int t = 0; t < T; ++t) {
-        const int cur = t & 1;
-        lstm_tile_step<DP>(w, wp, L, cur, cst,
-                           [&] { lstm_unstage_obs<DP>(L.xs, ex.obs + (size_t)t * DP, first, v.n, (size_t)T * DP); });
-        const float q = env_ok ? noise_lane(noise ? noise + ((size_t)t * v.n + e) * a : nullptr, seed, step0 + t,
-                                            (uint64_t)(env_offset + e), lo, a)
-                               : 1.0f;
-        const LaneSample sm = lstm_sample(L.part, le, lo, a, q);
-        if (owner) {
-            const size_t row = (size_t)e * T + t;
-            ex.rewards[row] = reward;
-            ex.dones[row] = terminal ? 1.0f : 0.0f;
-            ex.actions[row] = sm.action;
-            ex.logprobs[row] = sm.logprob;
-            ex.values[row] = sm.value;
-            float o;
-            last_fin = 0;
-            if (s.done) {   // auto-reset row (vector.py:144-151): the action is ignored, the next solution comes off the tape
-                if (s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
-                const uint32_t bits = v.tape[(size_t)(s.rounds % v.tape_rounds) * v.n + e];
-                const long long rounds = s.rounds + 1;
-                memory_begin_episode(s, bits, o, reward, terminal);
-                s.rounds = rounds;
-            } else {
-                double fr, fs;
-                int fl;
-                if (memory_step(v, s, sm.action, o, reward, terminal, fr, fl, fs)) {
-                    episode_account(v.fin[e], fr, fl, fs);
-                    last_fin = 1;
-                }
-            }
-            L.xs[le * XS] = o;
+        if constexpr (Env::kRefresh) {
+            if (env_ok) env.refresh(v, e, le, lo, sh, L.xs + le * XS);
+            __syncthreads();
         }
-        __syncthreads();
     }
 
     if (owner) {
-        v.env[e] = s;
-        v.fin[e].last_fin = last_fin;
-        live_rew[e] = reward;
-        live_term[e] = terminal ? 1 : 0;
-        live_trunc[e] = 0;
-        live_mask[e] = 1;
-    }
-    lstm_unstage_obs<DP>(L.xs, live_obs, first, v.n, (size_t)DP);
-    store_cstate(cell, first + c, first + c < v.n, cst);
-    store_hstate(h, first, v.n, L.xh[T & 1]);
-}
-
-// ... and over the synthetic byte-row env of BASELINE configs[2] (synth_env.hpp; rows of DP = obs_stride floats).  The 16 lanes
-// of an env's sampling group regenerate its observation row after the step, 16 values per lane (one Philox call each).
-template <int DP>
-__global__ void __launch_bounds__(kLstmThreads) rollout_lstm_synth_kernel(SynthView v, const float *params, int a, const float4 *wpack,
-                                                                         float *h, float *cell, pfa_experience ex, const float *noise,
-                                                                         uint64_t seed, uint64_t step0, long long env_offset,
-                                                                         float *live_obs, float *live_rew, uint8_t *live_term,
-                                                                         uint8_t *live_trunc, uint8_t *live_mask) {
-    constexpr int XS = XTile<DP>::XS;
-    __shared__ LstmLds<DP> L;
-    __shared__ int s_tick[16], s_episode[16];
-    const int le = threadIdx.x >> 4, lo = threadIdx.x & 15;
-    const int e = blockIdx.x * 16 + le;
-    const bool env_ok = e < v.n;
-    const bool owner = lo == 0 && env_ok;
-    const int T = ex.horizon_T;
-    const int c = lane_id() & 15;
-    const long long first = (long long)blockIdx.x * 16;
-
-    LstmFrags<DP> w;
-    w.load(params, a);
-    stage_gate_bias(params, DP, a, L.gbias);
-    const float4 *wp = wpack + (size_t)__builtin_amdgcn_readfirstlane(wave_id()) * 16 * 8 * 64;
-
-    lstm_stage_obs<DP>(live_obs, first, v.n, L.xs);
-    load_hstate(h, first, v.n, L.xh[0]);
-    f32x4 cst[2];
-    load_cstate(cell, first + c, first + c < v.n, cst);
-    SynthEnv s = {};
-    float reward = 0.0f;
-    bool terminal = false;
-    int last_fin = 0;
-    if (owner) {
-        s = v.env[e];
-        reward = live_rew[e];
-        terminal = live_term[e] != 0;
-    }
-    __syncthreads();
-
-    for (int t = 0; t < T; ++t) {
-        const int cur = t & 1;
-        lstm_tile_step<DP>(w, wp, L, cur, cst,
-                           [&] { lstm_unstage_obs<DP>(L.xs, ex.obs + (size_t)t * DP, first, v.n, (size_t)T * DP); });
-        const float q = env_ok ? noise_lane(noise ? noise + ((size_t)t * v.n + e) * a : nullptr, seed, step0 + t,
-                                            (uint64_t)(env_offset + e), lo, a)
-                               : 1.0f;
-        const LaneSample sm = lstm_sample(L.part, le, lo, a, q);
-        if (owner) {
-            const size_t row = (size_t)e * T + t;
-            ex.rewards[row] = reward;
-            ex.dones[row] = terminal ? 1.0f : 0.0f;
-            ex.actions[row] = sm.action;
-            ex.logprobs[row] = sm.logprob;
-            ex.values[row] = sm.value;
-            last_fin = 0;
-            if (s.done) {
-                synth_begin_episode(s, reward, terminal);
-            } else {
-                double fr, fs;
-                int fl;
-                if (synth_step(v, s, sm.action, (int)L.xs[le * XS], reward, terminal, fr, fl, fs)) {
-                    episode_account(v.fin[e], fr, fl, fs);
-                    last_fin = 1;
-                }
-            }
-            s_tick[le] = s.tick;
-            s_episode[le] = s.episode;
-        }
-        __syncthreads();
-        if (env_ok && lo * 16 < v.values) {   // the next observation row of this env, 16 values per lane
-            float vals[16];
-            synth_chunk(v, e, s_episode[le], s_tick[le], lo, vals);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (lo * 16 + k < v.values) L.xs[le * XS + lo * 16 + k] = vals[k];
-        }
-        __syncthreads();
-    }
-
-    if (owner) {
-        v.env[e] = s;
-        v.fin[e].last_fin = last_fin;
+        env.store(v, e, le, sh);
         live_rew[e] = reward;
         live_term[e] = terminal ? 1 : 0;
         live_trunc[e] = 0;
@@ -451,32 +383,48 @@ extern "C" int pfa_lstm_policy_step(const float *obs, int64_t rows, const float 
     return 0;
 }
 
+// What the three rollout entry points share: `name` is the entry point's kernel-timer name and the prefix of its error texts;
+// the entry point has checked `dims`, `cfg` and what only its env requires.  kOnlyDP != 0: the one row width the env has.
+template <class Env, int kOnlyDP = 0, class Config>
+static int launch_rollout_lstm(const char *name, void *state, const Config *cfg, const float *params, const pfa_mlp_dims *dims,
+                               const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                               const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                               uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    PFA_REQUIRE(state && params && wpack && h && c && exp && obs && rewards && terminals && truncations && masks, "%s: null buffer", name);
+    PFA_REQUIRE(dims->heads == 0, "%s: the fused rollout samples one Discrete head", name);
+    PFA_REQUIRE(exp->horizon_T >= 1, "%s: horizon must be >= 1", name);
+    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones, "%s: null experience buffer", name);
+    PFA_REQUIRE(noise || key, "%s: need an explicit noise tensor or a Philox key", name);
+    const typename Env::View v = Env::view(state, *cfg);
+    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
+    const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
+    ScopedKernelTimer timer(name, (hipStream_t)stream);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kLstmThreads), 0, (hipStream_t)stream, v, params, dims->num_actions,
+                           (const float4 *)wpack, h, c, *exp, noise, seed, step, (long long)env_offset, obs, rewards, terminals,
+                           truncations, masks);
+    };
+    if constexpr (kOnlyDP != 0) {
+        launch(rollout_lstm_kernel<kOnlyDP, Env>);
+    } else {
+        PFA_LSTM_DISPATCH_DP(dims->obs_stride, launch(rollout_lstm_kernel<DP, Env>));
+    }
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int pfa_rollout_lstm_squared(void *state, const pfa_squared_config *cfg, const float *params,
                                         const pfa_mlp_dims *dims, const void *wpack, float *h, float *c,
                                         const pfa_experience *exp, const float *noise, const pfa_noise_key *key,
                                         int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                                         uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     if (int rc = check_lstm_dims(dims)) return rc;
-    PFA_REQUIRE(state && cfg && params && wpack && h && c && exp && obs && rewards && terminals && truncations && masks,
-                "rollout_lstm: null buffer");
-    PFA_REQUIRE(dims->heads == 0, "rollout_lstm: the fused rollout samples one Discrete head");
-    PFA_REQUIRE(cfg->obs_stride == dims->obs_stride, "rollout_lstm: env obs_stride %d != policy obs_stride %d", cfg->obs_stride,
+    PFA_REQUIRE(cfg, "rollout_lstm_squared: null config");
+    PFA_REQUIRE(cfg->obs_stride == dims->obs_stride, "rollout_lstm_squared: env obs_stride %d != policy obs_stride %d", cfg->obs_stride,
                 dims->obs_stride);
-    PFA_REQUIRE(exp->horizon_T >= 1, "rollout_lstm: horizon must be >= 1");
-    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
-                "rollout_lstm: null experience buffer");
-    PFA_REQUIRE(noise || key, "rollout_lstm: need an explicit noise tensor or a Philox key");
-    PFA_REQUIRE(cfg->num_targets <= kMaxTargets, "rollout_lstm: too many targets");
-    SquaredView v = squared_view(state, *cfg);
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
-    ScopedKernelTimer timer("rollout_lstm_squared", (hipStream_t)stream);
-    PFA_LSTM_DISPATCH_DP(dims->obs_stride,
-                         hipLaunchKernelGGL(rollout_lstm_squared_kernel<DP>, dim3(grid), dim3(kLstmThreads), 0, (hipStream_t)stream,
-                                            v, params, dims->num_actions, (const float4 *)wpack, h, c, *exp, noise, seed, step,
-                                            (long long)env_offset, obs, rewards, terminals, truncations, masks));
-    PFA_LAUNCH_CHECK();
-    return 0;
+    PFA_REQUIRE(cfg->num_targets <= kMaxTargets, "rollout_lstm_squared: too many targets");
+    return launch_rollout_lstm<SquaredRollEnv>("rollout_lstm_squared", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset,
+                                               obs, rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_rollout_lstm_memory(void *state, const pfa_memory_config *cfg, const float *params, const pfa_mlp_dims *dims,
@@ -484,22 +432,13 @@ extern "C" int pfa_rollout_lstm_memory(void *state, const pfa_memory_config *cfg
                                        const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                                        uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     if (int rc = check_lstm_dims(dims)) return rc;
-    PFA_REQUIRE(state && cfg && params && wpack && h && c && exp && obs && rewards && terminals && truncations && masks,
-                "rollout_lstm_memory: null buffer");
-    PFA_REQUIRE(dims->heads == 0 && dims->num_actions == 2, "rollout_lstm_memory: ocean.Memory takes one Discrete(2) action");
+    PFA_REQUIRE(cfg, "rollout_lstm_memory: null config");
+    PFA_REQUIRE(dims->num_actions == 2, "rollout_lstm_memory: ocean.Memory takes one Discrete(2) action");
     PFA_REQUIRE(dims->obs_stride == kMemDP, "rollout_lstm_memory: observation rows are %d floats (got %d)", kMemDP, dims->obs_stride);
     PFA_REQUIRE(cfg->num_envs >= 1 && cfg->mem_length >= 1 && cfg->mem_length <= kMemMaxLen && cfg->tape_rounds >= 2,
                 "rollout_lstm_memory: bad env configuration");
-    PFA_REQUIRE(exp->horizon_T >= 1 && exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
-                "rollout_lstm_memory: bad experience buffers");
-    PFA_REQUIRE(noise || key, "rollout_lstm_memory: need an explicit noise tensor or a Philox key");
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    ScopedKernelTimer timer("rollout_lstm_memory", (hipStream_t)stream);
-    hipLaunchKernelGGL(rollout_lstm_memory_kernel, dim3((unsigned)((cfg->num_envs + 15) / 16)), dim3(kLstmThreads), 0, (hipStream_t)stream,
-                       memory_view(state, *cfg), params, dims->num_actions, (const float4 *)wpack, h, c, *exp, noise, seed, step,
-                       (long long)env_offset, obs, rewards, terminals, truncations, masks);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_rollout_lstm<MemoryRollEnv, kMemDP>("rollout_lstm_memory", state, cfg, params, dims, wpack, h, c, exp, noise, key,
+                                                      env_offset, obs, rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_rollout_lstm_synth(void *state, const pfa_synth_config *cfg, const float *params, const pfa_mlp_dims *dims,
@@ -508,22 +447,9 @@ extern "C" int pfa_rollout_lstm_synth(void *state, const pfa_synth_config *cfg, 
                                       uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     if (int rc = check_lstm_dims(dims)) return rc;
     if (int rc = check_synth_config(cfg)) return rc;
-    PFA_REQUIRE(state && params && wpack && h && c && exp && obs && rewards && terminals && truncations && masks,
-                "rollout_lstm_synth: null buffer");
-    PFA_REQUIRE(dims->heads == 0 && dims->num_actions == cfg->num_actions, "rollout_lstm_synth: the policy must have one Discrete(%d) head",
-                cfg->num_actions);
+    PFA_REQUIRE(dims->num_actions == cfg->num_actions, "rollout_lstm_synth: the policy must have one Discrete(%d) head", cfg->num_actions);
     PFA_REQUIRE(dims->obs_stride == cfg->obs_stride, "rollout_lstm_synth: env obs_stride %d != policy obs_stride %d", cfg->obs_stride,
                 dims->obs_stride);
-    PFA_REQUIRE(exp->horizon_T >= 1 && exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
-                "rollout_lstm_synth: bad experience buffers");
-    PFA_REQUIRE(noise || key, "rollout_lstm_synth: need an explicit noise tensor or a Philox key");
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
-    ScopedKernelTimer timer("rollout_lstm_synth", (hipStream_t)stream);
-    PFA_LSTM_DISPATCH_DP(dims->obs_stride,
-                         hipLaunchKernelGGL(rollout_lstm_synth_kernel<DP>, dim3(grid), dim3(kLstmThreads), 0, (hipStream_t)stream,
-                                            synth_view(state, *cfg), params, dims->num_actions, (const float4 *)wpack, h, c, *exp, noise,
-                                            seed, step, (long long)env_offset, obs, rewards, terminals, truncations, masks));
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_rollout_lstm<SynthRollEnv>("rollout_lstm_synth", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset, obs,
+                                             rewards, terminals, truncations, masks, stream);
 }

@@ -97,14 +97,17 @@ class Engine:
 
     # -------------------------------------------------------------------------------------------- rollout
     def rollout(self, T, noise, key_seed, step0, env_offset):
-        """clean_pufferl.evaluate's loop for a Squared or Memory vecenv: one persistent kernel (csrc/lstm_fused.hip).  The caller has
+        """clean_pufferl.evaluate's loop for a Squared, Memory or Synthetic vecenv: one persistent kernel (csrc/lstm_fused.hip).  The caller has
         made sure the reset-target tape holds the rounds of these T sends and accounts for them afterwards."""
         L = _lib.lib()
         vec, exp, fp = self.vec, self.exp, self.fp
         assert T == exp.horizon
         pack_gates(fp, self.wpack)
         key = _lib.NoiseKey(key_seed, step0)
-        fn = {'Memory': L.pfa_rollout_lstm_memory, 'Synthetic': L.pfa_rollout_lstm_synth}.get(type(vec).__name__, L.pfa_rollout_lstm_squared)   # same signature
+        name = getattr(vec, 'ROLLOUT_LSTM', None)       # the env family's entry point; they share one signature
+        if name is None:
+            raise NotImplementedError(f'{type(vec).__name__} has no fused recurrent rollout kernel')
+        fn = getattr(L, name)
         _lib.check(fn(_lib.ptr(vec.state), C.byref(vec.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
                       _lib.ptr(self.wpack), _lib.ptr(self.lstm_h), _lib.ptr(self.lstm_c), C.byref(exp.c),
                       _lib.ptr(noise), C.byref(key), env_offset, _lib.ptr(vec.obs_buf),

@@ -154,216 +154,6 @@ def _squared_kwargs(creator, args, kwargs):
     return int(d), int(nt)
 
 
-class Squared:
-    """Device-resident vecenv of N ocean Squared envs (backend protocol of pufferlib/vector.py).
-
-    State, live buffers and the reset-target tape are torch device tensors (torch is the allocator); every
-    method only enqueues HIP kernels on torch's current stream.  ``infos`` follow ``info_mode``:
-      'sync'  (default) one tiny D2H per send: exact list of per-episode dicts like Serial/EpisodeStats
-      'lazy'  recv() returns [] and episode statistics are read with ``episode_stats()`` (no per-step sync;
-              this is what pufferlib_amd.clean_pufferl.evaluate uses)
-    """
-    reset = reset
-    step = step
-
-    @property
-    def num_envs(self):
-        return self.agents_per_batch
-
-    def __init__(self, env_creators, env_args, env_kwargs, num_envs, obs_stride=None, info_mode='sync',
-                 env_offset=0, device=None, **kwargs):
-        import torch
-        for k in kwargs:
-            if k not in ('num_workers', 'batch_size', 'zero_copy', 'backend'):
-                raise APIUsageError(f'Invalid argument: {k}')
-        if len(env_creators) != num_envs:
-            raise APIUsageError('env_creators must be a list of length num_envs')
-        specs = {_squared_kwargs(c, a, k) for c, a, k in zip(env_creators, env_args, env_kwargs)}
-        if len(specs) != 1:
-            raise APIUsageError(f'obs/atn space mismatch: all envs must share one Squared configuration, got {specs}')
-        d, nt = specs.pop()
-        self.driver_env = SquaredSpec(d, nt)
-        d, nt = self.driver_env.distance_to_target, self.driver_env.num_targets
-        _lib.require_gpu()
-        self.L = _lib.lib()
-        self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
-        self.emulated = self.driver_env.emulated
-        self.agents_per_env = [1] * num_envs
-        self.agents_per_batch = num_envs
-        self.num_agents = num_envs
-        self.single_observation_space = self.driver_env.single_observation_space
-        self.single_action_space = self.driver_env.single_action_space
-        self.action_space = spaces.MultiDiscrete([8] * num_envs)
-        g = self.driver_env.grid_size
-        self.observation_space = spaces.Box(low=-1, high=1, shape=(num_envs, g, g), dtype=np.float32)
-        self.agent_ids = np.arange(num_envs)
-        self.initialized = False
-        self.flag = RESET
-        self.info_mode = info_mode
-        self.env_offset = int(env_offset)   # global index of local env 0 (multi-GPU sharding)
-
-        self.obs_dim = g * g
-        self.obs_stride = int(obs_stride) if obs_stride is not None else max(16, _round_up(self.obs_dim, 16))
-        self.episode_len = nt * d + 1        # max_ticks steps + the auto-reset row (SURVEY.md App. A.1)
-        self.tape_rounds = 192       # ring capacity: two rollouts of 4 x 96 sends.. (one being consumed + one prefetched)
-        self.cfg = _lib.SquaredConfig(num_envs, d, nt, self.obs_stride, self.tape_rounds)
-        nbytes = self.L.pfa_squared_state_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise APIUsageError(self.L.pfa_last_error().decode())
-        dev = self.device
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.obs_buf = torch.zeros(num_envs, self.obs_stride, dtype=torch.float32, device=dev)
-        self.observations = self.obs_buf[:, :self.obs_dim].unflatten(1, (g, g))   # view, shape (N, g, g)
-        self.driver_env._live_obs = self.obs_buf
-        self.rewards = torch.zeros(num_envs, dtype=torch.float32, device=dev)
-        self.terminals_u8 = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
-        self.truncations_u8 = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
-        self.masks_u8 = torch.ones(num_envs, dtype=torch.uint8, device=dev)
-        self.terminals = self.terminals_u8.view(torch.bool)
-        self.truncations = self.truncations_u8.view(torch.bool)
-        self.masks = self.masks_u8.view(torch.bool)
-        self._actions = torch.zeros(num_envs, dtype=torch.int64, device=dev)
-        self._fin = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
-        self._fin_ret = torch.zeros(num_envs, dtype=torch.float64, device=dev)
-        self._fin_len = torch.zeros(num_envs, dtype=torch.int32, device=dev)
-        self._fin_score = torch.zeros(num_envs, dtype=torch.float64, device=dev)
-        self._stats = torch.zeros(5, dtype=torch.float64, device=dev)   # 4 sums + tape underrun flag (0 for envs without a tape)
-        self.infos = []
-        self.sends = 0            # sends since async_reset
-        self.rounds_filled = 0    # reset rounds drawn into the tape (mirrors the device counter)
-        self.tape_event = None    # recorded by whoever filled tape rounds on ANOTHER stream (the trainer's prefetch)
-
-    def _wait_tape(self):
-        """Order the current stream behind a tape fill enqueued on a side stream: `rounds_filled` (host mirror) already counts
-        those rounds, so every consumer of the tape — send(), a fused rollout, async_reset() — must wait for the fill itself."""
-        if self.tape_event is not None:
-            import torch
-            torch.cuda.current_stream().wait_event(self.tape_event)
-
-    # -- tape bookkeeping (host mirror; the stream position itself lives on device) --------------------
-    def _rounds_needed(self, upto_send):
-        """Number of reset rounds consumed by sends 1..upto_send (every env resets on sends k*episode_len)."""
-        return upto_send // self.episode_len
-
-    @property
-    def max_sends_per_tape(self):
-        """Sends whose reset rounds one ensure_tape() call may draw ahead (half the ring: the other half may still be in use)."""
-        return max(1, (self.tape_rounds // 2) * self.episode_len)
-
-    def ensure_tape(self, extra_sends):
-        self._wait_tape()
-        need = self._rounds_needed(self.sends + extra_sends)
-        consumed = self._rounds_needed(self.sends)
-        if need - consumed > self.tape_rounds:
-            raise APIUsageError(f'{extra_sends} sends need {need - consumed} reset rounds; tape holds {self.tape_rounds}')
-        if need > self.rounds_filled:
-            _lib.check(self.L.pfa_squared_fill_tape(_lib.ptr(self.state), C.byref(self.cfg), need - self.rounds_filled,
-                                                    _lib.stream_handle()), 'fill_tape')
-            self.rounds_filled = need
-
-    def _live(self):
-        return (_lib.ptr(self.obs_buf), _lib.ptr(self.rewards), _lib.ptr(self.terminals_u8),
-                _lib.ptr(self.truncations_u8), _lib.ptr(self.masks_u8))
-
-    # -- protocol ---------------------------------------------------------------------------------------
-    def async_reset(self, seed=42):
-        self.flag = RECV
-        seeds = make_seeds(seed, self.num_agents)
-        if any(s != seeds[0] + i for i, s in enumerate(seeds)):
-            raise APIUsageError('pufferlib_amd.vector.Squared needs consecutive seeds (seed + env index)')
-        self._wait_tape()
-        self.tape_event = None
-        _lib.check(self.L.pfa_squared_async_reset(_lib.ptr(self.state), C.byref(self.cfg), int(seeds[0]), *self._live(),
-                                                  _lib.stream_handle()), 'async_reset')
-        self.sends = 0
-        self.rounds_filled = 0
-        self.infos = []
-
-    def send(self, actions):
-        import torch
-        send_precheck(self, actions)
-        if not torch.is_tensor(actions):
-            a = np.asarray(actions)
-            if not self.initialized and not self.action_space.contains(a):
-                raise APIUsageError('Actions do not match action space')
-            actions = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int64))
-        elif not self.initialized:
-            if actions.shape != (self.num_agents,) or actions.dtype not in (torch.int64, torch.int32):
-                raise APIUsageError('Actions do not match action space')
-        self.initialized = True
-        self._actions.copy_(actions.reshape(-1), non_blocking=True)
-        self.ensure_tape(1)
-        _lib.check(self.L.pfa_squared_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(self._actions), *self._live(),
-                                           _lib.stream_handle()), 'send')
-        self.sends += 1
-        self.infos = self._collect_infos() if self.info_mode == 'sync' else []
-
-    def device_send(self, actions):
-        """send() for a device int64 tensor of actions, no protocol bookkeeping and no host sync (rollout loops of policies
-        without a fused rollout kernel); the caller has drawn the reset rounds (ensure_tape)."""
-        self._wait_tape()
-        _lib.check(self.L.pfa_squared_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
-                                           _lib.stream_handle()), 'send')
-        self.sends += 1
-
-    def recv(self):
-        recv_precheck(self)
-        return (self.observations, self.rewards, self.terminals, self.truncations, self.infos, self.agent_ids,
-                self.masks)
-
-    def close(self):
-        self.flag = CLOSE
-
-    # -- infos -------------------------------------------------------------------------------------------
-    def _collect_infos(self):
-        # every env of a Squared vecenv finishes on the same sends: skip the readback on the others
-        if self.sends % self.episode_len != self.episode_len - 1:
-            return []
-        _lib.check(self.L.pfa_squared_last_infos(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(self._fin),
-                                                 _lib.ptr(self._fin_ret), _lib.ptr(self._fin_len),
-                                                 _lib.ptr(self._fin_score), _lib.stream_handle()), 'last_infos')
-        fin = self._fin.cpu().numpy().astype(bool)
-        if not fin.any():
-            return []
-        ret, ln, sc = self._fin_ret.cpu().numpy(), self._fin_len.cpu().numpy(), self._fin_score.cpu().numpy()
-        return [dict(episode_return=float(ret[i]), episode_length=int(ln[i]), score=float(sc[i]))
-                for i in np.nonzero(fin)[0]]
-
-    def episode_stats(self, reset=True):
-        """(count, mean episode_return, mean episode_length, mean score) over episodes finished since the last
-        reset of the accumulators — what clean_pufferl.evaluate reports (clean_pufferl.py:144-152)."""
-        _lib.check(self.L.pfa_squared_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(self._stats),
-                                                    1 if reset else 0, _lib.stream_handle()), 'episode_stats')
-        return self._stats[:4]      # [4] = tape underrun flag: read by the trainer from the same buffer (stats_with_flag)
-
-    stats_from_sums = staticmethod(episode_means)
-
-    def stats_with_flag(self, reset=True, out=None):
-        """The four sums + the tape underrun flag; `out`: a 5-element f64 buffer the kernel writes instead of the vecenv's own
-        (the trainer's pinned readback buffer: no device-to-host copy launch behind the kernel)."""
-        if out is not None:
-            _lib.check(self.L.pfa_squared_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out),
-                                                        1 if reset else 0, _lib.stream_handle()), 'episode_stats')
-            return out
-        self.episode_stats(reset)
-        return self._stats
-
-    # -- test introspection -------------------------------------------------------------------------------
-    def debug_targets(self):
-        import torch
-        out = torch.zeros(self.num_agents, self.cfg.num_targets, dtype=torch.int32, device=self.device)
-        _lib.check(self.L.pfa_squared_debug_targets(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out),
-                                                    _lib.stream_handle()), 'debug_targets')
-        return out.cpu().numpy()
-
-    def debug_stream_pos(self):
-        import torch
-        out = torch.zeros(1, dtype=torch.int64, device=self.device)
-        _lib.check(self.L.pfa_squared_debug_stream_pos(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out),
-                                                       _lib.stream_handle()), 'debug_stream_pos')
-        return int(out.item())
-
-
 class _SimpleSpec:
     """What ``driver_env`` exposes to policies (models.py:26-37) and clean_pufferl for a one-value-observation ocean env."""
 
@@ -411,16 +201,18 @@ class _DeviceVecEnv:
     buffers as torch device tensors aliased by recv() (like Serial's numpy buffers, vector.py:158-162), RESET->RECV->SEND
     state machine, ``info_mode`` 'sync' (exact per-episode info dicts, one small D2H on the sends that finish episodes) or
     'lazy' (recv() returns [], statistics through ``episode_stats``).  Subclasses provide the kernels:
-    ``_k_reset(seed)``, ``_k_send(actions)``, ``_k_stats(reset)``, ``_k_infos()`` and ``_finishing_send(sends)``."""
+    ``_k_reset(seed)``, ``_k_send(actions)``, ``_k_stats(reset, out)``, ``_k_infos()`` and ``_finishing_send(sends)``."""
     reset = reset
     step = step
     obs_stride = 16
+    ROLLOUT_LSTM = None     # name of the family's fused recurrent rollout entry point (lstm.Engine.rollout), None: it has none
     FAMILY = ''
     NAMES = ()
     DEFAULTS = ()
     SEEDED = False          # whether the env family reads the seeds async_reset is given
     AGENTS_PER_ENV = 1      # agent rows per env, env-major (PettingZoo emulation order, emulation.py:325-345)
     OBS_U8 = False          # live observation buffer of bytes (frame envs) instead of floats
+    CONFIG_NAME = ''        # how the "share one ... configuration" error names the family's settings
 
     @property
     def num_envs(self):
@@ -433,10 +225,9 @@ class _DeviceVecEnv:
                 raise APIUsageError(f'Invalid argument: {k}')
         if len(env_creators) != num_envs:
             raise APIUsageError('env_creators must be a list of length num_envs')
-        specs = {_creator_kwargs(c, a, k, self.NAMES, self.DEFAULTS, self.FAMILY)
-                 for c, a, k in zip(env_creators, env_args, env_kwargs)}
+        specs = {self._creator_spec(c, a, k) for c, a, k in zip(env_creators, env_args, env_kwargs)}
         if len(specs) != 1:
-            raise APIUsageError(f'obs/atn space mismatch: all envs must share one configuration, got {specs}')
+            raise APIUsageError(f'obs/atn space mismatch: all envs must share one {self.CONFIG_NAME}configuration, got {specs}')
         _lib.require_gpu()
         self.L = _lib.lib()
         self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
@@ -480,6 +271,9 @@ class _DeviceVecEnv:
         self.sends = 0
         self._alloc_state()
 
+    def _creator_spec(self, creator, args, kwargs):
+        return _creator_kwargs(creator, args, kwargs, self.NAMES, self.DEFAULTS, self.FAMILY)
+
     def _live(self):
         return (_lib.ptr(self.obs_buf), _lib.ptr(self.rewards), _lib.ptr(self.terminals_u8), _lib.ptr(self.truncations_u8),
                 _lib.ptr(self.masks_u8))
@@ -514,8 +308,12 @@ class _DeviceVecEnv:
                 raise APIUsageError('Actions do not match action space')
         self.initialized = True
         self._actions.copy_(actions.reshape(-1), non_blocking=True)
+        self._before_send()
         self.device_send(self._actions)
         self.infos = self._collect_infos() if self.info_mode == 'sync' else []
+
+    def _before_send(self):
+        """What send() does for the caller that device_send() leaves to it."""
 
     def recv(self):
         recv_precheck(self)
@@ -529,20 +327,152 @@ class _DeviceVecEnv:
             return []
         self._k_infos()
         fin = self._fin.cpu().numpy().astype(bool)
+        if not fin.any():
+            return []
         ret, ln, sc = self._fin_ret.cpu().numpy(), self._fin_len.cpu().numpy(), self._fin_score.cpu().numpy()
         return [dict(episode_return=float(ret[i]), episode_length=int(ln[i]), score=float(sc[i])) for i in np.nonzero(fin)[0]]
 
     def episode_stats(self, reset=True):
         """(count, sum episode_return, sum episode_length, sum score) of the episodes finished since the last reset of the
         accumulators, as a device f64 tensor — what clean_pufferl.evaluate averages (clean_pufferl.py:127-137)."""
-        self._k_stats(1 if reset else 0)
+        self._k_stats(1 if reset else 0, self._stats)
         return self._stats[:4]      # [4] = tape underrun flag: read by the trainer from the same buffer (stats_with_flag)
 
     stats_from_sums = staticmethod(episode_means)
 
-    def stats_with_flag(self, reset=True):
-        self.episode_stats(reset)
-        return self._stats
+    def stats_with_flag(self, reset=True, out=None):
+        """The four sums + the tape underrun flag; `out`: a 5-element f64 buffer the kernel writes instead of the vecenv's own
+        (the trainer's pinned readback buffer: no device-to-host copy launch behind the kernel)."""
+        out = self._stats if out is None else out
+        self._k_stats(1 if reset else 0, out)
+        return out
+
+
+class _ResetTape:
+    """Mixin of the device families whose resets consume random numbers that do not depend on actions: they are drawn ahead of
+    the sends, one round per reset of all envs, into a ring of ``tape_rounds`` rounds in the device state.  This is the host
+    mirror of the ring (the stream position itself lives on device).  The family provides ``_k_fill(rounds)``, ``episode_len``
+    and ``tape_rounds``.  Only these families have ``ensure_tape``: callers test for it."""
+    ROUNDS_AT_RESET = 0     # rounds async_reset itself draws and consumes
+    RING_SPARE = 0          # rounds of the ring one ensure_tape() call must leave alone
+    FILL_HALVES = False     # fill at most half the ring per launch
+
+    def _tape_reset(self):
+        """After the family's async_reset kernel: nothing sent, nothing drawn ahead."""
+        self.sends = 0
+        self.rounds_filled = self.ROUNDS_AT_RESET    # rounds drawn into the tape (mirrors the device counter)
+        self.tape_event = None
+
+    def _wait_tape(self):
+        """Order the current stream behind a tape fill enqueued on a side stream (``tape_event``, recorded by whoever filled
+        there: the trainer's prefetch): `rounds_filled` (host mirror) already counts those rounds, so every consumer of the
+        tape — send(), a fused rollout, async_reset() — must wait for the fill itself."""
+        if self.tape_event is not None:
+            import torch
+            torch.cuda.current_stream().wait_event(self.tape_event)
+
+    def _rounds_needed(self, upto_send):
+        """Rounds consumed by async_reset and sends 1..upto_send (every env resets on sends k*episode_len)."""
+        return self.ROUNDS_AT_RESET + upto_send // self.episode_len
+
+    @property
+    def max_sends_per_tape(self):
+        """Sends whose reset rounds one ensure_tape() call may draw ahead (half the ring: the other half may still be in use)."""
+        return max(1, (self.tape_rounds // 2) * self.episode_len)
+
+    def ensure_tape(self, extra_sends):
+        self._wait_tape()
+        need = self._rounds_needed(self.sends + extra_sends)
+        asked = need - self._rounds_needed(self.sends)
+        if asked > self.tape_rounds - self.RING_SPARE:
+            raise APIUsageError(f'{extra_sends} sends need {asked} reset rounds; tape holds {self.tape_rounds}')
+        while need > self.rounds_filled:
+            n = need - self.rounds_filled
+            if self.FILL_HALVES:
+                n = min(n, self.tape_rounds // 2)
+            self._k_fill(n)
+            self.rounds_filled += n
+
+
+class Squared(_ResetTape, _DeviceVecEnv):
+    """Device-resident vecenv of N ocean Squared envs (csrc/squared.hip).  State, live buffers and the reset-target tape are
+    torch device tensors (torch is the allocator); every method only enqueues HIP kernels on torch's current stream.  It has a
+    fused rollout kernel for either policy; the trainer draws the next rollout's tape rounds on a side stream (``tape_event``)."""
+    SEEDED = True
+    CONFIG_NAME = 'Squared '
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_squared'
+
+    def __init__(self, env_creators, env_args, env_kwargs, num_envs, obs_stride=None, **kwargs):
+        self._obs_stride_arg = obs_stride
+        super().__init__(env_creators, env_args, env_kwargs, num_envs, **kwargs)
+
+    def _creator_spec(self, creator, args, kwargs):
+        return _squared_kwargs(creator, args, kwargs)
+
+    def _spec(self, d, nt):
+        spec = SquaredSpec(d, nt)
+        self.obs_stride = int(self._obs_stride_arg) if self._obs_stride_arg is not None else max(16, _round_up(spec.grid_size ** 2, 16))
+        return spec
+
+    def _alloc_state(self):
+        import torch
+        sp = self.driver_env
+        g = sp.grid_size
+        self.obs_dim = g * g
+        self.observations = self.obs_buf[:, :self.obs_dim].unflatten(1, (g, g))   # view, shape (N, g, g)
+        sp._live_obs = self.obs_buf
+        self.episode_len = sp.num_targets * sp.distance_to_target + 1   # max_ticks steps + the auto-reset row (SURVEY.md App. A.1)
+        self.tape_rounds = 192       # ring capacity: two rollouts of 4 x 96 sends.. (one being consumed + one prefetched)
+        self.cfg = _lib.SquaredConfig(self.num_agents, sp.distance_to_target, sp.num_targets, self.obs_stride, self.tape_rounds)
+        nbytes = self.L.pfa_squared_state_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise APIUsageError(self.L.pfa_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._tape_reset()
+
+    def _finishing_send(self, sends):
+        return sends % self.episode_len == self.episode_len - 1
+
+    def _k_fill(self, rounds):
+        _lib.check(self.L.pfa_squared_fill_tape(_lib.ptr(self.state), C.byref(self.cfg), rounds, _lib.stream_handle()), 'fill_tape')
+
+    def _k_reset(self, seed):
+        self._wait_tape()
+        _lib.check(self.L.pfa_squared_async_reset(_lib.ptr(self.state), C.byref(self.cfg), seed, *self._live(), _lib.stream_handle()),
+                   'async_reset')
+        self._tape_reset()
+
+    def _before_send(self):
+        self.ensure_tape(1)
+
+    def _k_send(self, actions):
+        """The caller has drawn the reset rounds (send() does; rollout loops call ensure_tape for many sends at once)."""
+        self._wait_tape()
+        _lib.check(self.L.pfa_squared_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
+                                           _lib.stream_handle()), 'send')
+
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_squared_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
+                                                    _lib.stream_handle()), 'episode_stats')
+
+    def _k_infos(self):
+        _lib.check(self.L.pfa_squared_last_infos(_lib.ptr(self.state), C.byref(self.cfg), *self._fin_ptrs(), _lib.stream_handle()),
+                   'last_infos')
+
+    # -- test introspection -------------------------------------------------------------------------------
+    def debug_targets(self):
+        import torch
+        out = torch.zeros(self.num_agents, self.cfg.num_targets, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.pfa_squared_debug_targets(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out),
+                                                    _lib.stream_handle()), 'debug_targets')
+        return out.cpu().numpy()
+
+    def debug_stream_pos(self):
+        import torch
+        out = torch.zeros(1, dtype=torch.int64, device=self.device)
+        _lib.check(self.L.pfa_squared_debug_stream_pos(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out),
+                                                       _lib.stream_handle()), 'debug_stream_pos')
+        return int(out.item())
 
 
 def make_stochastic(p=0.7, horizon=100, **kwargs):
@@ -585,8 +515,8 @@ class Stochastic(_DeviceVecEnv):
         _lib.check(self.L.pfa_stochastic_send(_lib.ptr(self.state), self.num_agents, self.p, self.horizon, _lib.ptr(actions),
                                               *self._live(), _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset):
-        _lib.check(self.L.pfa_stochastic_episode_stats(_lib.ptr(self.state), self.num_agents, _lib.ptr(self._stats), reset,
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_stochastic_episode_stats(_lib.ptr(self.state), self.num_agents, _lib.ptr(out), reset,
                                                        _lib.stream_handle()), 'episode_stats')
 
     def _k_infos(self):
@@ -615,13 +545,14 @@ class MemorySpec(_SimpleSpec):
         self.horizon = 2 * self.mem_length + self.mem_delay
 
 
-class Memory(_DeviceVecEnv):
+class Memory(_ResetTape, _DeviceVecEnv):
     """Device-resident vecenv of N ocean Memory envs (csrc/memory.hip) — the env family that needs the recurrent policy.
     The solutions of future episodes come from the tape the backend keeps ahead of the sends (numpy's process-global legacy
-    stream, which does not depend on actions).  There is no fused rollout kernel for this env: clean_pufferl.evaluate steps
-    it through ``device_send`` (no host sync per step)."""
+    stream, which does not depend on actions).  With the recurrent policy clean_pufferl.evaluate runs it in the fused rollout
+    kernel (csrc/lstm_fused.hip); with the MLP policy it steps it through ``device_send`` (no host sync per step)."""
     FAMILY, NAMES, DEFAULTS = 'memory', ('mem_length', 'mem_delay'), (2, 2)
     SEEDED = True
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_memory'
 
     def _spec(self, mem_length, mem_delay):
         return MemorySpec(mem_length, mem_delay)
@@ -636,24 +567,10 @@ class Memory(_DeviceVecEnv):
         if nbytes == 0:
             raise APIUsageError(self.L.pfa_last_error().decode())
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self.rounds_filled = 0
+        self._tape_reset()
 
-    def _rounds_needed(self, upto_send):
-        """Reset rounds consumed by sends 1..upto_send: every env resets on sends k*horizon."""
-        return upto_send // self.episode_len
-
-    @property
-    def max_sends_per_tape(self):
-        return max(1, (self.tape_rounds // 2) * self.episode_len)
-
-    def ensure_tape(self, extra_sends):
-        need = self._rounds_needed(self.sends + extra_sends)
-        if need - self._rounds_needed(self.sends) > self.tape_rounds:
-            raise APIUsageError(f'{extra_sends} sends need more reset rounds than the tape holds ({self.tape_rounds})')
-        if need > self.rounds_filled:
-            _lib.check(self.L.pfa_memory_fill_tape(_lib.ptr(self.state), C.byref(self.cfg), need - self.rounds_filled,
-                                                   _lib.stream_handle()), 'fill_tape')
-            self.rounds_filled = need
+    def _k_fill(self, rounds):
+        _lib.check(self.L.pfa_memory_fill_tape(_lib.ptr(self.state), C.byref(self.cfg), rounds, _lib.stream_handle()), 'fill_tape')
 
     def _finishing_send(self, sends):
         return sends % self.episode_len == self.episode_len - 1
@@ -661,16 +578,15 @@ class Memory(_DeviceVecEnv):
     def _k_reset(self, seed):
         _lib.check(self.L.pfa_memory_async_reset(_lib.ptr(self.state), C.byref(self.cfg), seed, *self._live(), _lib.stream_handle()),
                    'async_reset')
-        self.sends = 0
-        self.rounds_filled = 0
+        self._tape_reset()
 
     def _k_send(self, actions):
         self.ensure_tape(1)
         _lib.check(self.L.pfa_memory_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                           _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset):
-        _lib.check(self.L.pfa_memory_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(self._stats), reset,
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_memory_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
                                                    _lib.stream_handle()), 'episode_stats')
 
     def _k_infos(self):
@@ -717,7 +633,7 @@ class SpacesSpec:
         pass
 
 
-class Spaces(_DeviceVecEnv):
+class Spaces(_ResetTape, _DeviceVecEnv):
     """Device-resident vecenv of N ocean Spaces envs (csrc/spaces.hip): structured observation (108-byte emulated rows, kept
     on device as rows of 128 floats holding the byte values — what models.Default's ``observations.float()`` computes) and a
     MultiDiscrete([2, 2]) action.  Observations come from numpy's process-global legacy generator, whose data-dependent
@@ -727,6 +643,9 @@ class Spaces(_DeviceVecEnv):
     FAMILY, NAMES, DEFAULTS = 'spaces', (), ()
     SEEDED = False
     obs_stride = 128
+    ROUNDS_AT_RESET = 1     # async_reset shows round 0
+    RING_SPARE = 1
+    FILL_HALVES = True
 
     def _spec(self):
         return SpacesSpec()
@@ -742,24 +661,10 @@ class Spaces(_DeviceVecEnv):
         if nbytes == 0:
             raise APIUsageError(self.L.pfa_last_error().decode())
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self.rounds_filled = 1
+        self._tape_reset()
 
-    def _rounds_needed(self, upto_send):
-        """Tape rounds consumed by async_reset (round 0) and sends 1..upto_send (every second send is a reset row)."""
-        return 1 + upto_send // 2
-
-    @property
-    def max_sends_per_tape(self):
-        return max(2, self.tape_rounds)          # a reset round every second send: half the ring
-
-    def ensure_tape(self, extra_sends):
-        need = self._rounds_needed(self.sends + extra_sends)
-        if need - self._rounds_needed(self.sends) >= self.tape_rounds:
-            raise APIUsageError(f'{extra_sends} sends need more reset rounds than the tape holds ({self.tape_rounds})')
-        while need > self.rounds_filled:
-            n = min(need - self.rounds_filled, self.tape_rounds // 2)
-            _lib.check(self.L.pfa_spaces_fill_tape(_lib.ptr(self.state), C.byref(self.cfg), n, _lib.stream_handle()), 'fill_tape')
-            self.rounds_filled += n
+    def _k_fill(self, rounds):
+        _lib.check(self.L.pfa_spaces_fill_tape(_lib.ptr(self.state), C.byref(self.cfg), rounds, _lib.stream_handle()), 'fill_tape')
 
     def _finishing_send(self, sends):
         return sends % 2 == 1
@@ -767,16 +672,15 @@ class Spaces(_DeviceVecEnv):
     def _k_reset(self, seed):
         _lib.check(self.L.pfa_spaces_async_reset(_lib.ptr(self.state), C.byref(self.cfg), seed, *self._live(), _lib.stream_handle()),
                    'async_reset')
-        self.sends = 0
-        self.rounds_filled = 1
+        self._tape_reset()
 
     def _k_send(self, actions):
         self.ensure_tape(1)
         _lib.check(self.L.pfa_spaces_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                           _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset):
-        _lib.check(self.L.pfa_spaces_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(self._stats), reset,
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_spaces_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
                                                    _lib.stream_handle()), 'episode_stats')
 
     def _k_infos(self):
@@ -827,6 +731,7 @@ class Synthetic(_DeviceVecEnv):
     of the reference tree, so there is nothing to be bit-exact with on the env side."""
     FAMILY, NAMES, DEFAULTS = 'synthetic', ('obs_values', 'num_actions', 'episode_length', 'obs_high'), (160, 7, 100, 10)
     SEEDED = True
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_synth'
 
     def _spec(self, obs_values, num_actions, episode_length, obs_high):
         from .cleanrl import obs_stride_for
@@ -859,8 +764,8 @@ class Synthetic(_DeviceVecEnv):
         _lib.check(self.L.pfa_synth_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                          _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset):
-        _lib.check(self.L.pfa_synth_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(self._stats), reset,
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_synth_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
                                                   _lib.stream_handle()), 'episode_stats')
 
     def _k_infos(self):
@@ -891,6 +796,7 @@ class Frames(Synthetic):
     reference tree (parity unpinned), so the workload keeps its observation / action shapes."""
     FAMILY, NAMES, DEFAULTS = 'frames', ('framestack', 'num_actions', 'episode_length'), (4, 4, 100)
     OBS_U8 = True
+    ROLLOUT_LSTM = None     # byte rows: a recurrent policy over frames is a conv LSTM, which runs on the GEMM-path engine
 
     def _spec(self, framestack, num_actions, episode_length):
         self.obs_stride = int(framestack) * 84 * 84            # bytes per row
@@ -967,8 +873,8 @@ class Bandit(_DeviceVecEnv):
         _lib.check(self.L.pfa_bandit_send(_lib.ptr(self.state), self.num_agents, self.solution, self.scale, _lib.ptr(self.noise),
                                           _lib.ptr(actions), *self._live(), _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset):
-        _lib.check(self.L.pfa_bandit_episode_stats(_lib.ptr(self.state), self.num_agents, _lib.ptr(self._stats), reset,
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_bandit_episode_stats(_lib.ptr(self.state), self.num_agents, _lib.ptr(out), reset,
                                                    _lib.stream_handle()), 'episode_stats')
 
     def _k_infos(self):
@@ -1017,8 +923,8 @@ class Multiagent(_DeviceVecEnv):
         _lib.check(self.L.pfa_multiagent_send(_lib.ptr(self.state), self.env_count, _lib.ptr(actions), *self._live(),
                                               _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset):
-        _lib.check(self.L.pfa_multiagent_episode_stats(_lib.ptr(self.state), self.env_count, _lib.ptr(self._stats), reset,
+    def _k_stats(self, reset, out):
+        _lib.check(self.L.pfa_multiagent_episode_stats(_lib.ptr(self.state), self.env_count, _lib.ptr(out), reset,
                                                        _lib.stream_handle()), 'episode_stats')
 
     def _collect_infos(self):
