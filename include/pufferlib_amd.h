@@ -663,23 +663,33 @@ int pfa_dist_info(int64_t *out8);
  *   mode 1 im2col, f32      ptr = NHWC activations [n][IH][IW][IC]; m = (n, oy, ox), k = (ky*KW + kx)*IC + ic
  *   mode 2 im2col, uint8    ptr = NCHW frames [n][IC][IH][IW];      m = (n, oy, ox), k = (ic*KH + ky)*KW + kx, the byte as a float 0..255
  *                           (`observations / 255.0`, models.py:150, rides in the other operand: pack_conv / perm 3 below)
+ *   mode 4 im2col, uint8, strided: ptr = frames of frame_bytes bytes in any channel order, byte (ic, y, x) at ic*sc + y*sy + x*sx
+ *                           (CHW: sc = H*W, sy = d*W, sx = d; HWC: sc = 1, sy = d*W*C, sx = d*C; d = the `[::d, ::d]` downsample of
+ *                           models.py:148); m = (n, oy, ox), k = (ky*KW + kx)*IC + ic, K a multiple of 16; HWC with IC = 4 loads one
+ *                           32-bit word per pixel, everything else bytes.  `/ 255.0` as in mode 2: pack_conv u8_order 2 / perm 5
  *   mode 3 col2im (for dX)  ptr = NHWC dOut [n][OH][OW][OC]; m = INPUT pixel (n, y, x); runs as S*S phases (y mod S, x mod S), each
- *                           contracting over the (KH/S)(KW/S) taps that reach it: k = (jy*(KW/S) + jx)*OC + oc, tap (py + jy*S, px + jx*S)
+ *                           contracting over the (KH/S)(KW/S) taps that reach it: k = (jy*(KW/S) + jx)*OC + oc, tap (py + jy*S, px + jx*S).
+ *                           IH, IW need not be multiples of S (phases of ceil(IH/S) x ceil(IW/S) slots, those past the edge dropped);
+ *                           pixels no window covers receive exactly 0
  * pfa_igemm_rows:    C[m][n] = epilogue(sum_k A(m,k) B[n][k]) with B row-major [N][ldb] (k contiguous; mode 3: [S*S][N][ldb], K =
  *                    KH*KW*OC in total), epilogue 0 none, 1 + bias[n], 2 relu(+ bias[n]), 3 zero where mask[m][n] <= 0 (relu' read
  *                    where the forward left it).  N a multiple of 16, the contraction length (per phase) of 16.
  * pfa_igemm_weights: out (+)= sum_m A(m,k) D[m][n] scattered to torch's parameter layout: perm 0 [k][n], 1 Linear [n][k],
- *                    2 conv [oc=n][ic][ky][kx] from mode-1 k order, 3 the same from mode-2 k order divided by 255, 4 Linear behind an NCHW
+ *                    2 conv [oc=n][ic][ky][kx] from mode-1 k order, 3 the same from mode-2 k order divided by 255, 5 from mode-4 k order
+ *                    (= mode 1's) divided by 255, 4 Linear behind an NCHW
  *                    Flatten from NHWC rows (IC, IH, IW of the operand = the flattened tensor); bias_out (nullable) (+)= the column
  *                    sums of D (the bias gradient, from the same pass over D); split over rows, f64 reduction of the splits
  *                    (deterministic).  workspace >= pfa_igemm_weights_workspace_bytes(M, K, N).
  * pfa_colsum:        out[n] (+)= sum_m D[m][n] on its own, f64, deterministic.
  * pfa_cnn_pack_conv / pfa_cnn_transpose: torch weights -> the matrices the loaders' patch orders need (after every optimizer
- *                    step): forward B [OC][k] (u8_order: torch's own order, weights / 255), dX B [S*S][IC][(KH/S)(KW/S)*OC] (nullable);
+ *                    step): forward B [OC][k] (u8_order 1: torch's own order, weights / 255; 2: mode 4's order, weights / 255), dX B [S*S][IC][(KH/S)(KW/S)*OC] (nullable);
  *                    Linear [N][K] -> [K][N] (B of its dX).
  * pfa_cnn_heads_sample / pfa_cnn_heads_loss (csrc/cnn_heads.hip): decode_actions + sample_logits, and the PPO loss with its
- *                    gradients w.r.t. the head outputs [rows][16] and the hidden vector [rows][512], for a chunk
+ *                    gradients w.r.t. the head outputs [rows][16] and the hidden vector [rows][hidden] (512 for the unsuffixed entry points), for a chunk
  *                    [q0, q0 + rows) of minibatch mb; loss_pairs16 as in pfa_ppo_mlp_grad (accumulate != 0 adds chunks up).
+ *                    pfa_cnn_heads_sample_w / pfa_cnn_heads_loss_w: the same kernels at hidden width `hidden` (a multiple of 16 up to
+ *                    1024; the unsuffixed entry points are these at 512).  Up to 15 actions; wider action sets go through
+ *                    pfa_heads_rows_* below on head outputs computed by pfa_igemm_rows.
  * pfa_cnn_gather_frames: the frames of such a chunk, contiguous.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -688,6 +698,7 @@ typedef struct {
     const void *ptr;
     int64_t lda;                                      /* dense only */
     int32_t IC, IH, IW, OC, OH, OW, KH, KW, S;        /* conv geometry (valid padding) */
+    int32_t sc, sy, sx, frame_bytes;                  /* mode 4 only (0 otherwise): byte strides of channel / row / column, bytes per frame */
 } pfa_igemm_operand;
 int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
                    int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, pfa_stream_t stream);
@@ -712,11 +723,18 @@ int pfa_cnn_pack_fc(const float *w, int32_t N, int32_t channels, int32_t hw, flo
 int pfa_cnn_heads_sample(const float *h, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
                          const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
                          int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream);
+int pfa_cnn_heads_sample_w(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+                           const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
+                           int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream);
 size_t pfa_cnn_heads_loss_workspace_bytes(void);
 int pfa_cnn_heads_loss(const float *h, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
                        const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
                        const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
                        float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream);
+int pfa_cnn_heads_loss_w(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
+                         const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
+                         const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
+                         float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream);
 int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t batch_rows, int32_t mb, const pfa_ppo_hparams *hp,
                           int64_t q0, int64_t rows, uint8_t *out, pfa_stream_t stream);
 

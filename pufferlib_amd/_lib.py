@@ -98,7 +98,8 @@ class SynthConfig(C.Structure):
 
 class IgemmOperand(C.Structure):
     _fields_ = [('mode', C.c_int32), ('reserved', C.c_int32), ('ptr', C.c_void_p), ('lda', C.c_int64), ('IC', C.c_int32), ('IH', C.c_int32),
-                ('IW', C.c_int32), ('OC', C.c_int32), ('OH', C.c_int32), ('OW', C.c_int32), ('KH', C.c_int32), ('KW', C.c_int32), ('S', C.c_int32)]
+                ('IW', C.c_int32), ('OC', C.c_int32), ('OH', C.c_int32), ('OW', C.c_int32), ('KH', C.c_int32), ('KW', C.c_int32), ('S', C.c_int32),
+                ('sc', C.c_int32), ('sy', C.c_int32), ('sx', C.c_int32), ('frame_bytes', C.c_int32)]   # mode 4 (strided uint8 frames) only
 
 
 class MlpDims(C.Structure):
@@ -284,6 +285,9 @@ _SIGNATURES = {
     'pfa_cnn_transpose': (C.c_int, [P, C.c_int32, C.c_int32, P, P]),
     'pfa_cnn_pack_fc': (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     'pfa_cnn_heads_sample': (C.c_int, [P, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
+    'pfa_cnn_heads_sample_w': (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
+    'pfa_cnn_heads_loss_w': (C.c_int, [P, C.c_int32, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P, P, C.c_int32,
+                                       C.POINTER(PpoHparams), P, C.c_int64, P, P, P, C.c_int32, P, P]),
     'pfa_cnn_heads_loss_workspace_bytes': (C.c_size_t, []),
     'pfa_cnn_heads_loss': (C.c_int, [P, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P, P, C.c_int32,
                                      C.POINTER(PpoHparams), P, C.c_int64, P, P, P, C.c_int32, P, P]),

@@ -286,16 +286,20 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
         else:
             policy = Policy(policy, seed=config.seed)     # e.g. the reference's cleanrl.Policy(models.Default)
     recurrent = isinstance(policy, RecurrentPolicy)
-    from .models import find_cnn
+    from .models import conv_geometry_of, find_cnn, set_conv_obs_shape
     conv = find_cnn(policy) is not None
     if conv:
         space = vecenv.single_observation_space
         if not (host_mode or isinstance(vecenv, Frames)):
-            raise NotImplementedError('models.Convolutional reads uint8 (framestack, 84, 84) frames: a host vecenv or vector.Frames')
-        if np.dtype(space.dtype) != np.uint8 or tuple(space.shape[-2:]) != (84, 84):
-            raise NotImplementedError(f'models.Convolutional reads uint8 (framestack, 84, 84) frames, the env shows {space.dtype} {space.shape}')
+            raise NotImplementedError('models.Convolutional reads uint8 frames: a host vecenv or vector.Frames')
+        if np.dtype(space.dtype) != np.uint8 or len(space.shape) != 3:
+            raise NotImplementedError(f'models.Convolutional reads 3-D uint8 frames, the env shows {space.dtype} {space.shape}')
+        # the frame shape is not in the weights: hand the env's to the policy (a module built elsewhere has none recorded), then check
+        # that channel count and flat_size agree with it (ValueError with both numbers otherwise)
+        set_conv_obs_shape(policy, space.shape)
+        conv_geometry_of(policy)
     if isinstance(vecenv, Frames) and not conv:
-        raise NotImplementedError('vector.Frames shows uint8 (framestack, 84, 84) observations: use models.Convolutional')
+        raise NotImplementedError('vector.Frames shows uint8 frame observations: use models.Convolutional')
     if recurrent and isinstance(vecenv, Stochastic):
         raise NotImplementedError('the device-resident Stochastic vecenv has a fused rollout for the MLP policy only '
                                   '(ocean.Stochastic: "do not use a policy with memory", ocean.py:534)')

@@ -8,7 +8,8 @@ the value through the GEMM path (pufferlib_amd.general.Evaluator) for every poli
 gradients of these quantities are computed by pufferlib_amd.clean_pufferl.train()'s kernels.
 
 Policy shapes outside the fused kernels' envelope (Default(hidden_size != 128), observation rows wider than 128 / 160 floats, more
-than 15 logits, LSTMWrapper sizes other than (128, 128), LSTMWrapper over the NatureCNN) adopt a general.GeneralParams buffer and
+than 15 logits, LSTMWrapper sizes other than (128, 128), LSTMWrapper over the NatureCNN, the NatureCNN with 16 .. 63 actions) adopt a
+general.GeneralParams buffer and
 run rollout and update through general.Engine."""
 import ctypes as C
 
@@ -42,8 +43,9 @@ def needs_general(policy_module, recurrent):
 def _needs_general(policy_module, recurrent):
     from .models import HIDDEN, decoder_heads, find_lstm, find_mlp
     lstm = find_lstm(policy_module)
-    if find_cnn(policy_module) is not None:
-        return lstm is not None
+    cnn = find_cnn(policy_module)
+    if cnn is not None:       # the conv engine's 16-lane head kernels take 15 actions; wider sets sample in the row kernels of the GEMM path
+        return lstm is not None or int(cnn.actor.weight.shape[0]) > 15
     mlp = find_mlp(policy_module)
     H, D = mlp.encoder.weight.shape
     nvec = decoder_heads(mlp)
@@ -112,8 +114,11 @@ class Policy(torch.nn.Module):
 
     def adopt(self, obs_stride, device):
         """Move the parameters into one flat device buffer (idempotent for the same stride/device)."""
-        if find_cnn(self.policy) is not None:       # models.Convolutional: its own parameter layout and engine (cnn.py)
-            if self._flat is None or self._flat.flat.device != torch.device(device):
+        if find_cnn(self.policy) is not None and not needs_general(self.policy, False):
+            # models.Convolutional: its own parameter layout and engine (cnn.py)
+            recorded = find_cnn(self.policy).__dict__.get('_pfa_obs_shape')      # (a trainer may have recorded the env's frame shape since)
+            if (self._flat is None or self._flat.flat.device != torch.device(device)
+                    or (recorded is not None and self._flat.geometry.obs_shape != recorded)):
                 from . import cnn
                 self._flat = ConvParams(self.policy, device)
                 self.cnn_engine = cnn.Engine(self._flat, chunk=256)       # grows on demand (Engine._alloc)
@@ -227,7 +232,7 @@ def _forward_tile(self, x2, rows, D, noise):
 
 
 def _forward_cnn(self, x2, rows, noise):
-    """policy(frames) for models.Convolutional: uint8 (rows, framestack*84*84) -> (actions, logprob, entropy, value)."""
+    """policy(frames) for models.Convolutional: uint8 (rows, frame bytes in the env's order) -> (actions, logprob, entropy, value)."""
     cp = self.adopt(0, x2.device)
     if x2.shape[1] != cp.obs_dim:
         raise ValueError(f'expected frames of {cp.obs_dim} bytes, got rows of {x2.shape[1]}')

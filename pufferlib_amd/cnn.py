@@ -1,14 +1,16 @@
 """NatureCNN policy engine (BASELINE configs[3]): pufferlib.models.Convolutional (models.py:113-157) behind
-frameworks.cleanrl.Policy, every product on the fp32-MFMA implicit-GEMM kernels of csrc/igemm.hip.
+frameworks.cleanrl.Policy, every product on the fp32-MFMA implicit-GEMM kernels of csrc/igemm.hip.  Any uint8 frame geometry of
+conv_geometry.ConvGeometry: channel-first frames with aligned rows (Atari) read through the word loader (mode 2), every other one —
+channel-last, downsampled, odd widths — through the strided loader (mode 4); hidden width any multiple of 16.
 
   Layer.forward / backward_dx / backward_dw      one conv or linear layer = one kernel launch each
-  Engine.forward(frames)                         the rollout / training forward of a batch of uint8 frames -> hidden [n][512]
+  Engine.forward(frames)                         the rollout / training forward of a batch of uint8 frames -> hidden [n][hidden width]
   Engine.policy_step(frames, ...)                policy(obs) in rollout mode: + heads + sample_logits (csrc/cnn_heads.hip)
   Engine.update(mb, ...)                         forward + PPO loss + backward of one minibatch (in chunks of `chunk` rows) ->
                                                  flat gradient in named_parameters() order + the 16-float loss tail
 
 Activations are NHWC f32 (conv outputs [n*OH*OW][OC]); the Linear behind nn.Flatten sees NHWC rows, its weight columns are
-re-ordered when packed.  Algorithmic work per frame: forward 2 (256*32*400 + 512*64*81 + 576*64*49 + 3136*512 +
+re-ordered when packed.  Algorithmic work per frame at the Atari shape: forward 2 (256*32*400 + 512*64*81 + 576*64*49 + 3136*512 +
 512*(A+1)) = 18.7 MFLOP, forward + backward ~ 3x that minus conv1's dX."""
 import ctypes as C
 
@@ -17,19 +19,25 @@ import torch
 from . import _lib
 
 F32 = torch.float32
-MODE_DENSE, MODE_IM2COL_F32, MODE_IM2COL_U8, MODE_COL2IM = 0, 1, 2, 3
+MODE_DENSE, MODE_IM2COL_F32, MODE_IM2COL_U8, MODE_COL2IM, MODE_IM2COL_U8S = 0, 1, 2, 3, 4
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_MASK = 0, 1, 2, 3
 
 
-def _operand(mode, tensor, lda=0, geom=(0,) * 9):
-    return _lib.IgemmOperand(mode, 0, tensor.data_ptr(), lda, *geom)
+def _operand(mode, tensor, lda=0, geom=(0,) * 9, strides=(0,) * 4):
+    """strides (mode 4 only): (sc, sy, sx, frame_bytes) — byte strides of channel / row / column of a frame, bytes per frame."""
+    return _lib.IgemmOperand(mode, 0, tensor.data_ptr(), lda, *geom, *strides)
 
 
 class ConvLayer:
-    """Conv2d(IC, OC, K, stride S), valid padding, + ReLU.  Input NHWC f32 [n][IH][IW][IC], or uint8 NCHW frames (first layer)."""
+    """Conv2d(IC, OC, K, stride S), valid padding, + ReLU.  Input NHWC f32 [n][IH][IW][IC], or uint8 frames (first layer): NCHW with
+    aligned rows, or — `strides` = (sc, sy, sx, frame_bytes) — any channel order / pixel stride through the strided loader."""
 
-    def __init__(self, weight, bias, ih, iw, stride, u8_input, device):
+    def __init__(self, weight, bias, ih, iw, stride, u8_input, device, strides=None):
         oc, ic, kh, kw = weight.shape
+        self.strides = tuple(strides) if strides else (0,) * 4
+        self.in_mode = (MODE_IM2COL_U8S if strides else MODE_IM2COL_U8) if u8_input else MODE_IM2COL_F32
+        self.pack_order = (2 if strides else 1) if u8_input else 0           # pfa_cnn_pack_conv u8_order
+        self.dw_perm = (5 if strides else 3) if u8_input else 2              # pfa_igemm_weights perm
         self.w, self.b = weight, bias
         self.IC, self.IH, self.IW, self.OC, self.KH, self.KW, self.S = ic, ih, iw, oc, kh, kw, stride
         self.OH, self.OW = (ih - kh) // stride + 1, (iw - kw) // stride + 1
@@ -45,7 +53,7 @@ class ConvLayer:
 
     def pack(self):
         L = _lib.lib()
-        _lib.check(L.pfa_cnn_pack_conv(_lib.ptr(self.w), C.byref(_operand(0, self.w, 0, self.geom)), 1 if self.u8 else 0, _lib.ptr(self.w_fwd),
+        _lib.check(L.pfa_cnn_pack_conv(_lib.ptr(self.w), C.byref(_operand(0, self.w, 0, self.geom)), self.pack_order, _lib.ptr(self.w_fwd),
                                        _lib.ptr(self.w_dx), _lib.stream_handle()), 'pack_conv')
 
     def out_rows(self, n):
@@ -53,7 +61,7 @@ class ConvLayer:
 
     def forward(self, x, n, out):
         """out [n*OH*OW][OC] = relu(conv(x) + bias)."""
-        a = _operand(MODE_IM2COL_U8 if self.u8 else MODE_IM2COL_F32, x, 0, self.geom)
+        a = _operand(self.in_mode, x, 0, self.geom, self.strides)
         _lib.check(_lib.lib().pfa_igemm_rows(C.byref(a), self.out_rows(n), self.K, _lib.ptr(self.w_fwd), self.K, self.OC, _lib.ptr(out), self.OC,
                                              EPI_BIAS_RELU, _lib.ptr(self.b), None, 0, _lib.stream_handle()), 'conv_forward')
 
@@ -65,9 +73,9 @@ class ConvLayer:
 
     def backward_dw(self, x, n, dout, gw, gb, accumulate, ws):
         """gw (torch layout [OC][IC][KH][KW]) (+)= dout^T im2col(x); gb (+)= column sums of dout."""
-        a = _operand(MODE_IM2COL_U8 if self.u8 else MODE_IM2COL_F32, x, 0, self.geom)
+        a = _operand(self.in_mode, x, 0, self.geom, self.strides)
         _lib.check(_lib.lib().pfa_igemm_weights(C.byref(a), self.out_rows(n), self.K, _lib.ptr(dout), self.OC, self.OC, _lib.ptr(gw),
-                                                3 if self.u8 else 2, 1 if accumulate else 0, _lib.ptr(gb), _lib.ptr(ws), _lib.stream_handle()), 'conv_dw')
+                                                self.dw_perm, 1 if accumulate else 0, _lib.ptr(gb), _lib.ptr(ws), _lib.stream_handle()), 'conv_dw')
 
     def dw_workspace(self, n):
         return _lib.lib().pfa_igemm_weights_workspace_bytes(self.out_rows(n), self.K, self.OC)
@@ -113,7 +121,9 @@ class LinearLayer:
 
 class Engine:
     """Forward / update of the NatureCNN policy over a ConvParams buffer.  `chunk` = frames per kernel batch (bounds the
-    activation memory: ~170 KB per frame with the gradients)."""
+    activation memory: ~170 KB per frame with the gradients at the Atari shape); clamped to what the geometry allows under
+    32-bit element offsets (5325 frames of 280 x 480 x 3 bytes) and a quarter of the device memory for the activations
+    (ConvGeometry.chunk_for)."""
 
     def __init__(self, cp, experience=None, chunk=8192):
         self.cp, self.dev = cp, cp.flat.device
@@ -123,26 +133,38 @@ class Engine:
         self.norm_partials = torch.zeros(1024, dtype=torch.float64, device=self.dev)
         v = cp.views
         dev = self.dev
-        self.conv1 = ConvLayer(v['network.0.weight'], v['network.0.bias'], 84, 84, 4, True, dev)
-        self.conv2 = ConvLayer(v['network.2.weight'], v['network.2.bias'], 20, 20, 2, False, dev)
-        self.conv3 = ConvLayer(v['network.4.weight'], v['network.4.bias'], 9, 9, 1, False, dev)
-        self.fc = LinearLayer(v['network.7.weight'], v['network.7.bias'], True, (64, 7, 7), dev)
+        geo = getattr(cp, 'geometry', None)
+        if geo is None:                     # a parameter buffer that names no geometry: the Atari one
+            from .conv_geometry import ConvGeometry, default_obs_shape
+            geo = ConvGeometry(default_obs_shape(cp.framestack))
+        self.geometry = geo
+        (_, h1, w1, _, h2, w2, _, _, _), (_, _, _, _, h3, w3, _, _, _) = geo.layers[0], geo.layers[1]
+        strides = None if geo.aligned_chw else (geo.sc, geo.sy, geo.sx, geo.frame_bytes)
+        self.conv1 = ConvLayer(v['network.0.weight'], v['network.0.bias'], h1, w1, 4, True, dev, strides)
+        self.conv2 = ConvLayer(v['network.2.weight'], v['network.2.bias'], h2, w2, 2, False, dev)
+        self.conv3 = ConvLayer(v['network.4.weight'], v['network.4.bias'], h3, w3, 1, False, dev)
+        self.fc = LinearLayer(v['network.7.weight'], v['network.7.bias'], True, geo.out_shape, dev)
         self.layers = [self.conv1, self.conv2, self.conv3, self.fc]
-        self.frame_bytes = cp.framestack * 84 * 84
+        self.frame_bytes = geo.frame_bytes
+        self.hidden = self.fc.N
+        # frames per kernel batch: what 32-bit element offsets allow, and activations (with their gradients) within a quarter of the device
+        total = torch.cuda.get_device_properties(dev).total_memory if dev.type == 'cuda' else None
+        self.max_chunk = geo.chunk_for(total // 4 if total else None)
         self.chunk = 0
         self.packed_version = -1
         self.version = 0          # bumped by whoever changes the weights (optimizer step, checkpoint load)
         self._alloc(chunk)
 
     def _alloc(self, chunk):
+        chunk = min(int(chunk), self.max_chunk)
         if chunk <= self.chunk:
             return
-        dev, n = self.dev, chunk
+        dev, n, H = self.dev, chunk, self.hidden
         self.chunk = n
-        self.a1 = torch.empty(n * 400, 32, device=dev)
-        self.a2 = torch.empty(n * 81, 64, device=dev)
-        self.a3 = torch.empty(n * 49, 64, device=dev)
-        self.h = torch.empty(n, 512, device=dev)
+        self.a1 = torch.empty(self.conv1.out_rows(n), 32, device=dev)
+        self.a2 = torch.empty(self.conv2.out_rows(n), 64, device=dev)
+        self.a3 = torch.empty(self.conv3.out_rows(n), 64, device=dev)
+        self.h = torch.empty(n, H, device=dev)
         self.d1 = torch.empty_like(self.a1)
         self.d2 = torch.empty_like(self.a2)
         self.d3 = torch.empty_like(self.a3)
@@ -151,10 +173,10 @@ class Engine:
         self.frames = torch.empty(n, self.frame_bytes, dtype=torch.uint8, device=dev)
         L = _lib.lib()
         ws = max([self.conv1.dw_workspace(n), self.conv2.dw_workspace(n), self.conv3.dw_workspace(n), self.fc.dw_workspace(n),
-                  L.pfa_igemm_weights_workspace_bytes(n, 512, 16)])
+                  L.pfa_igemm_weights_workspace_bytes(n, H, 16)])
         self.ws = torch.empty(ws, dtype=torch.uint8, device=dev)
         self.ws_loss = torch.empty(L.pfa_cnn_heads_loss_workspace_bytes(), dtype=torch.uint8, device=dev)
-        self.g16 = torch.empty(16, 512, device=dev)
+        self.g16 = torch.empty(16, H, device=dev)
         self.gb16 = torch.empty(16, device=dev)
 
     def pack(self):
@@ -165,7 +187,7 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------------------------ forward
     def forward(self, frames, n):
-        """frames uint8 [n][F*84*84] (NCHW per frame) -> self.h[:n] (hidden, post-ReLU); keeps a1/a2/a3 for a backward."""
+        """frames uint8 [n][frame_bytes] (the env's own byte order) -> self.h[:n] (hidden, post-ReLU); keeps a1/a2/a3 for a backward."""
         assert n <= self.chunk
         self.pack()
         self.conv1.forward(frames, n, self.a1)
@@ -182,15 +204,15 @@ class Engine:
             m = min(self.chunk, n - lo)
             h = self.forward(frames[lo:lo + m], m)
             nz = None if noise is None else noise[lo:lo + m]
-            _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(h), m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']),
-                                              _lib.ptr(v['value_fn.bias']), self.cp.num_actions, _lib.ptr(nz), C.byref(key), row_offset + lo,
-                                              _lib.ptr(actions[lo:lo + m]), _lib.ptr(logprob[lo:lo + m]),
-                                              None if entropy is None else _lib.ptr(entropy[lo:lo + m]), _lib.ptr(value[lo:lo + m]),
-                                              _lib.stream_handle()), 'cnn_heads_sample')
+            _lib.check(L.pfa_cnn_heads_sample_w(_lib.ptr(h), self.hidden, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']),
+                                                _lib.ptr(v['value_fn.bias']), self.cp.num_actions, _lib.ptr(nz), C.byref(key), row_offset + lo,
+                                                _lib.ptr(actions[lo:lo + m]), _lib.ptr(logprob[lo:lo + m]),
+                                                None if entropy is None else _lib.ptr(entropy[lo:lo + m]), _lib.ptr(value[lo:lo + m]),
+                                                _lib.stream_handle()), 'cnn_heads_sample')
 
     # ------------------------------------------------------------------------------------------------------------- update
     def backward(self, frames, m, dh_pre, gv, acc):
-        """Back-propagate d loss / d (pre-ReLU hidden) [m][512] through Linear(3136,512) and the three conv layers of the chunk
+        """Back-propagate d loss / d (pre-ReLU hidden) [m][hidden] through Linear(flat_size, hidden) and the three conv layers of the chunk
         whose forward just ran (activations a1/a2/a3 live); weight / bias gradients into the views `gv` (accumulate = acc)."""
         self.fc.backward_dw(self.a3, m, dh_pre, gv['network.7.weight'], gv['network.7.bias'], acc, self.ws)
         self.fc.backward_dx(dh_pre, m, self.a3, self.d3)            # d3 masked by relu'(a3)
@@ -233,13 +255,13 @@ class Engine:
             acc = ci > 0
             _lib.check(L.pfa_cnn_gather_frames(_lib.ptr(obs_u8), self.frame_bytes, B, mb, C.byref(hp), q0, m, _lib.ptr(self.frames), stream), 'gather')
             h = self.forward(self.frames, m)
-            _lib.check(L.pfa_cnn_heads_loss(_lib.ptr(h), C.byref(exp_c), B, mb, q0, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']),
+            _lib.check(L.pfa_cnn_heads_loss_w(_lib.ptr(h), self.hidden, C.byref(exp_c), B, mb, q0, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']),
                                             _lib.ptr(v['value_fn.weight']), _lib.ptr(v['value_fn.bias']), cp.num_actions, C.byref(hp),
                                             _lib.ptr(adv_stats), global_mb_rows, _lib.ptr(self.dout), _lib.ptr(self.dh), _lib.ptr(tail),
                                             1 if acc else 0, _lib.ptr(self.ws_loss), stream), 'cnn_heads_loss')
-            # heads: dW = dout^T h ([16][512]: rows < A actor, row A value_fn), db = column sums of dout
-            a = _operand(MODE_DENSE, h, 512)
-            _lib.check(L.pfa_igemm_weights(C.byref(a), m, 512, _lib.ptr(self.dout), 16, 16, _lib.ptr(self.g16), 1, 1 if acc else 0,
+            # heads: dW = dout^T h ([16][hidden]: rows < A actor, row A value_fn), db = column sums of dout
+            a = _operand(MODE_DENSE, h, self.hidden)
+            _lib.check(L.pfa_igemm_weights(C.byref(a), m, self.hidden, _lib.ptr(self.dout), 16, 16, _lib.ptr(self.g16), 1, 1 if acc else 0,
                                            _lib.ptr(self.gb16), _lib.ptr(self.ws), stream), 'heads_dw')
             dh_pre = self.dh                       # already w.r.t. the pre-ReLU hidden (masked in the heads kernel)
             self.backward(self.frames, m, dh_pre, gv, acc)

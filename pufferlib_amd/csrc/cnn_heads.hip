@@ -1,13 +1,15 @@
-// cnn_heads.hip — the head side of the NatureCNN policy (pufferlib/models.py:152-157 decode_actions: actor Linear(512, A),
-// value_fn Linear(512, 1)) on the 512-wide hidden vector the conv stack + Linear(3136, 512) of csrc/igemm.hip produce:
+// cnn_heads.hip — the head side of the NatureCNN policy (pufferlib/models.py:152-157 decode_actions: actor Linear(H, A),
+// value_fn Linear(H, 1)) on the H-wide hidden vector the conv stack + Linear(flat_size, H) of csrc/igemm.hip produce (H = 512 or 128):
 //   cnn_heads_sample   rollout: logits, value, sample_logits (cleanrl.py:25-47) -> action, log-prob, entropy, value
 //   cnn_heads_loss     training: the same heads, the PPO loss of clean_pufferl.py:202-238, d loss / d (head outputs) [rows][16],
-//                      d loss / d (pre-ReLU hidden) [rows][512], the six loss sums (f64, (hi, lo) float pairs)
+//                      d loss / d (pre-ReLU hidden) [rows][H], the six loss sums (f64, (hi, lo) float pairs)
 //   cnn_gather_frames  the uint8 frames of a chunk of minibatch rows, copied next to each other (rows of a minibatch are
 //                      bptt_horizon-long segments of the env-major experience, clean_pufferl.py:455-457)
 // 16 lanes per row (lane lo = head output lo), the row's hidden vector in LDS, head weights in LDS (padded rows: conflict-free),
 // the 16-lane log-softmax / arg-max pieces shared with the MLP and LSTM policies (sampler.hpp), so all three sample and score
-// with identical arithmetic.  VALU work: 2 x 512 x (A + 1) flop per row against ~56 MFLOP in the conv stack.
+// with identical arithmetic.  The hidden width is a template argument (512: the Atari binding, 128: crafter / dm_lab / butterfly) or, for
+// any other multiple of 16 up to 1024, a run-time argument of the same code (pfa_cnn_heads_sample_w / _loss_w; the LDS carve follows
+// the width).  More than 15 actions: the row kernels of csrc/general.hip on head outputs computed by pfa_igemm_rows.  VALU work: 2 x H x (A + 1) flop per row against ~56 MFLOP in the conv stack.
 #include "common.hpp"
 #include "lane_ops.hpp"
 #include "mlp_tile.hpp"
@@ -16,46 +18,54 @@
 
 namespace pfa {
 
-constexpr int kCnnH = 512;
+constexpr int kCnnH = 512;        // the Atari width: pfa_cnn_heads_sample / _loss; the _w entry points carry the width
+constexpr int kCnnMaxH = 1024;    // LDS: 16 head rows of H + 1 floats and 16 hidden rows of H floats (129 KB at 1024, of 160 KB)
 
-struct CnnHeads {   // actor.weight [A][512], actor.bias [A], value_fn.weight [1][512], value_fn.bias [1] (torch layout)
+struct CnnHeads {   // actor.weight [A][H], actor.bias [A], value_fn.weight [1][H], value_fn.bias [1] (torch layout), H = the hidden width
     const float *w2, *b2, *wv, *bv;
     int a;
 };
 
-__device__ __forceinline__ void cnn_stage_heads(const CnnHeads &hd, float *w2v /* [16][513] */, float *b2v) {
-    for (int i = threadIdx.x; i < kOut * kCnnH; i += blockDim.x) {
-        const int o = i / kCnnH, u = i - o * kCnnH;
-        w2v[o * (kCnnH + 1) + u] = o < hd.a ? hd.w2[o * kCnnH + u] : (o == hd.a ? hd.wv[u] : 0.0f);
+// HT: the hidden width as a template argument (512, 128), or 0 = the run-time width `hrt` (any multiple of 16)
+template <int HT>
+__device__ __forceinline__ void cnn_stage_heads(const CnnHeads &hd, float *w2v /* [16][H + 1] */, float *b2v, int hrt) {
+    const int H = HT ? HT : hrt;
+    for (int i = threadIdx.x; i < kOut * H; i += blockDim.x) {
+        const int o = i / H, u = i - o * H;
+        w2v[o * (H + 1) + u] = o < hd.a ? hd.w2[o * H + u] : (o == hd.a ? hd.wv[u] : 0.0f);
     }
     for (int i = threadIdx.x; i < kOut; i += blockDim.x) b2v[i] = i < hd.a ? hd.b2[i] : (i == hd.a ? hd.bv[0] : 0.0f);
 }
-__device__ __forceinline__ float cnn_head_dot(const float *hrow, const float *w2v, const float *b2v, int lo) {
+template <int HT>
+__device__ __forceinline__ float cnn_head_dot(const float *hrow, const float *w2v, const float *b2v, int lo, int hrt) {
+    const int H = HT ? HT : hrt;
     float acc = b2v[lo];
-    const float *w = w2v + lo * (kCnnH + 1);
+    const float *w = w2v + lo * (H + 1);
 #pragma unroll 8
-    for (int u = 0; u < kCnnH; ++u) acc = fmaf(hrow[u], w[u], acc);   // k-ordered fma chain, like nn.Linear's fp32 dot
+    for (int u = 0; u < H; ++u) acc = fmaf(hrow[u], w[u], acc);   // k-ordered fma chain, like nn.Linear's fp32 dot
     return acc;
 }
 
-__global__ void __launch_bounds__(256) cnn_heads_sample_kernel(const float *h, long long rows, CnnHeads hd, const float *noise, uint64_t seed,
+template <int HT>
+__global__ void __launch_bounds__(256) cnn_heads_sample_kernel(const float *h, int hrt, long long rows, CnnHeads hd, const float *noise, uint64_t seed,
                                                               uint64_t step, long long row_offset, long long *actions, float *logprob,
                                                               float *entropy, float *value) {
     extern __shared__ float lds[];
-    float *w2v = lds, *b2v = w2v + kOut * (kCnnH + 1), *hs = b2v + kOut;   // hs [16][512]
-    cnn_stage_heads(hd, w2v, b2v);
+    const int H = HT ? HT : hrt;
+    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;   // hs [16][H]
+    cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
     const long long tiles = (rows + 15) / 16;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         __syncthreads();
-        for (int i = threadIdx.x; i < 16 * kCnnH; i += 256) {
-            const long long r = tile * 16 + i / kCnnH;
-            hs[i] = r < rows ? h[r * kCnnH + i % kCnnH] : 0.0f;
+        for (int i = threadIdx.x; i < 16 * H; i += 256) {
+            const long long r = tile * 16 + i / H;
+            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
         }
         __syncthreads();
         const long long row = tile * 16 + le;
         const bool ok = row < rows;
-        const float mine = cnn_head_dot(hs + le * kCnnH, w2v, b2v, lo);
+        const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
         const float q = ok ? noise_lane(noise ? noise + row * a : nullptr, seed, step, (uint64_t)(row_offset + row), lo, a) : 1.0f;
         const LaneSample sm = sample_row16(mine, lo, a, q);
         if (ok && lo == 0) {
@@ -68,14 +78,16 @@ __global__ void __launch_bounds__(256) cnn_heads_sample_kernel(const float *h, l
 }
 
 // rows = a chunk [q0, q0 + rows) of minibatch `map.mb`; ex.* are read at map.flat(q0 + row).
-__global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, long long rows, RowMap map, long long q0, pfa_experience ex, CnnHeads hd,
+template <int HT>
+__global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, int hrt, long long rows, RowMap map, long long q0, pfa_experience ex, CnnHeads hd,
                                                             pfa_ppo_hparams hp, const double *adv_stats, double global_rows,
-                                                            float *dout /* [rows][16] */, float *dh /* [rows][512] */,
+                                                            float *dout /* [rows][16] */, float *dh /* [rows][H] */,
                                                             double *stats_partial /* [gridDim.x][8] */) {
     extern __shared__ float lds[];
-    float *w2v = lds, *b2v = w2v + kOut * (kCnnH + 1), *hs = b2v + kOut;
+    const int H = HT ? HT : hrt;
+    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;
     __shared__ double st[16][8];
-    cnn_stage_heads(hd, w2v, b2v);
+    cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
     float adv_mean = 0.0f, adv_den = 1.0f;
     if (hp.norm_adv) {
@@ -91,9 +103,9 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, lon
     const long long tiles = (rows + 15) / 16;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         __syncthreads();
-        for (int i = threadIdx.x; i < 16 * kCnnH; i += 256) {
-            const long long r = tile * 16 + i / kCnnH;
-            hs[i] = r < rows ? h[r * kCnnH + i % kCnnH] : 0.0f;
+        for (int i = threadIdx.x; i < 16 * H; i += 256) {
+            const long long r = tile * 16 + i / H;
+            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
         }
         __syncthreads();
         const long long row = tile * 16 + le;
@@ -102,7 +114,7 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, lon
         const float w = ok ? 1.0f : 0.0f;
         const int action = ex.actions[fr];
         const float old_logprob = ex.logprobs[fr], old_value = ex.values[fr], adv_raw = ex.advantages[fr], ret = ex.returns[fr];
-        const float mine = cnn_head_dot(hs + le * kCnnH, w2v, b2v, lo);
+        const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
         const bool is_logit = lo < a;
         const float mx = row16_max(is_logit ? mine : -INFINITY);
         const float ev = is_logit ? expf(mine - mx) : 0.0f;
@@ -146,17 +158,37 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, lon
         else if (lo == a) d = dv;
         if (ok) dout[row * kOut + lo] = d;
         // d loss / d h[u] = sum_o d_o W2v[o][u]; lane lo owns u = lo, lo + 16, ...
-        float dhv[kCnnH / 16];
+        // (the hidden vector is relu(Linear(...)): hand back d loss / d (pre-activation), i.e. masked by relu')
+        if (HT) {
+            float dhv[(HT ? HT : 16) / 16];
 #pragma unroll
-        for (int j = 0; j < kCnnH / 16; ++j) dhv[j] = 0.0f;
-        for (int o = 0; o <= a; ++o) {
-            const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
+            for (int j = 0; j < HT / 16; ++j) dhv[j] = 0.0f;
+            for (int o = 0; o <= a; ++o) {
+                const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
 #pragma unroll
-            for (int j = 0; j < kCnnH / 16; ++j) dhv[j] = fmaf(d_o, w2v[o * (kCnnH + 1) + lo + 16 * j], dhv[j]);
-        }
-        if (ok) {   // the hidden vector is relu(Linear(...)): hand back d loss / d (pre-activation), i.e. masked by relu'
+                for (int j = 0; j < HT / 16; ++j) dhv[j] = fmaf(d_o, w2v[o * (HT + 1) + lo + 16 * j], dhv[j]);
+            }
+            if (ok) {
 #pragma unroll
-            for (int j = 0; j < kCnnH / 16; ++j) dh[row * kCnnH + lo + 16 * j] = hs[le * kCnnH + lo + 16 * j] > 0.0f ? dhv[j] : 0.0f;
+                for (int j = 0; j < HT / 16; ++j) dh[row * HT + lo + 16 * j] = hs[le * HT + lo + 16 * j] > 0.0f ? dhv[j] : 0.0f;
+            }
+        } else {   // any width: the same fma chains over o, eight columns of the lane at a time
+            for (int j0 = 0; j0 < H / 16; j0 += 8) {
+                float dhv[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dhv[j] = 0.0f;
+                for (int o = 0; o <= a; ++o) {
+                    const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (j0 + j < H / 16) dhv[j] = fmaf(d_o, w2v[o * (H + 1) + lo + 16 * (j0 + j)], dhv[j]);
+                }
+                if (ok) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (j0 + j < H / 16) dh[row * H + lo + 16 * (j0 + j)] = hs[le * H + lo + 16 * (j0 + j)] > 0.0f ? dhv[j] : 0.0f;
+                }
+            }
         }
         if (lo == 0) {
             acc[0] += (double)(fmaxf(pg1, pg2) * w);
@@ -205,62 +237,102 @@ __global__ void __launch_bounds__(256) cnn_gather_frames_kernel(const uint8_t *f
     }
 }
 
-static size_t cnn_heads_lds() { return (size_t)(kOut * (kCnnH + 1) + kOut + 16 * kCnnH) * sizeof(float); }
+static size_t cnn_heads_lds(int H) { return (size_t)(kOut * (H + 1) + kOut + 16 * H) * sizeof(float); }
+
+template <int HT>
+static int cnn_launch_sample(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const CnnHeads &hd, const float *noise,
+                             const pfa_noise_key *key, long long row_offset, long long *actions, float *logprob, float *entropy, float *value) {
+    static int lds_set = 0;   // the opt-in LDS size of this instantiation (grows with the run-time width)
+    const int lds = (int)cnn_heads_lds(H);
+    if (lds > lds_set) {
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_sample_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        lds_set = lds;
+    }
+    hipLaunchKernelGGL(cnn_heads_sample_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, hd, noise, key ? key->seed : 0,
+                       key ? key->step : 0, row_offset, actions, logprob, entropy, value);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+template <int HT>
+static int cnn_launch_loss(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const RowMap &map, long long q0,
+                           const pfa_experience &ex, const CnnHeads &hd, const pfa_ppo_hparams &hp, const double *adv_stats, double global_rows,
+                           float *dout, float *dh, double *partial) {
+    static int lds_set = 0;
+    const int lds = (int)cnn_heads_lds(H);
+    if (lds > lds_set) {
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_loss_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        lds_set = lds;
+    }
+    hipLaunchKernelGGL(cnn_heads_loss_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, map, q0, ex, hd, hp, adv_stats, global_rows, dout,
+                       dh, partial);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
 
 }  // namespace pfa
 
 using namespace pfa;
 
-extern "C" int pfa_cnn_heads_sample(const float *h, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+extern "C" int pfa_cnn_heads_sample_w(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
                                     const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
                                     int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream) {
     PFA_REQUIRE(rows >= 0 && h && actor_w && actor_b && value_w && value_b && actions && logprob && value, "cnn.heads_sample: null buffer");
+    PFA_REQUIRE(hidden >= 16 && hidden % 16 == 0 && hidden <= kCnnMaxH, "cnn.heads_sample: hidden must be a multiple of 16 in 16..1024 (got %d)", hidden);
     PFA_REQUIRE(num_actions >= 1 && num_actions <= 15, "cnn.heads_sample: num_actions must be in 1..15");
     PFA_REQUIRE(noise || key, "cnn.heads_sample: need an explicit noise tensor or a Philox key");
     if (rows == 0) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cnn_heads_lds()));
-        attr_set = true;
-    }
     const long long tiles = (rows + 15) / 16;
     const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
     CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
     ScopedKernelTimer timer("cnn_heads_sample", (hipStream_t)stream);
-    hipLaunchKernelGGL(cnn_heads_sample_kernel, dim3(grid), dim3(256), cnn_heads_lds(), (hipStream_t)stream, h, (long long)rows, hd, noise,
-                       key ? key->seed : 0, key ? key->step : 0, (long long)row_offset, (long long *)actions, logprob, entropy, value);
-    PFA_LAUNCH_CHECK();
-    return 0;
+#define PFA_CNN_SAMPLE(HT) \
+    cnn_launch_sample<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, noise, key, (long long)row_offset, (long long *)actions, logprob, entropy, value)
+    if (hidden == 512) return PFA_CNN_SAMPLE(512);
+    if (hidden == 128) return PFA_CNN_SAMPLE(128);
+    return PFA_CNN_SAMPLE(0);
+#undef PFA_CNN_SAMPLE
+}
+
+extern "C" int pfa_cnn_heads_sample(const float *h, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+                                    const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
+                                    int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream) {
+    return pfa_cnn_heads_sample_w(h, kCnnH, rows, actor_w, actor_b, value_w, value_b, num_actions, noise, key, row_offset, actions, logprob, entropy,
+                                  value, stream);
 }
 
 extern "C" size_t pfa_cnn_heads_loss_workspace_bytes(void) { return (size_t)1024 * 8 * sizeof(double); }
 
-extern "C" int pfa_cnn_heads_loss(const float *h, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
+extern "C" int pfa_cnn_heads_loss_w(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
                                   const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
                                   const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
                                   float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream) {
     PFA_REQUIRE(h && exp && hp && dout && dh && loss_pairs16 && workspace && actor_w && actor_b && value_w && value_b, "cnn.heads_loss: null buffer");
     PFA_REQUIRE(num_actions >= 1 && num_actions <= 15, "cnn.heads_loss: num_actions must be in 1..15");
+    PFA_REQUIRE(hidden >= 16 && hidden % 16 == 0 && hidden <= kCnnMaxH, "cnn.heads_loss: hidden must be a multiple of 16 in 16..1024 (got %d)", hidden);
     PFA_REQUIRE(hp->num_minibatches >= 1 && batch_rows % hp->num_minibatches == 0 && mb >= 0 && mb < hp->num_minibatches, "cnn.heads_loss: bad minibatch");
     const int64_t mbs = batch_rows / hp->num_minibatches;
     PFA_REQUIRE(q0 >= 0 && rows >= 1 && q0 + rows <= mbs, "cnn.heads_loss: chunk outside the minibatch");
     PFA_REQUIRE(!hp->norm_adv || adv_stats, "cnn.heads_loss: norm_adv needs adv_stats");
-    static bool attr_set = false;
-    if (!attr_set) {
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_loss_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cnn_heads_lds()));
-        attr_set = true;
-    }
     const long long tiles = (rows + 15) / 16;
     const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
     CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     ScopedKernelTimer timer("cnn_heads_loss", (hipStream_t)stream);
-    hipLaunchKernelGGL(cnn_heads_loss_kernel, dim3(grid), dim3(256), cnn_heads_lds(), (hipStream_t)stream, h, (long long)rows, map, (long long)q0, *exp,
-                       hd, *hp, adv_stats, (double)global_mb_rows, dout, dh, (double *)workspace);
-    PFA_LAUNCH_CHECK();
+#define PFA_CNN_LOSS(HT) \
+    cnn_launch_loss<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, map, (long long)q0, *exp, hd, *hp, adv_stats, (double)global_mb_rows, dout, dh, (double *)workspace)
+    if (int rc = hidden == 512 ? PFA_CNN_LOSS(512) : hidden == 128 ? PFA_CNN_LOSS(128) : PFA_CNN_LOSS(0)) return rc;
+#undef PFA_CNN_LOSS
     hipLaunchKernelGGL(cnn_stats_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, (int)grid, loss_pairs16, (int)accumulate);
     PFA_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pfa_cnn_heads_loss(const float *h, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
+                                  const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
+                                  const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
+                                  float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream) {
+    return pfa_cnn_heads_loss_w(h, kCnnH, exp, batch_rows, mb, q0, rows, actor_w, actor_b, value_w, value_b, num_actions, hp, adv_stats,
+                                global_mb_rows, dout, dh, loss_pairs16, accumulate, workspace, stream);
 }
 
 extern "C" int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t batch_rows, int32_t mb, const pfa_ppo_hparams *hp,

@@ -13,7 +13,11 @@
 // patch elements) as floats 0..255 — the `/ 255.0` is folded into its packed weights (forward) and into the reduction of its
 // weight gradient, one VALU conversion per element instead of four.  dX of a stride-S layer runs as S*S phases (input pixels with equal
 // (y mod S, x mod S) share the (KH/S)(KW/S) kernel taps that reach them), so no multiply is spent on the structural zeros of a
-// transposed strided convolution.
+// transposed strided convolution; IH, IW need not be multiples of S (ragged phases of ceil(IH/S) x ceil(IW/S) pixel slots, the ones
+// past the edge dropped by the epilogue), and input pixels no window covers receive exactly 0.
+// Frames in any other layout — channel-last (H, W, C), a `[::d, ::d]` pixel stride, rows that are not multiples of four bytes — go through
+// the strided uint8 mode (kAIm2colU8S): byte (ic, y, x) of a frame at ic*sc + y*sy + x*sx, patch order (ky, kx, ic), so that C = 4
+// channel-last is one aligned word per pixel; C = 1 / 3 load bytes at four incrementally kept offsets.  Same `/ 255` folding.
 //
 // Address arithmetic is the cost that competes with the MFMAs (VALU and MFMA issue from the same SIMD port and do not overlap),
 // so it is incremental: a thread keeps the (tap, channel) decomposition of its fixed k-quad (rows form) or its fixed row pair's
@@ -38,7 +42,7 @@ constexpr int kIgThreads = 256;
 constexpr int kIgBK = 16;
 constexpr int kIgLS = kIgBK + 4;   // LDS row stride (floats) of a [row][16 k] slab
 
-enum IgAMode : int { kADense = 0, kAIm2colF32 = 1, kAIm2colU8 = 2, kACol2im = 3 };
+enum IgAMode : int { kADense = 0, kAIm2colF32 = 1, kAIm2colU8 = 2, kACol2im = 3, kAIm2colU8S = 4 };
 enum IgEpilogue : int { kEpiNone = 0, kEpiBias = 1, kEpiBiasRelu = 2, kEpiMask = 3 };
 
 // One conv layer (valid padding): input [N][IH][IW][IC] (NHWC f32) or uint8 [N][IC][IH][IW]; output [N][OH][OW][OC] NHWC.
@@ -51,15 +55,42 @@ struct IgA {
     const void *ptr;   // dense: float [M][lda]; im2col f32: NHWC input; im2col u8: NCHW frames; col2im: dOut NHWC [N][OH][OW][OC]
     int lda;
     IgGeom g;
-    int JH, JW, HP, WP;   // col2im: taps per phase (KH/S, KW/S) and pixels per phase and frame (IH/S, IW/S)
+    int JH, JW, HP, WP;   // col2im: taps per phase (KH/S, KW/S) and pixel slots per phase and frame (ceil(IH/S), ceil(IW/S))
+    // strided u8 (kAIm2colU8S): byte (ic, y, x) of frame n sits at n*fb + ic*sc + y*sy + x*sx (channel order and the `[::d, ::d]` of
+    // models.py:148 are strides, not copies); word != 0: IC == 4 channel-last, every pixel one aligned 32-bit word; a slab of 16 patch
+    // elements is adv_pix whole pixels + adv_ch channels
+    int sc, sy, sx, fb, word, adv_pix, adv_ch;
 };
 
 // -------------------------------------------------------------------------------------------------- the k part of an address
 // Where patch elements k .. k+3 sit relative to a row's base element, kept incrementally (k advances by one slab at a time).
 struct IgK {
     int off;          // element offset to add to the row base
-    int p, q, ch;     // running decomposition: im2col f32 (ky, kx, ic) / u8 (ic, ky, kx) / col2im (jy, jx, oc)
+    int p, q, ch;     // running decomposition: im2col f32 (ky, kx, ic) / u8 (ic, ky, kx) / col2im (jy, jx, oc) / strided u8 (ky, kx, ic)
+    int o1, o2, o3;   // strided u8, byte path: the offsets of elements k+1 .. k+3 (they may sit in the next pixel or patch row)
 };
+
+// strided u8: byte offsets of patch elements k .. k+3 from (p, q, ch) = (ky, kx, ic) of element k; adds and compares only
+__device__ __forceinline__ void ig_k_u8s_offsets(const IgA &a, IgK &s) {
+    s.off = s.p * a.sy + s.q * a.sx + s.ch * a.sc;
+    if (a.word) return;
+    int o = s.off, q = s.q, ch = s.ch;
+    auto step = [&]() {
+        o += a.sc;
+        if (++ch == a.g.IC) {
+            ch = 0;
+            o += a.sx - a.g.IC * a.sc;
+            if (++q == a.g.KW) {
+                q = 0;
+                o += a.sy - a.g.KW * a.sx;
+            }
+        }
+        return o;
+    };
+    s.o1 = step();
+    s.o2 = step();
+    s.o3 = step();
+}
 
 template <int MODE>
 __device__ __forceinline__ IgK ig_k_init(const IgA &a, int k) {
@@ -79,6 +110,12 @@ __device__ __forceinline__ IgK ig_k_init(const IgA &a, int k) {
         s.q = t % a.g.KH;
         s.p = t / a.g.KH;
         s.off = (s.p * a.g.IH + s.q) * a.g.IW + s.ch;
+    } else if (MODE == kAIm2colU8S) {   // k = (ky*KW + kx)*IC + ic
+        const int pix = k / a.g.IC;
+        s.ch = k - pix * a.g.IC;
+        s.p = pix / a.g.KW;
+        s.q = pix - s.p * a.g.KW;
+        ig_k_u8s_offsets(a, s);
     } else {                              // k = (jy*JW + jx)*OC + oc; the row base is dOut pixel (yy, xx): tap (jy, jx) reads (yy-jy, xx-jx)
         const int pix = k / a.g.OC;
         s.ch = k - pix * a.g.OC;
@@ -113,6 +150,18 @@ __device__ __forceinline__ void ig_k_advance(const IgA &a, IgK &s) {   // k += 1
             }
         }
         s.off = (s.p * a.g.IH + s.q) * a.g.IW + s.ch;
+    } else if (MODE == kAIm2colU8S) {
+        s.ch += a.adv_ch;
+        s.q += a.adv_pix;
+        if (s.ch >= a.g.IC) {
+            s.ch -= a.g.IC;
+            ++s.q;
+        }
+        while (s.q >= a.g.KW) {
+            s.q -= a.g.KW;
+            ++s.p;
+        }
+        ig_k_u8s_offsets(a, s);
     } else {
         s.ch += kIgBK;
         while (s.ch >= a.g.OC) {
@@ -144,6 +193,10 @@ __device__ __forceinline__ IgRow ig_row(const IgA &a, int m) {
         const int n = m / ohw, rem = m - n * ohw, oy = rem / a.g.OW, ox = rem - oy * a.g.OW;
         r.base = MODE == kAIm2colF32 ? ((n * a.g.IH + oy * a.g.S) * a.g.IW + ox * a.g.S) * a.g.IC
                                        : (n * a.g.IC * a.g.IH + oy * a.g.S) * a.g.IW + ox * a.g.S;
+    } else if (MODE == kAIm2colU8S) {
+        const int ohw = a.g.OH * a.g.OW;
+        const int n = m / ohw, rem = m - n * ohw, oy = rem / a.g.OW, ox = rem - oy * a.g.OW;
+        r.base = n * a.fb + oy * a.g.S * a.sy + ox * a.g.S * a.sx;
     } else {
         const int hw = a.HP * a.WP;
         const int n = m / hw, rem = m - n * hw, yy = rem / a.WP, xx = rem - yy * a.WP;
@@ -179,6 +232,14 @@ __device__ __forceinline__ float4 ig_load4(const IgA &a, const IgRow &r, const I
     if (MODE == kAIm2colU8) {   // four bytes = one aligned word, as floats 0..255; the `/ 255.0` of models.py:150 rides in the other operand
         const uint32_t w = *reinterpret_cast<const uint32_t *>((const uint8_t *)a.ptr + (r.base + k.off));   // (packed weights / dW scale)
         return make_float4((float)(w & 0xFFu), (float)((w >> 8) & 0xFFu), (float)((w >> 16) & 0xFFu), (float)(w >> 24));
+    }
+    if (MODE == kAIm2colU8S) {   // bytes as floats 0..255 through three strides; the `/ 255.0` rides in the other operand as above
+        const uint8_t *p = (const uint8_t *)a.ptr + r.base;
+        if (a.word) {
+            const uint32_t w = *reinterpret_cast<const uint32_t *>(p + k.off);
+            return make_float4((float)(w & 0xFFu), (float)((w >> 8) & 0xFFu), (float)((w >> 16) & 0xFFu), (float)(w >> 24));
+        }
+        return make_float4((float)p[k.off], (float)p[k.o1], (float)p[k.o2], (float)p[k.o3]);
     }
     if (MODE == kACol2im && ((unsigned)(r.y - k.p) >= (unsigned)a.g.OH || (unsigned)(r.x - k.q) >= (unsigned)a.g.OW))
         return make_float4(0.f, 0.f, 0.f, 0.f);
@@ -286,7 +347,9 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_kernel(IgA A, int M,
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + wv * 16 * MI + a * 16 + 4 * g + r;
             size_t orow = (size_t)m;
-            if (MODE == kACol2im) {   // -> input pixel
+            bool inside = true;
+            if (MODE == kACol2im) {   // -> input pixel; a slot of a ragged phase (IH or IW not a multiple of S) may lie past the edge
+                inside = eyy * A.g.S + py < A.g.IH && exx * A.g.S + px < A.g.IW;
                 orow = ((size_t)en * A.g.IH + (size_t)(eyy * A.g.S + py)) * A.g.IW + (size_t)(exx * A.g.S + px);
                 if (++exx == A.WP) {
                     exx = 0;
@@ -296,7 +359,7 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_kernel(IgA A, int M,
                     }
                 }
             }
-            if (m >= M) continue;
+            if (m >= M || !inside) continue;
 #pragma unroll
             for (int b = 0; b < NI; ++b) {
                 const int n = n0 + b * 16 + c;
@@ -350,7 +413,7 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_split_kernel(IgA A, 
                                                                         const float *__restrict__ mask, int ldmask) {
     constexpr int TM = 64 * MI, TN = 16 * NI, RS = kIgSplitRS, PLANE = (TM + TN) * RS;
     constexpr int RPP = 32, LA = TM / RPP, LB = TN / RPP;      // loader: 8 threads per slab row, 32 rows per pass
-    constexpr bool kAInt = MODE == kAIm2colU8;                // A = bytes as floats: exact in ONE bf16 piece
+    constexpr bool kAInt = MODE == kAIm2colU8 || MODE == kAIm2colU8S;                // A = bytes as floats: exact in ONE bf16 piece
     static_assert(TN % RPP == 0 && LB >= 1 && LB <= 2, "the split form takes 32- and 64-column tiles");
     __shared__ __attribute__((aligned(16))) unsigned char lds[3 * PLANE];
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id(), c = lane & 15, g = lane >> 4;
@@ -455,7 +518,9 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_split_kernel(IgA A, 
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + wv * 16 * MI + a * 16 + 4 * g + r;
             size_t orow = (size_t)m;
+            bool inside = true;
             if (MODE == kACol2im) {
+                inside = eyy * A.g.S + py < A.g.IH && exx * A.g.S + px < A.g.IW;
                 orow = ((size_t)en * A.g.IH + (size_t)(eyy * A.g.S + py)) * A.g.IW + (size_t)(exx * A.g.S + px);
                 if (++exx == A.WP) {
                     exx = 0;
@@ -465,7 +530,7 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_split_kernel(IgA A, 
                     }
                 }
             }
-            if (m >= M) continue;
+            if (m >= M || !inside) continue;
 #pragma unroll
             for (int b = 0; b < NI; ++b) {
                 const int n = n0 + b * 16 + c;
@@ -487,6 +552,7 @@ struct IgM {   // (n, oy, ox) of a row of an im2col operand, advanced by 16 rows
 };
 template <int MODE>
 __device__ __forceinline__ int ig_m_base(const IgA &a, const IgM &r) {
+    if (MODE == kAIm2colU8S) return r.n * a.fb + r.oy * a.g.S * a.sy + r.ox * a.g.S * a.sx;
     return MODE == kAIm2colF32 ? ((r.n * a.g.IH + r.oy * a.g.S) * a.g.IW + r.ox * a.g.S) * a.g.IC
                                  : (r.n * a.g.IC * a.g.IH + r.oy * a.g.S) * a.g.IW + r.ox * a.g.S;
 }
@@ -644,7 +710,8 @@ __global__ void __launch_bounds__(256) igemm_weights_reduce_kernel(const float *
     long long p;
     if (perm == 0) p = i;
     else if (perm == 1) p = (long long)n * K + k;
-    else if (perm == 2) {
+    else if (perm == 2 || perm == 5) {   // 5: the strided uint8 first layer — mode-1 k order, bytes not yet divided by 255
+        if (perm == 5) s /= 255.0;
         const int pix = k / g.IC, ic = k - pix * g.IC, ky = pix / g.KW, kx = pix - ky * g.KW;
         p = (((long long)n * g.IC + ic) * g.KH + ky) * g.KW + kx;
     } else if (perm == 3) {
@@ -695,7 +762,8 @@ __global__ void __launch_bounds__(256) ig_pack_conv_kernel(const float *__restri
     const float v = w[i];
     const int K = g.IC * g.KH * g.KW;
     if (fwd) {   // the uint8 loader hands out raw bytes: its weights carry the `/ 255.0` of models.py:150
-        if (u8_order) fwd[(long long)oc * K + ((long long)ic * g.KH + ky) * g.KW + kx] = v / 255.0f;
+        if (u8_order == 1) fwd[(long long)oc * K + ((long long)ic * g.KH + ky) * g.KW + kx] = v / 255.0f;
+        else if (u8_order == 2) fwd[(long long)oc * K + ((long long)ky * g.KW + kx) * g.IC + ic] = v / 255.0f;   // strided uint8 loader
         else fwd[(long long)oc * K + ((long long)ky * g.KW + kx) * g.IC + ic] = v;
     }
     if (dx) {
@@ -726,7 +794,7 @@ __global__ void __launch_bounds__(256) ig_transpose_kernel(const float *__restri
 
 static int ig_check_a(const pfa_igemm_operand *a, int64_t M, int K) {
     PFA_REQUIRE(a && a->ptr, "igemm: null A operand");
-    PFA_REQUIRE(a->mode >= 0 && a->mode <= 3, "igemm: bad A mode %d", a->mode);
+    PFA_REQUIRE(a->mode >= 0 && a->mode <= 4, "igemm: bad A mode %d", a->mode);
     PFA_REQUIRE(K >= 4 && K % 4 == 0, "igemm: K must be a multiple of 4 (got %d)", K);
     PFA_REQUIRE(((uintptr_t)a->ptr & 15) == 0, "igemm: the A operand must be 16-byte aligned");
     if (a->mode == kADense) {
@@ -743,10 +811,16 @@ static int ig_check_a(const pfa_igemm_operand *a, int64_t M, int K) {
     if (a->mode == kAIm2colU8)
         PFA_REQUIRE(a->KW % 4 == 0 && a->IW % 4 == 0 && a->S % 4 == 0 && (a->IC * a->IH * a->IW) % 4 == 0 && K == a->KH * a->KW * a->IC,
                     "igemm: im2col u8 needs KW, IW, S multiples of 4 (aligned 4-byte patch runs) and K == IC*KH*KW");
+    if (a->mode == kAIm2colU8S) {
+        PFA_REQUIRE(a->IC >= 1 && K == a->KH * a->KW * a->IC && K % kIgBK == 0, "igemm: strided u8 needs K == KH*KW*IC, a multiple of 16");
+        PFA_REQUIRE(a->sc >= 1 && a->sy >= 1 && a->sx >= 1 && a->frame_bytes >= 1 &&
+                        (int64_t)(a->IC - 1) * a->sc + (int64_t)(a->IH - 1) * a->sy + (int64_t)(a->IW - 1) * a->sx < a->frame_bytes,
+                    "igemm: strided u8: the last byte (IC-1)*sc + (IH-1)*sy + (IW-1)*sx must lie inside a frame of frame_bytes");
+        PFA_REQUIRE(frames * a->frame_bytes < (1ll << 31), "igemm: operand too large for 32-bit element offsets (split the rows)");
+    }
     if (a->mode == kACol2im)
-        PFA_REQUIRE(a->OC % 4 == 0 && K == a->KH * a->KW * a->OC && a->KH % a->S == 0 && a->KW % a->S == 0 && a->IH % a->S == 0 && a->IW % a->S == 0 &&
-                        true,
-                    "igemm: col2im needs OC %% 4 == 0, K == KH*KW*OC, and KH, KW, IH, IW multiples of the stride");
+        PFA_REQUIRE(a->OC % 4 == 0 && K == a->KH * a->KW * a->OC && a->KH % a->S == 0 && a->KW % a->S == 0,
+                    "igemm: col2im needs OC %% 4 == 0, K == KH*KW*OC, and KH, KW multiples of the stride");
     return 0;
 }
 static int g_ig_products = 0;   // 0: exact fp32 MFMA products (default); 1: six-term bf16 split products in the rows form
@@ -758,11 +832,21 @@ static IgA ig_make_a(const pfa_igemm_operand *a) {
     r.lda = (int)a->lda;
     r.g = IgGeom{a->IC, a->IH, a->IW, a->OC, a->OH, a->OW, a->KH, a->KW, a->S};
     r.JH = r.JW = r.HP = r.WP = 0;
-    if (a->mode == kACol2im) {
+    r.sc = r.sy = r.sx = r.fb = r.word = r.adv_pix = r.adv_ch = 0;
+    if (a->mode == kACol2im) {   // ragged phases: slots past the edge are computed and dropped by the epilogue
         r.JH = a->KH / a->S;
         r.JW = a->KW / a->S;
-        r.HP = a->IH / a->S;
-        r.WP = a->IW / a->S;
+        r.HP = (a->IH + a->S - 1) / a->S;
+        r.WP = (a->IW + a->S - 1) / a->S;
+    }
+    if (a->mode == kAIm2colU8S) {
+        r.sc = a->sc;
+        r.sy = a->sy;
+        r.sx = a->sx;
+        r.fb = a->frame_bytes;
+        r.word = a->IC == 4 && a->sc == 1 && a->sx % 4 == 0 && a->sy % 4 == 0 && a->frame_bytes % 4 == 0;
+        r.adv_pix = kIgBK / a->IC;
+        r.adv_ch = kIgBK % a->IC;
     }
     return r;
 }
@@ -826,7 +910,7 @@ extern "C" int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, 
     if (A.mode == kACol2im) {   // S*S phases of M / (S*S) pixels, each contracting over its own K / (S*S) taps x channels
         phases = A.g.S * A.g.S;
         PFA_REQUIRE(M % ((long long)A.g.IH * A.g.IW) == 0, "igemm.rows: col2im rows must be whole frames");
-        Mp = M / phases;
+        Mp = M / ((long long)A.g.IH * A.g.IW) * A.HP * A.WP;   // pixel slots per phase (== M / phases when IH, IW are multiples of S)
         Kp = K / phases;
     }
     PFA_REQUIRE(Kp % kIgBK == 0 && ldb >= Kp, "igemm.rows: the contraction length (per phase) must be a multiple of 16 and ldb >= it");
@@ -840,6 +924,7 @@ extern "C" int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, 
         case kADense: PFA_IG_ROWS(kADense, MI, NI); break;           \
         case kAIm2colF32: PFA_IG_ROWS(kAIm2colF32, MI, NI); break;   \
         case kAIm2colU8: PFA_IG_ROWS(kAIm2colU8, MI, NI); break;     \
+        case kAIm2colU8S: PFA_IG_ROWS(kAIm2colU8S, MI, NI); break;   \
         default: PFA_IG_ROWS(kACol2im, MI, NI); break;               \
     }
     // A dense product over few rows (one rollout step of the width-general policies: 4096 rows) fills the chip only with 64-row tiles.
@@ -855,6 +940,7 @@ extern "C" int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, 
         case kADense: PFA_IG_SPLIT(kADense, NI); break;              \
         case kAIm2colF32: PFA_IG_SPLIT(kAIm2colF32, NI); break;      \
         case kAIm2colU8: PFA_IG_SPLIT(kAIm2colU8, NI); break;        \
+        case kAIm2colU8S: PFA_IG_SPLIT(kAIm2colU8S, NI); break;      \
         default: PFA_IG_SPLIT(kACol2im, NI); break;                  \
     }
         if (tn == 64) {
@@ -910,7 +996,7 @@ extern "C" int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t 
     PFA_REQUIRE(a->mode != kACol2im, "igemm.weights: the col2im operand belongs to the rows form");
     PFA_REQUIRE(M >= 1 && M < (1ll << 31) && D && out && workspace && N >= 16 && N % 16 == 0 && ldd >= N && ldd % 4 == 0 && ((uintptr_t)D & 15) == 0,
                 "igemm.weights: bad shapes");
-    PFA_REQUIRE(perm >= 0 && perm <= 4, "igemm.weights: bad permutation");
+    PFA_REQUIRE(perm >= 0 && perm <= 5, "igemm.weights: bad permutation");
     const IgA A = ig_make_a(a);
     const IgWeightPlan p = ig_weight_plan(M, K, N);
     float *partial = (float *)workspace;
@@ -925,11 +1011,13 @@ extern "C" int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t 
     if (p.kj == 4) PFA_IG_WEIGHTS(MODE, 4, NI);                      \
     else if (p.kj == 3) PFA_IG_WEIGHTS(MODE, 3, NI);                 \
     else if (p.kj == 1 && MODE == kADense) PFA_IG_WEIGHTS(kADense, 1, NI); \
+    else if (p.kj == 1 && MODE == kAIm2colU8S) PFA_IG_WEIGHTS(kAIm2colU8S, 1, NI); \
     else PFA_IG_WEIGHTS(MODE, 2, NI);
 #define PFA_IG_WEIGHTS_MODE(NI)                                        \
     switch (A.mode) {                                                  \
         case kADense: PFA_IG_WEIGHTS_KJ(kADense, NI) break;            \
         case kAIm2colF32: PFA_IG_WEIGHTS_KJ(kAIm2colF32, NI) break;    \
+        case kAIm2colU8S: PFA_IG_WEIGHTS_KJ(kAIm2colU8S, NI) break;    \
         default: PFA_IG_WEIGHTS_KJ(kAIm2colU8, NI) break;              \
     }
         if (p.tn == 64) {

@@ -110,7 +110,7 @@ int check_frames_config(const pfa_synth_config *c) {
     PFA_REQUIRE(c->num_envs >= 1, "frames: num_envs must be >= 1");
     PFA_REQUIRE(c->obs_values >= 16 && c->obs_values % 16 == 0 && c->obs_stride == c->obs_values && c->obs_high == 255,
                 "frames: rows are obs_values = obs_stride bytes (a multiple of 16) of uniform 0..255");
-    PFA_REQUIRE(c->num_actions >= 2 && c->num_actions <= 15, "frames: num_actions must be in 2..15");
+    PFA_REQUIRE(c->num_actions >= 2 && c->num_actions <= 63, "frames: num_actions must be in 2..63");   // (what the conv policies' heads take)
     PFA_REQUIRE(c->episode_length >= 1, "frames: bad episode_length");
     return 0;
 }

@@ -86,7 +86,9 @@ class GeneralParams:
             self.features = int(self.cnn.actor.weight.shape[1])
             convs = [m for m in self.cnn.network if isinstance(m, nn.Conv2d)]
             self.framestack = int(convs[0].weight.shape[1])
-            self.obs_dim = self.obs_stride = self.framestack * 84 * 84
+            from .models import conv_geometry_of
+            self.geometry = conv_geometry_of(policy_module)       # frame shape + channel order + downsample -> strides, layer sizes
+            self.obs_dim = self.obs_stride = self.geometry.frame_bytes
         else:
             self.kind = 'mlp'
             self.nvec = decoder_heads(self.mlp)
@@ -154,6 +156,7 @@ class _ConvAdapter:
         self.gp = gp
         self.flat = gp.flat
         self.framestack = gp.framestack
+        self.geometry = gp.geometry
         self.num_actions = gp.num_actions
         self.count = gp.count
         self.prefix = {}
@@ -429,6 +432,8 @@ class Engine:
         self.net = _net_for_general(gp, conv_chunk=min(frames_per_chunk, 2048))
         self.state = None
         self.norm_partials = torch.zeros(1024, dtype=torch.float64, device=self.dev)
+        if self.net.kind == 'cnn':          # (32-bit element offsets bound a kernel batch of large frames)
+            frames_per_chunk = min(frames_per_chunk, self.net.conv.max_chunk)
         self.frames_per_chunk = frames_per_chunk
         self.lstm_h = self.lstm_c = None
         self._step_rows = 0
@@ -620,12 +625,18 @@ class Engine:
                 u['h0'][k0:k0 + rc].copy_(hs[Th - 1])
                 u['c0'][k0:k0 + rc].copy_(c[Th])
                 head_in, ldh = hs, Hl
+            elif net.kind == 'cnn':      # no LSTM above the conv stack (more actions than the conv engine's 16-lane heads take): the rows
+                #                          stay segment-major, the hidden vector is read where the conv engine left it
+                _lib.check(L.pfa_cnn_gather_frames(_lib.ptr(exp.obs), net.conv.frame_bytes, B, mb, C.byref(hp), k0 * Th, rows,
+                                                   _lib.ptr(u['frames']), stream), 'gather_frames')
+                head_in, ldh = net.conv.forward(u['frames'], rows), F
             else:
                 net.encode(u['obs'], rows, u['feat'], F)
                 head_in, ldh = u['feat'], F
+            time_major = 0 if (net.kind == 'cnn' and not net.lstm) else rc
             # ---- heads + loss -----------------------------------------------------------------------------------------------
             net.head_outputs(head_in, ldh, rows, u['out'])
-            _lib.check(L.pfa_heads_rows_loss(_lib.ptr(u['out']), NO, C.byref(exp.c), B, mb, k0 * Th, rows, rc, net.A, net.heads, C.byref(hp),
+            _lib.check(L.pfa_heads_rows_loss(_lib.ptr(u['out']), NO, C.byref(exp.c), B, mb, k0 * Th, rows, time_major, net.A, net.heads, C.byref(hp),
                                              _lib.ptr(adv_stats), global_mb_rows, _lib.ptr(u['dout']), NO, NO, _lib.ptr(tail), 1 if acc else 0,
                                              _lib.ptr(u['loss_ws']), stream), 'heads_rows_loss')
             gemm_weights(head_in, ldh, rows, FH, u['dout'], NO, NO, u['g2v'], acc, u['gb2v'], u['ws'])
@@ -649,7 +660,7 @@ class Engine:
                 else:
                     rows_perm(dxh, ldx, u['dpre'], F, rows, F, rc, Th, False, act=xh, lda=ldx)     # and back to segment-major
             else:
-                gemm_rows(u['dout'], NO, rows, NO, net.w2vT, NO, FH, u['dpre'], F, EPI_MASK, None, u['feat'], F)
+                gemm_rows(u['dout'], NO, rows, NO, net.w2vT, NO, FH, u['dpre'], F, EPI_MASK, None, head_in, F)
             # ---- encoder backward -------------------------------------------------------------------------------------------
             if net.kind == 'mlp':
                 gemm_weights(u['obs'], net.Kp, rows, net.Kp, u['dpre'], F, F, u['g1'], acc, u['gb1'], u['ws'])

@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .conv_geometry import ConvGeometry, default_obs_shape
 
 HIDDEN = 128
 
@@ -73,18 +74,31 @@ class LSTMWrapper(nn.Module):
 
 
 class Convolutional(nn.Module):
-    """pufferlib.models.Convolutional (models.py:113-157), the CleanRL NatureCNN used for Atari: the same modules, names
+    """pufferlib.models.Convolutional (models.py:113-157), the CleanRL NatureCNN: the same signature, modules, names
     (``network.0/2/4/7``, ``actor``, ``value_fn``) and initialisation (layer_init: orthogonal sqrt(2), actor 0.01, value 1), so
-    state_dicts are interchangeable with the reference.  Parameter container: the arithmetic runs in csrc/igemm.hip /
-    csrc/cnn_heads.hip through pufferlib_amd.cnn.Engine."""
+    state_dicts are interchangeable with the reference.  Any uint8 frame shape the three valid-padding convolutions fit in,
+    channel-first or ``channels_last``, with the ``downsample`` pixel stride; ``flat_size`` must be what the conv stack yields on the
+    env's frames (ValueError otherwise — the reference fails there with a shape error inside nn.Linear).  Parameter container: the
+    arithmetic runs in csrc/igemm.hip / csrc/cnn_heads.hip through pufferlib_amd.cnn.Engine."""
 
     def __init__(self, env, *args, framestack=4, flat_size=64 * 7 * 7, input_size=512, hidden_size=512, output_size=512,
                  channels_last=False, downsample=1, **kwargs):
         super().__init__()
-        if channels_last or downsample != 1 or hidden_size != 512 or output_size != 512 or flat_size != 64 * 7 * 7:
-            raise NotImplementedError('pufferlib_amd.models.Convolutional runs the Atari geometry: uint8 (framestack, 84, 84) frames, '
-                                      'flat_size 3136, hidden 512')
+        if hidden_size < 16 or hidden_size % 16 != 0:
+            raise ValueError(f'pufferlib_amd.models.Convolutional: hidden_size must be a multiple of 16 (got {hidden_size})')
+        if output_size != hidden_size:      # (both heads read the same hidden vector, models.py:154-157)
+            raise NotImplementedError(f'pufferlib_amd.models.Convolutional: output_size {output_size} != hidden_size {hidden_size}: a '
+                                      'value head that reads anything but the hidden vector is not built (the reference fails in forward)')
         self.framestack = int(framestack)
+        self.channels_last = bool(channels_last)
+        self.downsample = int(downsample)
+        space = getattr(env, 'single_observation_space', None)
+        self.obs_shape = tuple(int(x) for x in space.shape) if space is not None else None    # None: the Atari default (conv_geometry)
+        geom = ConvGeometry(self.obs_shape or default_obs_shape(framestack, channels_last), channels_last, downsample)
+        if geom.channels != self.framestack:
+            raise ValueError(f'pufferlib_amd.models.Convolutional: framestack {framestack} but the frames have {geom.channels} channels '
+                             f'(shape {geom.obs_shape}, channels_last={self.channels_last})')
+        geom.check_flat_size(flat_size)
         self.network = nn.Sequential(
             layer_init(nn.Conv2d(framestack, 32, 8, stride=4)), nn.ReLU(),
             layer_init(nn.Conv2d(32, 64, 4, stride=2)), nn.ReLU(),
@@ -108,13 +122,48 @@ def find_cnn(module):
     return None
 
 
+def conv_geometry_of(policy_module, obs_shape=None):
+    """ConvGeometry of the Convolutional-shaped module inside `policy_module` (ours or the reference's: both carry ``channels_last``
+    and ``downsample``).  The frame shape cannot be read off the weights (flat_size fixes only the conv3 output), so it travels:
+    `obs_shape` (the vecenv's, handed in by clean_pufferl.create), else what our Convolutional / an LSTMWrapper recorded from its
+    env, else the Atari default (framestack, 84, 84).  Validates it against the module's layers."""
+    net = find_cnn(policy_module)
+    convs = [m for m in net.network if isinstance(m, nn.Conv2d)]
+    fc = [m for m in net.network if isinstance(m, nn.Linear)]
+    framestack = int(convs[0].weight.shape[1])
+    channels_last = bool(getattr(net, 'channels_last', False))
+    downsample = int(getattr(net, 'downsample', 1))
+    if obs_shape is None:
+        obs_shape = getattr(net, '_pfa_obs_shape', None) or getattr(net, 'obs_shape', None)
+    if obs_shape is None:
+        for m in policy_module.modules():
+            if m is not net and getattr(m, 'obs_shape', None) is not None and len(m.obs_shape) == 3:
+                obs_shape = m.obs_shape
+                break
+    if obs_shape is None:
+        obs_shape = default_obs_shape(framestack, channels_last)
+    geom = ConvGeometry(tuple(obs_shape), channels_last, downsample)
+    if geom.channels != framestack:
+        raise ValueError(f'frames of shape {geom.obs_shape} (channels_last={channels_last}) have {geom.channels} channels, '
+                         f'the first conv layer reads {framestack}')
+    geom.check_flat_size(int(fc[0].weight.shape[1]))
+    return geom
+
+
+def set_conv_obs_shape(policy_module, obs_shape):
+    """Record the env's frame shape on a Convolutional-shaped module built elsewhere (clean_pufferl.create, the cleanrl wrappers)."""
+    net = find_cnn(policy_module)
+    if net is not None and obs_shape is not None and len(tuple(obs_shape)) == 3:
+        net.__dict__['_pfa_obs_shape'] = tuple(int(x) for x in obs_shape)
+
+
 class ConvParams:
     """One flat fp32 device buffer holding the NatureCNN parameters in named_parameters() order (network.0.weight, .bias,
     network.2.*, network.4.*, network.7.*, actor.*, value_fn.*), every module parameter re-pointed at its view: module,
     kernels, optimizer and checkpoints see the same bytes.  The interface the trainer uses matches FlatParams."""
     multidiscrete = False
 
-    def __init__(self, policy_module, device):
+    def __init__(self, policy_module, device, obs_shape=None):
         net = find_cnn(policy_module)
         if net is None:
             raise ValueError('policy has no network/actor/value_fn (models.Convolutional shape)')
@@ -129,14 +178,15 @@ class ConvParams:
             if ws[0] != shape[0] or ws[2:] != shape[2:] or (shape[1] is not None and ws[1] != shape[1]) or tuple(cv.stride) != stride \
                     or tuple(cv.padding) != (0, 0):
                 raise NotImplementedError(f'conv layer {ws} stride {cv.stride}: only the NatureCNN geometry is built')
-        if tuple(fc[0].weight.shape) != (512, 3136):
-            raise NotImplementedError('Linear(3136, 512) expected behind the conv stack')
+        self.hidden = int(fc[0].weight.shape[0])
+        if self.hidden % 16 != 0 or self.hidden > 1024 or tuple(net.actor.weight.shape[1:]) != (self.hidden,) \
+                or tuple(net.value_fn.weight.shape) != (1, self.hidden):
+            raise NotImplementedError(f'hidden width {self.hidden}: a multiple of 16 up to 1024, read by both heads')
         self.framestack = int(convs[0].weight.shape[1])
-        if (self.framestack * 8) % 4 != 0:
-            raise NotImplementedError('framestack')
+        self.geometry = conv_geometry_of(policy_module, obs_shape)
         self.num_actions = int(net.actor.weight.shape[0])
-        if self.num_actions > 15:
-            raise NotImplementedError('the head kernels take up to 15 actions')
+        if self.num_actions > 15:       # (cleanrl.needs_general sends wider action sets through general.GeneralParams)
+            raise NotImplementedError('the 16-lane head kernels take up to 15 actions; 16..63 run on the GEMM path (general.py)')
         self.nvec = [self.num_actions]
         self.names = [n for n, _ in net.named_parameters()]
         sizes = [p.numel() for _, p in net.named_parameters()]
@@ -148,7 +198,7 @@ class ConvParams:
                 v = self.views[name]
                 v.copy_(p.detach().to(device=device, dtype=torch.float32))
                 p.data = v
-        self.obs_dim = self.obs_stride = self.framestack * 84 * 84
+        self.obs_dim = self.obs_stride = self.geometry.frame_bytes
 
     def split(self, flat):
         out, o = {}, 0

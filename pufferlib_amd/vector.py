@@ -773,40 +773,46 @@ class Synthetic(_DeviceVecEnv):
                    'last_infos')
 
 
-def make_frames(framestack=4, num_actions=4, episode_length=100, **kwargs):
+def make_frames(framestack=4, num_actions=4, episode_length=100, height=84, width=84, channels_last=False, **kwargs):
     """Env creator token of the synthetic frame env (BASELINE configs[3]'s workload shape, SURVEY config C4: uint8
     (framestack, 84, 84) observations uniform in 0..255 as the Atari wrappers hand them to the NatureCNN, atari/environment.py:14-41,
-    4 actions like Breakout)."""
-    return FramesSpec(framestack, num_actions, episode_length)
+    4 actions like Breakout).  height / width / channels_last give the other frame shapes models.Convolutional is bound to —
+    (height, width, framestack) rows for the channel-last ones; the byte stream of a row does not depend on the shape's order."""
+    return FramesSpec(framestack, num_actions, episode_length, height, width, channels_last)
 
 
 class FramesSpec(_SimpleSpec):
-    def __init__(self, framestack=4, num_actions=4, episode_length=100):
+    def __init__(self, framestack=4, num_actions=4, episode_length=100, height=84, width=84, channels_last=False):
         super().__init__(0, 255, int(num_actions))
         self.framestack, self.num_actions, self.episode_length = int(framestack), int(num_actions), int(episode_length)
-        self.single_observation_space = spaces.Box(low=0, high=255, shape=(self.framestack, 84, 84), dtype=np.uint8)
+        self.height, self.width, self.channels_last = int(height), int(width), bool(channels_last)
+        self.shape = (self.height, self.width, self.framestack) if self.channels_last else (self.framestack, self.height, self.width)
+        if (self.framestack * self.height * self.width) % 16 != 0:
+            raise APIUsageError(f'frames of shape {self.shape}: the device env writes rows of a multiple of 16 bytes')
+        self.single_observation_space = spaces.Box(low=0, high=255, shape=self.shape, dtype=np.uint8)
         self.observation_space = self.single_observation_space
         self.emulated = namespace(observation_dtype=np.dtype(np.uint8),
-                                  emulated_observation_dtype=np.dtype((np.uint8, (self.framestack, 84, 84))))
+                                  emulated_observation_dtype=np.dtype((np.uint8, self.shape)))
 
 
 class Frames(Synthetic):
-    """Device-resident synthetic frame vecenv: the byte generator of ``Synthetic`` writing uint8 (framestack, 84, 84) rows, reward 1
+    """Device-resident synthetic frame vecenv: the byte generator of ``Synthetic`` writing uint8 (framestack, 84, 84) rows (or any
+    other frame shape, channel-first or channel-last: make_frames), reward 1
     when the action equals byte 0 of the shown frame modulo the action count.  Atari itself is a third-party emulator outside the
     reference tree (parity unpinned), so the workload keeps its observation / action shapes."""
-    FAMILY, NAMES, DEFAULTS = 'frames', ('framestack', 'num_actions', 'episode_length'), (4, 4, 100)
+    FAMILY, NAMES, DEFAULTS = 'frames', ('framestack', 'num_actions', 'episode_length', 'height', 'width', 'channels_last'), (4, 4, 100, 84, 84, False)
     OBS_U8 = True
     ROLLOUT_LSTM = None     # byte rows: a recurrent policy over frames is a conv LSTM, which runs on the GEMM-path engine
 
-    def _spec(self, framestack, num_actions, episode_length):
-        self.obs_stride = int(framestack) * 84 * 84            # bytes per row
-        return FramesSpec(framestack, num_actions, episode_length)
+    def _spec(self, framestack, num_actions, episode_length, height=84, width=84, channels_last=False):
+        self.obs_stride = int(framestack) * int(height) * int(width)            # bytes per row
+        return FramesSpec(framestack, num_actions, episode_length, height, width, channels_last)
 
     def _alloc_state(self):
         import torch
         sp = self.driver_env
         self.obs_dim = self.obs_stride
-        self.observations = self.obs_buf.view(self.num_agents, sp.framestack, 84, 84)
+        self.observations = self.obs_buf.view(self.num_agents, *sp.shape)
         self.episode_len = sp.episode_length + 1
         self.cfg = _lib.SynthConfig(self.num_agents, self.obs_stride, self.obs_stride, sp.num_actions, sp.episode_length, 255, 0, self.env_offset)
         nbytes = self.L.pfa_synth_state_bytes(C.byref(self.cfg))
