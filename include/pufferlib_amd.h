@@ -589,6 +589,13 @@ int pfa_store_rows(const pfa_experience *exp, int32_t rows, int32_t num_slots, i
                    const float *rewards, const uint8_t *dones, const int64_t *actions, const float *logprob,
                    const float *value, const int32_t *env_ids, const uint8_t *mask, int32_t *counters,
                    int32_t *stored_dropped, pfa_stream_t stream);
+/* The same for uint8 frame rows of row_bytes bytes each, any size, copied byte by byte in a kernel of its own.  pfa_store_rows moves
+ * a row as float4s (obs_stride a multiple of 4 floats), so it takes frame rows only where their size is a multiple of 16 bytes; frames
+ * such as 9 x 7 x 3 (189 bytes) or 9 x 7 x 4 (252 bytes) go through this entry point. */
+int pfa_store_rows_bytes(const pfa_experience *exp, int32_t rows, int32_t num_slots, int32_t row_bytes, const uint8_t *obs,
+                         const float *rewards, const uint8_t *dones, const int64_t *actions, const float *logprob,
+                         const float *value, const int32_t *env_ids, const uint8_t *mask, int32_t *counters,
+                         int32_t *stored_dropped, pfa_stream_t stream);
 /* Observation rows of minibatch mb in TIME-MAJOR order (row t*R + k = segment mb + k*nmb, step t). */
 int pfa_gather_obs_time_major(const pfa_experience *exp, int64_t batch_rows, int32_t mb, const pfa_ppo_hparams *hp,
                               int32_t obs_stride, float *out, pfa_stream_t stream);
@@ -671,6 +678,24 @@ int pfa_dist_info(int64_t *out8);
  *                           contracting over the (KH/S)(KW/S) taps that reach it: k = (jy*(KW/S) + jx)*OC + oc, tap (py + jy*S, px + jx*S).
  *                           IH, IW need not be multiples of S (phases of ceil(IH/S) x ceil(IW/S) slots, those past the edge dropped);
  *                           pixels no window covers receive exactly 0
+ *   mode 5 same-padded im2col, f32 (the 3 x 3 padding-1 convolutions of pufferlib.models.ProcgenResnet, models.py:198-231): stride 1,
+ *                           odd KH = KW, padding (KH-1)/2, OH = IH, OW = IW, IC a multiple of 4; ptr = NHWC activations, m = (n, oy, ox),
+ *                           k = (ky*KW + kx)*IC + ic; tap (oy + ky - pad, ox + kx - pad) reads 0 outside the image (one test per k-quad).
+ *                           Bit 0 of `reserved` = ReLU on load: the operand is relu(ptr) (a residual block's conv0 and its dW, while the
+ *                           skip connection reads ptr itself).  dX of such a layer is the same mode on dOut (IC and OC swapped) against
+ *                           the flipped kernel pfa_cnn_pack_conv_same writes: no col2im phases
+ *   mode 6 same-padded im2col, uint8, strided: byte (ic, y, x) at ic*sc + y*sy + x*sx as in mode 4, IC = 1..4, one bounds test per
+ *                           element; K = KH*KW*IC for pfa_igemm_weights (perm 5), that rounded up to 16 for the rows form (the elements
+ *                           past KH*KW*IC read as 0 and meet zero weight columns).  `/ 255.0` as in modes 2 and 4
+ *                           Modes 5 and 6 always run the exact fp32 kernel: pfa_igemm_set_products(1) does not reach them.
+ * pfa_igemm_rows_add: pfa_igemm_rows for modes 5 and 6 with the residual epilogues: 4 (acc + bias[n]) + addend[m][n] (x + conv1(..)),
+ *                    5 relu of that (the last block, read only through Flatten - ReLU), 6 (zero where mask[m][n] <= 0) + addend[m][n]
+ *                    (dX of a block's conv0 joined with the skip gradient); epilogues 0..3 as below.  addend must not be the output.
+ * pfa_cnn_pack_conv_same: torch weights of a mode 5 / 6 layer -> forward B [OC][ldf] (columns KH*KW*IC .. ldf-1 are left alone: keep them
+ *                    zero; u8 != 0: weights / 255) and dX B [IC][KH*KW*OC] (nullable), the kernel flipped in both axes.
+ * pfa_maxpool3s2_forward / _backward: max_pool2d(kernel 3, stride 2, padding 1) on NHWC f32 [n][H][W][C] -> [n][(H+1)/2][(W+1)/2][C], C a
+ *                    multiple of 4; the backward is a gather (each input pixel sums the dOut of the windows whose first maximum it
+ *                    is — torch's tie rule), deterministic, no atomics.
  * pfa_igemm_rows:    C[m][n] = epilogue(sum_k A(m,k) B[n][k]) with B row-major [N][ldb] (k contiguous; mode 3: [S*S][N][ldb], K =
  *                    KH*KW*OC in total), epilogue 0 none, 1 + bias[n], 2 relu(+ bias[n]), 3 zero where mask[m][n] <= 0 (relu' read
  *                    where the forward left it).  N a multiple of 16, the contraction length (per phase) of 16.
@@ -694,11 +719,11 @@ int pfa_dist_info(int64_t *out8);
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int32_t mode;
-    int32_t reserved;
+    int32_t reserved;                                 /* 0; mode 5: bit 0 = ReLU on load */
     const void *ptr;
     int64_t lda;                                      /* dense only */
-    int32_t IC, IH, IW, OC, OH, OW, KH, KW, S;        /* conv geometry (valid padding) */
-    int32_t sc, sy, sx, frame_bytes;                  /* mode 4 only (0 otherwise): byte strides of channel / row / column, bytes per frame */
+    int32_t IC, IH, IW, OC, OH, OW, KH, KW, S;        /* conv geometry (valid padding; modes 5, 6: same padding, OH = IH, OW = IW, S = 1) */
+    int32_t sc, sy, sx, frame_bytes;                  /* modes 4 and 6 only (0 otherwise): byte strides of channel / row / column, bytes per frame */
 } pfa_igemm_operand;
 int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
                    int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, pfa_stream_t stream);
@@ -716,6 +741,13 @@ int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t K, const fl
 size_t pfa_colsum_workspace_bytes(int32_t N);
 int pfa_colsum(const float *D, int64_t M, int32_t N, int32_t ldd, float *out, int32_t accumulate, void *workspace, pfa_stream_t stream);
 int pfa_cnn_pack_conv(const float *w, const pfa_igemm_operand *geom, int32_t u8_order, float *fwd, float *dx, pfa_stream_t stream);
+int pfa_igemm_rows_add(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
+                       int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd,
+                       pfa_stream_t stream);
+int pfa_cnn_pack_conv_same(const float *w, const pfa_igemm_operand *geom, int32_t u8, float *fwd, int32_t ldf, float *dx, pfa_stream_t stream);
+int pfa_maxpool3s2_forward(const float *in, int64_t frames, int32_t H, int32_t W, int32_t channels, float *out, pfa_stream_t stream);
+int pfa_maxpool3s2_backward(const float *in, const float *out, const float *dout, int64_t frames, int32_t H, int32_t W, int32_t channels,
+                            float *din, pfa_stream_t stream);
 int pfa_cnn_transpose(const float *w, int32_t N, int32_t K, float *out, pfa_stream_t stream);
 /* Linear(channels*hw, N) behind nn.Flatten of an NCHW tensor (models.py:133) for NHWC activations: perm_out [N][K'] with the
  * columns in NHWC order (B of the forward), t_out [K'][N] (B of dX); pfa_igemm_weights perm 4 undoes the order for dW. */

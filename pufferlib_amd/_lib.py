@@ -99,7 +99,7 @@ class SynthConfig(C.Structure):
 class IgemmOperand(C.Structure):
     _fields_ = [('mode', C.c_int32), ('reserved', C.c_int32), ('ptr', C.c_void_p), ('lda', C.c_int64), ('IC', C.c_int32), ('IH', C.c_int32),
                 ('IW', C.c_int32), ('OC', C.c_int32), ('OH', C.c_int32), ('OW', C.c_int32), ('KH', C.c_int32), ('KW', C.c_int32), ('S', C.c_int32),
-                ('sc', C.c_int32), ('sy', C.c_int32), ('sx', C.c_int32), ('frame_bytes', C.c_int32)]   # mode 4 (strided uint8 frames) only
+                ('sc', C.c_int32), ('sy', C.c_int32), ('sx', C.c_int32), ('frame_bytes', C.c_int32)]   # modes 4 / 6 (strided uint8 frames) only
 
 
 class MlpDims(C.Structure):
@@ -229,6 +229,7 @@ _SIGNATURES = {
                                            C.c_int32, P, P, C.POINTER(C.c_int32), P]),
     'pfa_store_step': (C.c_int, [C.POINTER(Experience), C.c_int32, C.c_int32, C.c_int32, P, P, P, P, P, P, P]),
     'pfa_store_rows': (C.c_int, [C.POINTER(Experience), C.c_int32, C.c_int32, C.c_int32, P, P, P, P, P, P, P, P, P, P, P]),
+    'pfa_store_rows_bytes': (C.c_int, [C.POINTER(Experience), C.c_int32, C.c_int32, C.c_int32, P, P, P, P, P, P, P, P, P, P, P]),
     'pfa_gather_obs_time_major': (C.c_int, [C.POINTER(Experience), C.c_int64, C.c_int32, C.POINTER(PpoHparams), C.c_int32, P, P]),
     'pfa_lstm_heads_loss_workspace_bytes': (C.c_size_t, []),
     'pfa_lstm_heads_loss': (C.c_int, [P, C.POINTER(Experience), C.c_int64, C.c_int32, P, C.POINTER(MlpDims),
@@ -282,6 +283,11 @@ _SIGNATURES = {
     'pfa_colsum_workspace_bytes': (C.c_size_t, [C.c_int32]),
     'pfa_colsum': (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, P, P]),
     'pfa_cnn_pack_conv': (C.c_int, [P, C.POINTER(IgemmOperand), C.c_int32, P, P, P]),
+    'pfa_igemm_rows_add': (C.c_int, [C.POINTER(IgemmOperand), C.c_int64, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, P, C.c_int32, P,
+                                     C.c_int32, P]),
+    'pfa_cnn_pack_conv_same': (C.c_int, [P, C.POINTER(IgemmOperand), C.c_int32, P, C.c_int32, P, P]),
+    'pfa_maxpool3s2_forward': (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P]),
+    'pfa_maxpool3s2_backward': (C.c_int, [P, P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P]),
     'pfa_cnn_transpose': (C.c_int, [P, C.c_int32, C.c_int32, P, P]),
     'pfa_cnn_pack_fc': (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     'pfa_cnn_heads_sample': (C.c_int, [P, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),

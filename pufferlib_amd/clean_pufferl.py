@@ -286,9 +286,19 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
         else:
             policy = Policy(policy, seed=config.seed)     # e.g. the reference's cleanrl.Policy(models.Default)
     recurrent = isinstance(policy, RecurrentPolicy)
-    from .models import conv_geometry_of, find_cnn, set_conv_obs_shape
-    conv = find_cnn(policy) is not None
-    if conv:
+    from .models import conv_geometry_of, find_cnn, find_resnet, set_conv_obs_shape, set_resnet_obs_shape
+    resnet = find_resnet(policy) is not None
+    conv = find_cnn(policy) is not None or resnet       # either one reads uint8 frames and drives the cnn_engine slot
+    if resnet:
+        space = vecenv.single_observation_space
+        if recurrent:
+            raise NotImplementedError('LSTMWrapper over models.ProcgenResnet (procgen\'s Recurrent) is not built: use the feed-forward Policy')
+        if not (host_mode or isinstance(vecenv, Frames)):
+            raise NotImplementedError('models.ProcgenResnet reads uint8 frames: a host vecenv or vector.Frames')
+        if np.dtype(space.dtype) != np.uint8 or len(space.shape) != 3:
+            raise NotImplementedError(f'models.ProcgenResnet reads 3-D uint8 frames (H, W, C), the env shows {space.dtype} {space.shape}')
+        set_resnet_obs_shape(policy, space.shape)      # the frame shape is not in the weights: ResnetParams checks it against them
+    elif conv:
         space = vecenv.single_observation_space
         if not (host_mode or isinstance(vecenv, Frames)):
             raise NotImplementedError('models.Convolutional reads uint8 frames: a host vecenv or vector.Frames')
@@ -299,7 +309,7 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
         set_conv_obs_shape(policy, space.shape)
         conv_geometry_of(policy)
     if isinstance(vecenv, Frames) and not conv:
-        raise NotImplementedError('vector.Frames shows uint8 frame observations: use models.Convolutional')
+        raise NotImplementedError('vector.Frames shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
     if recurrent and isinstance(vecenv, Stochastic):
         raise NotImplementedError('the device-resident Stochastic vecenv has a fused rollout for the MLP policy only '
                                   '(ocean.Stochastic: "do not use a policy with memory", ocean.py:534)')
@@ -352,7 +362,7 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
     elif conv:
         cnn_engine = policy.cnn_engine
         cnn_engine.experience = experience
-        cnn_engine._alloc(min(8192, max(experience.minibatch_size, total_agents)))
+        cnn_engine._alloc(min(4096 if resnet else 8192, max(experience.minibatch_size, total_agents)))
     if recurrent and gen_engine is None:
         from . import lstm as plstm
         lstm_engine = plstm.Engine(fp, experience, vecenv)

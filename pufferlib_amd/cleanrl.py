@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .models import ConvParams, FlatParams, find_cnn
+from .models import ConvParams, FlatParams, ResnetParams, find_cnn, find_resnet
 
 KERNEL_STRIDES = (16, 32, 64, 96, 128)     # observation row strides (floats) every policy kernel is built for
 RECURRENT_STRIDES = KERNEL_STRIDES + (160,)  # the recurrent path also takes MiniGrid-shaped 160-byte rows (SURVEY config C3)
@@ -44,6 +44,13 @@ def _needs_general(policy_module, recurrent):
     from .models import HIDDEN, decoder_heads, find_lstm, find_mlp
     lstm = find_lstm(policy_module)
     cnn = find_cnn(policy_module)
+    resnet = find_resnet(policy_module)
+    if resnet is not None:    # models.ProcgenResnet has its own engine (resnet.py) and no GEMM-path form: what it cannot run is not built
+        if lstm is not None:
+            raise NotImplementedError('LSTMWrapper over models.ProcgenResnet (procgen\'s Recurrent) is not built: use the feed-forward Policy')
+        if int(resnet.actor.weight.shape[0]) > 15:
+            raise NotImplementedError(f'models.ProcgenResnet with {int(resnet.actor.weight.shape[0])} actions: the 16-lane head kernels take up to 15')
+        return False
     if cnn is not None:       # the conv engine's 16-lane head kernels take 15 actions; wider sets sample in the row kernels of the GEMM path
         return lstm is not None or int(cnn.actor.weight.shape[0]) > 15
     mlp = find_mlp(policy_module)
@@ -83,12 +90,14 @@ def _evaluator(self, device, recurrent):
     fused update kernels change the parameters without telling it)."""
     from . import general
     if self._flat is None:
-        D = general.find_mlp(self.policy).encoder.weight.shape[1] if find_cnn(self.policy) is None else 0
+        D = general.find_mlp(self.policy).encoder.weight.shape[1] if find_cnn(self.policy) is None and find_resnet(self.policy) is None else 0
         self.adopt(obs_stride_for(int(D), recurrent) if D else 0, device)
     if getattr(self, '_evaluator', None) is None:
         if isinstance(self._flat, general.GeneralParams):
             eng = getattr(self, 'gen_engine', None)
             net = eng.net if eng is not None else general._net_for_general(self._flat)
+        elif isinstance(self._flat, ResnetParams):
+            raise NotImplementedError('policy(frames, action=...) for models.ProcgenResnet: use train()')
         elif isinstance(self._flat, ConvParams):
             raise NotImplementedError('policy(obs, action=...) for the non-recurrent models.Convolutional: wrap it in LSTMWrapper or use train()')
         else:
@@ -114,6 +123,15 @@ class Policy(torch.nn.Module):
 
     def adopt(self, obs_stride, device):
         """Move the parameters into one flat device buffer (idempotent for the same stride/device)."""
+        if find_resnet(self.policy) is not None and not needs_general(self.policy, False):
+            # models.ProcgenResnet: its own parameter layout and engine (resnet.py), in the slot the NatureCNN's engine takes
+            recorded = find_resnet(self.policy).__dict__.get('_pfa_obs_shape')
+            if (self._flat is None or self._flat.flat.device != torch.device(device)
+                    or (recorded is not None and self._flat.geometry.obs_shape != recorded)):
+                from . import resnet
+                self._flat = ResnetParams(self.policy, device)
+                self.cnn_engine = resnet.Engine(self._flat, chunk=256)    # grows on demand (Engine._alloc)
+            return self._flat
         if find_cnn(self.policy) is not None and not needs_general(self.policy, False):
             # models.Convolutional: its own parameter layout and engine (cnn.py)
             recorded = find_cnn(self.policy).__dict__.get('_pfa_obs_shape')      # (a trainer may have recorded the env's frame shape since)
@@ -154,6 +172,10 @@ class Policy(torch.nn.Module):
         x2 = x.reshape(rows, -1)
         D = x2.shape[1]
         general_shape = needs_general(self.policy, False)
+        if find_resnet(self.policy) is not None:
+            if action is not None:
+                raise NotImplementedError('policy(frames, action=...) for models.ProcgenResnet: use train()')
+            return self._forward_cnn(x2, rows, noise)
         if action is not None or general_shape:
             # given actions (cleanrl.py:60-66 with action=...): log-prob / entropy / value of THOSE actions; or a policy shape that
             # runs in the GEMM path altogether
@@ -238,7 +260,7 @@ def _forward_cnn(self, x2, rows, noise):
         raise ValueError(f'expected frames of {cp.obs_dim} bytes, got rows of {x2.shape[1]}')
     frames = x2.to(torch.uint8).contiguous()       # the reference divides whatever it is given by 255 (models.py:152); frames are bytes
     eng = self.cnn_engine
-    eng._alloc(min(rows, 8192))
+    eng._alloc(min(rows, 8192 if isinstance(cp, ConvParams) else 4096))
     dev = x2.device
     actions = torch.empty(rows, dtype=torch.int64, device=dev)
     logprob = torch.empty(rows, dtype=torch.float32, device=dev)

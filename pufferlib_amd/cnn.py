@@ -131,20 +131,13 @@ class Engine:
         self.experience = experience      # the trainer's buffers (uint8 obs [B][frame_bytes]) for update()
         self.state = None                 # (no recurrent state; the trainer's epoch loop resets it for either engine)
         self.norm_partials = torch.zeros(1024, dtype=torch.float64, device=self.dev)
-        v = cp.views
         dev = self.dev
         geo = getattr(cp, 'geometry', None)
         if geo is None:                     # a parameter buffer that names no geometry: the Atari one
             from .conv_geometry import ConvGeometry, default_obs_shape
             geo = ConvGeometry(default_obs_shape(cp.framestack))
         self.geometry = geo
-        (_, h1, w1, _, h2, w2, _, _, _), (_, _, _, _, h3, w3, _, _, _) = geo.layers[0], geo.layers[1]
-        strides = None if geo.aligned_chw else (geo.sc, geo.sy, geo.sx, geo.frame_bytes)
-        self.conv1 = ConvLayer(v['network.0.weight'], v['network.0.bias'], h1, w1, 4, True, dev, strides)
-        self.conv2 = ConvLayer(v['network.2.weight'], v['network.2.bias'], h2, w2, 2, False, dev)
-        self.conv3 = ConvLayer(v['network.4.weight'], v['network.4.bias'], h3, w3, 1, False, dev)
-        self.fc = LinearLayer(v['network.7.weight'], v['network.7.bias'], True, geo.out_shape, dev)
-        self.layers = [self.conv1, self.conv2, self.conv3, self.fc]
+        self._build_layers(geo)
         self.frame_bytes = geo.frame_bytes
         self.hidden = self.fc.N
         # frames per kernel batch: what 32-bit element offsets allow, and activations (with their gradients) within a quarter of the device
@@ -155,29 +148,45 @@ class Engine:
         self.version = 0          # bumped by whoever changes the weights (optimizer step, checkpoint load)
         self._alloc(chunk)
 
+    def _build_layers(self, geo):
+        """The layer objects over the parameter views: sets self.fc (the Linear behind Flatten) and self.layers (what pack() and the
+        workspace size run over).  An engine of another encoder (resnet.Engine) overrides this, _alloc_maps, forward and backward."""
+        v, dev = self.cp.views, self.dev
+        (_, h1, w1, _, h2, w2, _, _, _), (_, _, _, _, h3, w3, _, _, _) = geo.layers[0], geo.layers[1]
+        strides = None if geo.aligned_chw else (geo.sc, geo.sy, geo.sx, geo.frame_bytes)
+        self.conv1 = ConvLayer(v['network.0.weight'], v['network.0.bias'], h1, w1, 4, True, dev, strides)
+        self.conv2 = ConvLayer(v['network.2.weight'], v['network.2.bias'], h2, w2, 2, False, dev)
+        self.conv3 = ConvLayer(v['network.4.weight'], v['network.4.bias'], h3, w3, 1, False, dev)
+        self.fc = LinearLayer(v['network.7.weight'], v['network.7.bias'], True, geo.out_shape, dev)
+        self.layers = [self.conv1, self.conv2, self.conv3, self.fc]
+
     def _alloc(self, chunk):
         chunk = min(int(chunk), self.max_chunk)
         if chunk <= self.chunk:
             return
         dev, n, H = self.dev, chunk, self.hidden
         self.chunk = n
-        self.a1 = torch.empty(self.conv1.out_rows(n), 32, device=dev)
-        self.a2 = torch.empty(self.conv2.out_rows(n), 64, device=dev)
-        self.a3 = torch.empty(self.conv3.out_rows(n), 64, device=dev)
+        self._alloc_maps(n)
         self.h = torch.empty(n, H, device=dev)
-        self.d1 = torch.empty_like(self.a1)
-        self.d2 = torch.empty_like(self.a2)
-        self.d3 = torch.empty_like(self.a3)
         self.dh = torch.empty_like(self.h)
         self.dout = torch.empty(n, 16, device=dev)
         self.frames = torch.empty(n, self.frame_bytes, dtype=torch.uint8, device=dev)
         L = _lib.lib()
-        ws = max([self.conv1.dw_workspace(n), self.conv2.dw_workspace(n), self.conv3.dw_workspace(n), self.fc.dw_workspace(n),
-                  L.pfa_igemm_weights_workspace_bytes(n, H, 16)])
+        ws = max([layer.dw_workspace(n) for layer in self.layers] + [L.pfa_igemm_weights_workspace_bytes(n, H, 16)])
         self.ws = torch.empty(ws, dtype=torch.uint8, device=dev)
         self.ws_loss = torch.empty(L.pfa_cnn_heads_loss_workspace_bytes(), dtype=torch.uint8, device=dev)
         self.g16 = torch.empty(16, H, device=dev)
         self.gb16 = torch.empty(16, device=dev)
+
+    def _alloc_maps(self, n):
+        """The conv activations of n frames and their gradients."""
+        dev = self.dev
+        self.a1 = torch.empty(self.conv1.out_rows(n), 32, device=dev)
+        self.a2 = torch.empty(self.conv2.out_rows(n), 64, device=dev)
+        self.a3 = torch.empty(self.conv3.out_rows(n), 64, device=dev)
+        self.d1 = torch.empty_like(self.a1)
+        self.d2 = torch.empty_like(self.a2)
+        self.d3 = torch.empty_like(self.a3)
 
     def pack(self):
         if self.packed_version != self.version:

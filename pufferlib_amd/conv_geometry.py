@@ -92,3 +92,43 @@ class ConvGeometry:
 def default_obs_shape(framestack, channels_last=False):
     """Where nobody recorded the env's frame shape: the Atari one."""
     return (84, 84, int(framestack)) if channels_last else (int(framestack), 84, 84)
+
+
+class ResnetGeometry:
+    """pufferlib.models.ProcgenResnet (models.py:159-231) on channel-last uint8 frames (H, W, C): three ConvSequences of
+    Conv2d(3x3, padding 1) -> max_pool2d(3, stride 2, padding 1) -> two residual blocks, widths (w, 2w, 2w).  `seqs` holds
+    (IC, H, W, OC, PH, PW) per sequence: the conv keeps (H, W), the pool yields ((H+1)//2, (W+1)//2)."""
+
+    def __init__(self, obs_shape, cnn_width=16):
+        obs_shape = tuple(int(s) for s in obs_shape)
+        if len(obs_shape) != 3 or min(obs_shape) < 1:
+            raise ValueError(f'models.ProcgenResnet reads 3-D uint8 frames (H, W, C), got shape {obs_shape}')
+        h, w, c = obs_shape
+        self.obs_shape, self.cnn_width = obs_shape, int(cnn_width)
+        self.channels, self.frame_bytes = c, h * w * c
+        self.sc, self.sy, self.sx = 1, w * c, c                        # `permute(0, 3, 1, 2)` is a set of strides, never a copy
+        self.seqs = []
+        ic = c
+        for oc in (self.cnn_width, 2 * self.cnn_width, 2 * self.cnn_width):
+            ph, pw = (h + 1) // 2, (w + 1) // 2
+            self.seqs.append((ic, h, w, oc, ph, pw))
+            ic, h, w = oc, ph, pw
+        self.out_shape = (ic, h, w)                                    # what nn.Flatten sees (NCHW)
+        self.flat_size = ic * h * w
+
+    def elements_per_frame(self):
+        return max([self.frame_bytes] + [oc * h * w for _, h, w, oc, _, _ in self.seqs])
+
+    def max_chunk(self):
+        return max(1, (OFFSET_LIMIT - 1) // self.elements_per_frame() - 1)
+
+    def activation_bytes_per_frame(self):
+        """fp32 maps kept for one frame of a chunk: per sequence the pre-pool map and five block-sized maps, plus the gradients (one
+        pre-pool sized, three block sized), plus the frame."""
+        return self.frame_bytes + 4 * sum(2 * oc * h * w + 8 * oc * ph * pw for _, h, w, oc, ph, pw in self.seqs)
+
+    def chunk_for(self, memory_bytes=None):
+        n = self.max_chunk()
+        if memory_bytes is not None:
+            n = min(n, max(1, int(memory_bytes) // self.activation_bytes_per_frame()))
+        return n

@@ -237,6 +237,16 @@ __global__ void __launch_bounds__(256) cnn_gather_frames_kernel(const uint8_t *f
     }
 }
 
+// the same for frames whose size is not a multiple of 16 bytes (odd frame shapes such as 9 x 7 x 3): byte by byte
+__global__ void __launch_bounds__(256) cnn_gather_frames_bytes_kernel(const uint8_t *frames, long long frame_bytes, RowMap map, long long q0, long long rows,
+                                                                     uint8_t *out) {
+    const long long total = rows * frame_bytes;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / frame_bytes, c = i - r * frame_bytes;
+        out[i] = frames[map.flat(q0 + r) * frame_bytes + c];
+    }
+}
+
 static size_t cnn_heads_lds(int H) { return (size_t)(kOut * (H + 1) + kOut + 16 * H) * sizeof(float); }
 
 template <int HT>
@@ -337,10 +347,18 @@ extern "C" int pfa_cnn_heads_loss(const float *h, const pfa_experience *exp, int
 
 extern "C" int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t batch_rows, int32_t mb, const pfa_ppo_hparams *hp,
                                      int64_t q0, int64_t rows, uint8_t *out, pfa_stream_t stream) {
-    PFA_REQUIRE(frames && out && hp && frame_bytes >= 16 && frame_bytes % 16 == 0, "cnn.gather_frames: frames must be a multiple of 16 bytes");
+    PFA_REQUIRE(frames && out && hp && frame_bytes >= 1, "cnn.gather_frames: null buffer or empty frames");
     PFA_REQUIRE(hp->num_minibatches >= 1 && batch_rows % hp->num_minibatches == 0 && mb >= 0 && mb < hp->num_minibatches, "cnn.gather_frames: bad minibatch");
     PFA_REQUIRE(q0 >= 0 && rows >= 1 && q0 + rows <= batch_rows / hp->num_minibatches, "cnn.gather_frames: chunk outside the minibatch");
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
+    if (frame_bytes % 16 != 0) {
+        const long long bytes = rows * frame_bytes;
+        const unsigned g = (unsigned)((bytes + 255) / 256 < 65535 ? (bytes + 255) / 256 : 65535);
+        hipLaunchKernelGGL(cnn_gather_frames_bytes_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, frames, (long long)frame_bytes, map, (long long)q0,
+                           (long long)rows, out);
+        PFA_LAUNCH_CHECK();
+        return 0;
+    }
     const long long total = rows * (frame_bytes / 16);
     const unsigned grid = (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
     hipLaunchKernelGGL(cnn_gather_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, (long long)frame_bytes, map, (long long)q0,

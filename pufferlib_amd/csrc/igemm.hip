@@ -42,8 +42,13 @@ constexpr int kIgThreads = 256;
 constexpr int kIgBK = 16;
 constexpr int kIgLS = kIgBK + 4;   // LDS row stride (floats) of a [row][16 k] slab
 
-enum IgAMode : int { kADense = 0, kAIm2colF32 = 1, kAIm2colU8 = 2, kACol2im = 3, kAIm2colU8S = 4 };
-enum IgEpilogue : int { kEpiNone = 0, kEpiBias = 1, kEpiBiasRelu = 2, kEpiMask = 3 };
+enum IgAMode : int { kADense = 0, kAIm2colF32 = 1, kAIm2colU8 = 2, kACol2im = 3, kAIm2colU8S = 4, kAIm2colPad = 5, kAIm2colU8P = 6 };
+enum IgEpilogue : int { kEpiNone = 0, kEpiBias = 1, kEpiBiasRelu = 2, kEpiMask = 3, kEpiBiasAdd = 4, kEpiBiasAddRelu = 5, kEpiMaskAdd = 6 };
+// Modes 5 / 6 — the stride-1 same-padded 3 x 3 convolutions of models.ProcgenResnet (models.py:159-231): a tap outside the image reads
+// as 0.  Mode 5 (NHWC f32, IC a multiple of 4: a k-quad lies inside one pixel, one bounds test per quad, the shape of the col2im test)
+// can apply ReLU as it loads (a residual block's conv0 reads relu(x) while the skip needs x itself); mode 6 reads strided uint8 frames
+// with 1..4 channels (a quad may straddle pixels: one test per element; elements past KH*KW*IC read as 0 so the rows form can run K
+// rounded up to 16).  Their epilogues 4..6 add a second [m][n] operand: the residual sum of the forward and of dX.
 
 // One conv layer (valid padding): input [N][IH][IW][IC] (NHWC f32) or uint8 [N][IC][IH][IW]; output [N][OH][OW][OC] NHWC.
 struct IgGeom {
@@ -59,6 +64,7 @@ struct IgA {
     // strided u8 (kAIm2colU8S): byte (ic, y, x) of frame n sits at n*fb + ic*sc + y*sy + x*sx (channel order and the `[::d, ::d]` of
     // models.py:148 are strides, not copies); word != 0: IC == 4 channel-last, every pixel one aligned 32-bit word; a slab of 16 patch
     // elements is adv_pix whole pixels + adv_ch channels
+    // same-padded modes: adv_pix = the padding (K-1)/2; mode 5: word != 0 = ReLU on load; mode 6: adv_ch = KH*KW*IC (the true K)
     int sc, sy, sx, fb, word, adv_pix, adv_ch;
 };
 
@@ -92,10 +98,41 @@ __device__ __forceinline__ void ig_k_u8s_offsets(const IgA &a, IgK &s) {
     s.o3 = step();
 }
 
+// same-padded uint8 (mode 6): elements k .. k+3 one by one — byte offsets (off, o1..o3) from the row's own pixel, tap rows / columns as
+// bytes of p / q, validity (k + i < KH*KW*IC) in bits 0..3 of ch, k itself above them.  Divisions: once per slab, this layer has two.
+__device__ __forceinline__ void ig_k_u8p(const IgA &a, IgK &s, int k) {
+    int o[4];
+    s.p = s.q = 0;
+    s.ch = k << 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int kk = k + i;
+        const bool ok = kk < a.adv_ch;
+        const int pix = ok ? kk / a.g.IC : 0, ic = ok ? kk - pix * a.g.IC : 0;
+        const int ky = ok ? pix / a.g.KW : a.adv_pix, kx = ok ? pix - ky * a.g.KW : a.adv_pix;
+        o[i] = ic * a.sc + (ky - a.adv_pix) * a.sy + (kx - a.adv_pix) * a.sx;
+        s.p |= ky << (8 * i);
+        s.q |= kx << (8 * i);
+        s.ch |= (ok ? 1 : 0) << i;
+    }
+    s.off = o[0];
+    s.o1 = o[1];
+    s.o2 = o[2];
+    s.o3 = o[3];
+}
+
 template <int MODE>
 __device__ __forceinline__ IgK ig_k_init(const IgA &a, int k) {
     IgK s;
-    if (MODE == kADense) {
+    if (MODE == kAIm2colPad) {          // k = (ky*KW + kx)*IC + ic; the row base is the output pixel's own input pixel
+        const int pix = k / a.g.IC;
+        s.ch = k - pix * a.g.IC;
+        s.p = pix / a.g.KW;
+        s.q = pix - s.p * a.g.KW;
+        s.off = ((s.p - a.adv_pix) * a.g.IW + (s.q - a.adv_pix)) * a.g.IC + s.ch;
+    } else if (MODE == kAIm2colU8P) {
+        ig_k_u8p(a, s, k);
+    } else if (MODE == kADense) {
         s.p = s.q = s.ch = 0;
         s.off = k;
     } else if (MODE == kAIm2colF32) {   // k = (ky*KW + kx)*IC + ic
@@ -128,7 +165,19 @@ __device__ __forceinline__ IgK ig_k_init(const IgA &a, int k) {
 
 template <int MODE>
 __device__ __forceinline__ void ig_k_advance(const IgA &a, IgK &s) {   // k += 16
-    if (MODE == kADense) {
+    if (MODE == kAIm2colPad) {
+        s.ch += kIgBK;
+        while (s.ch >= a.g.IC) {
+            s.ch -= a.g.IC;
+            if (++s.q == a.g.KW) {
+                s.q = 0;
+                ++s.p;
+            }
+        }
+        s.off = ((s.p - a.adv_pix) * a.g.IW + (s.q - a.adv_pix)) * a.g.IC + s.ch;
+    } else if (MODE == kAIm2colU8P) {
+        ig_k_u8p(a, s, (s.ch >> 4) + kIgBK);
+    } else if (MODE == kADense) {
         s.off += kIgBK;
     } else if (MODE == kAIm2colF32) {
         s.ch += kIgBK;
@@ -186,7 +235,13 @@ template <int MODE>
 __device__ __forceinline__ IgRow ig_row(const IgA &a, int m) {
     IgRow r;
     r.y = r.x = 0;
-    if (MODE == kADense) {
+    if (MODE == kAIm2colPad || MODE == kAIm2colU8P) {   // OH == IH, OW == IW: the output pixel names the centre of its patch
+        const int hw = a.g.IH * a.g.IW;
+        const int n = m / hw, rem = m - n * hw;
+        r.y = rem / a.g.IW;
+        r.x = rem - r.y * a.g.IW;
+        r.base = MODE == kAIm2colPad ? m * a.g.IC : n * a.fb + r.y * a.sy + r.x * a.sx;
+    } else if (MODE == kADense) {
         r.base = m * a.lda;
     } else if (MODE == kAIm2colF32 || MODE == kAIm2colU8) {
         const int ohw = a.g.OH * a.g.OW;
@@ -229,6 +284,25 @@ __device__ __forceinline__ bool ig_dbg_bad(int operand, long long idx, long long
 
 template <int MODE>
 __device__ __forceinline__ float4 ig_load4(const IgA &a, const IgRow &r, const IgK &k) {
+    if (MODE == kAIm2colPad) {   // the whole quad is one tap: zeros when it lies in the padding
+        if ((unsigned)(r.y + k.p - a.adv_pix) >= (unsigned)a.g.IH || (unsigned)(r.x + k.q - a.adv_pix) >= (unsigned)a.g.IW)
+            return make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 v = *reinterpret_cast<const float4 *>((const float *)a.ptr + (r.base + k.off));
+        if (a.word) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+        return v;
+    }
+    if (MODE == kAIm2colU8P) {   // every element its own tap; `/ 255.0` rides in the other operand as in modes 2 and 4
+        const uint8_t *p = (const uint8_t *)a.ptr + r.base;
+        const int off[4] = {k.off, k.o1, k.o2, k.o3};
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int y = r.y + ((k.p >> (8 * i)) & 0xFF) - a.adv_pix, x = r.x + ((k.q >> (8 * i)) & 0xFF) - a.adv_pix;
+            const bool ok = ((k.ch >> i) & 1) && (unsigned)y < (unsigned)a.g.IH && (unsigned)x < (unsigned)a.g.IW;
+            v[i] = ok ? (float)p[off[i]] : 0.f;
+        }
+        return make_float4(v[0], v[1], v[2], v[3]);
+    }
     if (MODE == kAIm2colU8) {   // four bytes = one aligned word, as floats 0..255; the `/ 255.0` of models.py:150 rides in the other operand
         const uint32_t w = *reinterpret_cast<const uint32_t *>((const uint8_t *)a.ptr + (r.base + k.off));   // (packed weights / dW scale)
         return make_float4((float)(w & 0xFFu), (float)((w >> 8) & 0xFFu), (float)((w >> 16) & 0xFFu), (float)(w >> 24));
@@ -253,7 +327,8 @@ __device__ __forceinline__ float4 ig_load4(const IgA &a, const IgRow &r, const I
 template <int MODE, int MI, int NI>
 __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_kernel(IgA A, int M, int K, const float *__restrict__ B, int ldb, int N,
                                                                   float *__restrict__ Cout, int ldc, int epi, const float *__restrict__ bias,
-                                                                  const float *__restrict__ mask, int ldmask) {
+                                                                  const float *__restrict__ mask, int ldmask, const float *__restrict__ addend,
+                                                                  int ldadd) {
     constexpr int TM = 64 * MI, TN = 16 * NI;
     constexpr int kStage = (TM + TN) * kIgLS;
     __shared__ __attribute__((aligned(16))) float lds[2 * kStage];
@@ -367,6 +442,11 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_rows_kernel(IgA A, int M,
                 if (epi == kEpiBias || epi == kEpiBiasRelu) v += bias[n];
                 if (epi == kEpiBiasRelu) v = fmaxf(v, 0.0f);
                 if (epi == kEpiMask) v = mask[orow * ldmask + n] > 0.0f ? v : 0.0f;   // relu' of the layer input, read where it was produced
+                if constexpr (MODE == kAIm2colPad || MODE == kAIm2colU8P) {   // the residual sums (compiled into the same-padded modes only)
+                    if (epi == kEpiBiasAdd || epi == kEpiBiasAddRelu) v = (v + bias[n]) + addend[orow * ldadd + n];   // conv1(..) + inputs
+                    if (epi == kEpiBiasAddRelu) v = fmaxf(v, 0.0f);
+                    if (epi == kEpiMaskAdd) v = (mask[orow * ldmask + n] > 0.0f ? v : 0.0f) + addend[orow * ldadd + n];   // dX + skip gradient
+                }
                 if (IG_DBG_BAD(2, (long long)(orow * ldc + n), 1, m)) continue;
                 Cout[orow * ldc + n] = v;
             }
@@ -552,8 +632,8 @@ struct IgM {   // (n, oy, ox) of a row of an im2col operand, advanced by 16 rows
 };
 template <int MODE>
 __device__ __forceinline__ int ig_m_base(const IgA &a, const IgM &r) {
-    if (MODE == kAIm2colU8S) return r.n * a.fb + r.oy * a.g.S * a.sy + r.ox * a.g.S * a.sx;
-    return MODE == kAIm2colF32 ? ((r.n * a.g.IH + r.oy * a.g.S) * a.g.IW + r.ox * a.g.S) * a.g.IC
+    if (MODE == kAIm2colU8S || MODE == kAIm2colU8P) return r.n * a.fb + r.oy * a.g.S * a.sy + r.ox * a.g.S * a.sx;
+    return MODE == kAIm2colF32 || MODE == kAIm2colPad ? ((r.n * a.g.IH + r.oy * a.g.S) * a.g.IW + r.ox * a.g.S) * a.g.IC
                                  : (r.n * a.g.IC * a.g.IH + r.oy * a.g.S) * a.g.IW + r.ox * a.g.S;
 }
 
@@ -608,6 +688,10 @@ __global__ void __launch_bounds__(kIgThreads, 2) igemm_weights_kernel(IgA A, int
         IgRow r;
         r.y = r.x = 0;
         r.base = MODE == kADense ? rm.n * A.lda : ig_m_base<MODE>(A, rm);
+        if (MODE == kAIm2colPad || MODE == kAIm2colU8P) {   // the padding test of ig_load4 needs the output pixel
+            r.y = rm.oy;
+            r.x = rm.ox;
+        }
         const bool row_ok = mrow + ar < m_hi;
 #pragma unroll
         for (int j = 0; j < KJ; ++j) fa[j] = (row_ok && k_ok[j]) ? ig_load4<MODE>(A, r, kc[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -792,11 +876,121 @@ __global__ void __launch_bounds__(256) ig_transpose_kernel(const float *__restri
     out[(size_t)k * N + n] = w[i];
 }
 
+// Stride-1 same-padded conv [OC][IC][KH][KW] -> forward B [OC][ldf] (k = (ky*KW + kx)*IC + ic; columns KH*KW*IC .. ldf-1 are the caller's
+// zeros; u8: weights / 255) and dX B [IC][(ky'*KW + kx')*OC + oc] = w[oc][ic][KH-1-ky'][KW-1-kx']: dX of such a layer is the same mode-5
+// product on dOut with the kernel flipped and the channel roles swapped.
+__global__ void __launch_bounds__(256) ig_pack_conv_same_kernel(const float *__restrict__ w, IgGeom g, int u8, float *__restrict__ fwd, int ldf,
+                                                               float *__restrict__ dx) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long total = (long long)g.OC * g.IC * g.KH * g.KW;
+    if (i >= total) return;
+    const int kx = (int)(i % g.KW);
+    long long t = i / g.KW;
+    const int ky = (int)(t % g.KH);
+    t /= g.KH;
+    const int ic = (int)(t % g.IC), oc = (int)(t / g.IC);
+    const float v = w[i];
+    if (fwd) fwd[(long long)oc * ldf + ((long long)ky * g.KW + kx) * g.IC + ic] = u8 ? v / 255.0f : v;
+    if (dx) dx[(long long)ic * g.KH * g.KW * g.OC + ((long long)(g.KH - 1 - ky) * g.KW + (g.KW - 1 - kx)) * g.OC + oc] = v;
+}
+
+// max_pool2d(kernel 3, stride 2, padding 1) on NHWC f32 [n][H][W][C] -> [n][PH][PW][C], PH = (H+1)/2, PW = (W+1)/2; one thread per
+// output pixel and channel quad, the maximum over the in-image taps only (the padding never wins: a window always holds its centre).
+__global__ void __launch_bounds__(256) ig_maxpool_fwd_kernel(const float *__restrict__ in, long long total, int H, int W, int C4, float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int PH = (H + 1) / 2, PW = (W + 1) / 2;
+    const int c = (int)(i % C4);
+    long long t = i / C4;
+    const int px = (int)(t % PW);
+    t /= PW;
+    const int py = (int)(t % PH);
+    const long long n = t / PH;
+    const float4 *src = reinterpret_cast<const float4 *>(in) + n * H * W * C4 + c;
+    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int y = 2 * py + dy;
+        if ((unsigned)y >= (unsigned)H) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int x = 2 * px + dx;
+            if ((unsigned)x >= (unsigned)W) continue;
+            const float4 v = src[((long long)y * W + x) * C4];
+            m = make_float4(fmaxf(m.x, v.x), fmaxf(m.y, v.y), fmaxf(m.z, v.z), fmaxf(m.w, v.w));
+        }
+    }
+    reinterpret_cast<float4 *>(out)[i] = m;
+}
+
+// Its backward in gather form (no atomics, deterministic): an input pixel sums the dOut of the at most four windows (two per axis: a
+// stride-2 window of 3 overlaps its neighbour in one row / column) whose maximum it is.  The pooled values are conv + bias with no
+// ReLU in between, so exact ties have measure zero on real-valued maps; constant frame regions still produce them, and then the
+// gradient goes where torch sends it: to the first tap in row-major order that holds the maximum.
+__global__ void __launch_bounds__(256) ig_maxpool_bwd_kernel(const float *__restrict__ in, const float *__restrict__ out, const float *__restrict__ dout,
+                                                            long long total, int H, int W, int C4, float *__restrict__ din) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int PH = (H + 1) / 2, PW = (W + 1) / 2;
+    const int c = (int)(i % C4);
+    long long t = i / C4;
+    const int x = (int)(t % W);
+    t /= W;
+    const int y = (int)(t % H);
+    const long long n = t / H;
+    const float4 *src = reinterpret_cast<const float4 *>(in) + n * H * W * C4 + c;
+    const float4 mine4 = src[((long long)y * W + x) * C4];
+    const float mine[4] = {mine4.x, mine4.y, mine4.z, mine4.w};
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int py = y / 2; py <= (y + 1) / 2 && py < PH; ++py)
+        for (int px = x / 2; px <= (x + 1) / 2 && px < PW; ++px) {
+            const long long o = ((n * PH + py) * PW + px) * C4 + c;
+            const float4 m4 = reinterpret_cast<const float4 *>(out)[o], d4 = reinterpret_cast<const float4 *>(dout)[o];
+            const float m[4] = {m4.x, m4.y, m4.z, m4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
+            bool win[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) win[q] = mine[q] == m[q];
+            if (!(win[0] || win[1] || win[2] || win[3])) continue;
+            for (int ty = 2 * py - 1; ty <= y; ++ty) {          // an earlier tap with the same value takes the gradient (torch: first index)
+                if (ty < 0) continue;
+                for (int tx = 2 * px - 1; tx <= 2 * px + 1; ++tx) {
+                    if (tx < 0 || tx >= W || (ty == y && tx >= x)) continue;
+                    const float4 e4 = src[((long long)ty * W + tx) * C4];
+                    const float e[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) win[q] = win[q] && e[q] != m[q];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) g[q] += win[q] ? d[q] : 0.f;
+        }
+    reinterpret_cast<float4 *>(din)[i] = make_float4(g[0], g[1], g[2], g[3]);
+}
+
 static int ig_check_a(const pfa_igemm_operand *a, int64_t M, int K) {
     PFA_REQUIRE(a && a->ptr, "igemm: null A operand");
-    PFA_REQUIRE(a->mode >= 0 && a->mode <= 4, "igemm: bad A mode %d", a->mode);
-    PFA_REQUIRE(K >= 4 && K % 4 == 0, "igemm: K must be a multiple of 4 (got %d)", K);
+    PFA_REQUIRE(a->mode >= 0 && a->mode <= 6, "igemm: bad A mode %d", a->mode);
+    PFA_REQUIRE(a->mode == kAIm2colU8P || (K >= 4 && K % 4 == 0), "igemm: K must be a multiple of 4 (got %d)", K);
     PFA_REQUIRE(((uintptr_t)a->ptr & 15) == 0, "igemm: the A operand must be 16-byte aligned");
+    PFA_REQUIRE((a->reserved & ~1) == 0 && (a->reserved == 0 || a->mode == kAIm2colPad), "igemm: reserved bit 0 (ReLU on load) belongs to mode 5");
+    if (a->mode == kAIm2colPad || a->mode == kAIm2colU8P) {   // stride 1, odd square kernel, padding (K-1)/2: the output is the input's size
+        PFA_REQUIRE(a->S == 1 && a->KH == a->KW && a->KH >= 1 && a->KH % 2 == 1 && a->KH < 128 && a->OH == a->IH && a->OW == a->IW && a->IH >= 1 &&
+                        a->IW >= 1 && a->IC >= 1 && a->OC >= 1,
+                    "igemm: the same-padded modes take stride 1, an odd square kernel and OH == IH, OW == IW");
+        const int64_t frames = M / ((int64_t)a->IH * a->IW) + 1;
+        PFA_REQUIRE(frames * a->IC * a->IH * a->IW < (1ll << 31) && frames * a->OC * a->IH * a->IW < (1ll << 31),
+                    "igemm: operand too large for 32-bit element offsets (split the rows)");
+        const int kt = a->KH * a->KW * a->IC;
+        if (a->mode == kAIm2colPad) {
+            PFA_REQUIRE(a->IC % 4 == 0 && K == kt, "igemm: same-padded im2col f32 needs IC %% 4 == 0 and K == KH*KW*IC");
+        } else {
+            PFA_REQUIRE(a->IC <= 4 && (K == kt || (K % kIgBK == 0 && K >= kt && K < kt + kIgBK)),
+                        "igemm: same-padded u8 needs IC <= 4 and K == KH*KW*IC (weight form) or that rounded up to 16 (rows form)");
+            PFA_REQUIRE(a->sc >= 1 && a->sy >= 1 && a->sx >= 1 && a->frame_bytes >= 1 &&
+                            (int64_t)(a->IC - 1) * a->sc + (int64_t)(a->IH - 1) * a->sy + (int64_t)(a->IW - 1) * a->sx < a->frame_bytes,
+                        "igemm: same-padded u8: the last byte (IC-1)*sc + (IH-1)*sy + (IW-1)*sx must lie inside a frame of frame_bytes");
+            PFA_REQUIRE(frames * a->frame_bytes < (1ll << 31), "igemm: operand too large for 32-bit element offsets (split the rows)");
+        }
+        return 0;
+    }
     if (a->mode == kADense) {
         PFA_REQUIRE(a->lda % 4 == 0 && a->lda >= K, "igemm: dense lda must be a multiple of 4 and >= K");
         PFA_REQUIRE(M * a->lda < (1ll << 31), "igemm: operand too large for 32-bit element offsets (split the rows)");
@@ -848,6 +1042,17 @@ static IgA ig_make_a(const pfa_igemm_operand *a) {
         r.adv_pix = kIgBK / a->IC;
         r.adv_ch = kIgBK % a->IC;
     }
+    if (a->mode == kAIm2colPad || a->mode == kAIm2colU8P) {
+        r.adv_pix = a->KH / 2;
+        r.word = a->reserved & 1;
+        r.adv_ch = a->KH * a->KW * a->IC;
+        if (a->mode == kAIm2colU8P) {
+            r.sc = a->sc;
+            r.sy = a->sy;
+            r.sx = a->sx;
+            r.fb = a->frame_bytes;
+        }
+    }
     return r;
 }
 
@@ -895,12 +1100,31 @@ static size_t ig_partial_bytes(const IgWeightPlan &p, int K, int N) { return ali
 
 using namespace pfa;
 
+static int ig_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc, int32_t epilogue,
+                   const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd, pfa_stream_t stream);
+
 extern "C" int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
                               int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, pfa_stream_t stream) {
+    PFA_REQUIRE(epilogue >= 0 && epilogue <= 3, "igemm.rows: bad epilogue");
+    return ig_rows(a, M, K, B, ldb, N, C, ldc, epilogue, bias, mask, ldmask, nullptr, 0, stream);
+}
+
+extern "C" int pfa_igemm_rows_add(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
+                                  int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd,
+                                  pfa_stream_t stream) {
+    PFA_REQUIRE(a && (a->mode == kAIm2colPad || a->mode == kAIm2colU8P), "igemm.rows_add: the residual epilogues belong to the same-padded modes 5 and 6");
+    PFA_REQUIRE(epilogue >= 0 && epilogue <= 6, "igemm.rows_add: bad epilogue");
+    PFA_REQUIRE(epilogue < kEpiBiasAdd || (addend && ldadd >= N && addend != C), "igemm.rows_add: epilogues 4..6 need an addend [M][ldadd >= N] that is not the output");
+    PFA_REQUIRE((epilogue != kEpiBiasAdd && epilogue != kEpiBiasAddRelu) || bias, "igemm.rows_add: bias epilogue without a bias vector");
+    PFA_REQUIRE(epilogue != kEpiMaskAdd || (mask && ldmask >= N), "igemm.rows_add: mask epilogue without a mask");
+    return ig_rows(a, M, K, B, ldb, N, C, ldc, epilogue, bias, mask, ldmask, addend, ldadd, stream);
+}
+
+static int ig_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc, int32_t epilogue,
+                   const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd, pfa_stream_t stream) {
     if (int rc = ig_check_a(a, M, K)) return rc;
     PFA_REQUIRE(M >= 0 && M < (1ll << 31) && B && C && N >= 16 && N % 16 == 0 && ldc >= N, "igemm.rows: bad shapes (N must be a multiple of 16)");
     PFA_REQUIRE(((uintptr_t)B & 15) == 0 && ldb % 4 == 0, "igemm.rows: B must be 16-byte aligned with ldb a multiple of 4");
-    PFA_REQUIRE(epilogue >= 0 && epilogue <= 3, "igemm.rows: bad epilogue");
     PFA_REQUIRE((epilogue != kEpiBias && epilogue != kEpiBiasRelu) || bias, "igemm.rows: bias epilogue without a bias vector");
     PFA_REQUIRE(epilogue != kEpiMask || (mask && ldmask >= N), "igemm.rows: mask epilogue without a mask");
     if (M == 0) return 0;
@@ -918,9 +1142,11 @@ extern "C" int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, 
 #define PFA_IG_ROWS(MODE, MI, NI)                                                                                                          \
     hipLaunchKernelGGL((igemm_rows_kernel<MODE, MI, NI>), dim3((unsigned)(((Mp + 64 * MI - 1) / (64 * MI) + 7) / 8 * 8), N / (16 * NI), phases), \
                        dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue, \
-                       bias, mask, (int)ldmask)
+                       bias, mask, (int)ldmask, addend, (int)ldadd)
 #define PFA_IG_ROWS_MODE(MI, NI)                   \
     switch (A.mode) {                              \
+        case kAIm2colPad: PFA_IG_ROWS(kAIm2colPad, MI, NI); break;   \
+        case kAIm2colU8P: PFA_IG_ROWS(kAIm2colU8P, MI, NI); break;   \
         case kADense: PFA_IG_ROWS(kADense, MI, NI); break;           \
         case kAIm2colF32: PFA_IG_ROWS(kAIm2colF32, MI, NI); break;   \
         case kAIm2colU8: PFA_IG_ROWS(kAIm2colU8, MI, NI); break;     \
@@ -930,7 +1156,7 @@ extern "C" int pfa_igemm_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, 
     // A dense product over few rows (one rollout step of the width-general policies: 4096 rows) fills the chip only with 64-row tiles.
     const int tn = N % 64 == 0 ? 64 : N % 32 == 0 ? 32 : 16;
     const bool few = A.mode == kADense && ((Mp + (tn == 16 ? 255 : 127)) / (tn == 16 ? 256 : 128)) * (N / tn) < 256;
-    if (g_ig_products == 1 && !few && tn >= 32 && Kp % kIgSplitBK == 0) {   // opt-in: the six-term bf16 form of the same products
+    if (g_ig_products == 1 && !few && tn >= 32 && Kp % kIgSplitBK == 0 && A.mode <= kAIm2colU8S) {   // opt-in: the six-term bf16 form of the same products (modes 5, 6: always the fp32 kernel)
 #define PFA_IG_SPLIT(MODE, NI)                                                                                                             \
     hipLaunchKernelGGL((igemm_rows_split_kernel<MODE, 2, NI>), dim3((unsigned)(((Mp + 127) / 128 + 7) / 8 * 8), N / (16 * NI), phases),    \
                        dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue,   \
@@ -1018,6 +1244,8 @@ extern "C" int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t 
         case kADense: PFA_IG_WEIGHTS_KJ(kADense, NI) break;            \
         case kAIm2colF32: PFA_IG_WEIGHTS_KJ(kAIm2colF32, NI) break;    \
         case kAIm2colU8S: PFA_IG_WEIGHTS_KJ(kAIm2colU8S, NI) break;    \
+        case kAIm2colPad: PFA_IG_WEIGHTS_KJ(kAIm2colPad, NI) break;    \
+        case kAIm2colU8P: PFA_IG_WEIGHTS_KJ(kAIm2colU8P, NI) break;    \
         default: PFA_IG_WEIGHTS_KJ(kAIm2colU8, NI) break;              \
     }
         if (p.tn == 64) {
@@ -1075,6 +1303,43 @@ extern "C" int pfa_cnn_pack_fc(const float *w, int32_t N, int32_t channels, int3
     const long long total = (long long)N * channels * hw;
     hipLaunchKernelGGL(ig_pack_fc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (int)N, (int)channels, (int)hw,
                        perm_out, t_out);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pfa_cnn_pack_conv_same(const float *w, const pfa_igemm_operand *geom, int32_t u8, float *fwd, int32_t ldf, float *dx, pfa_stream_t stream) {
+    PFA_REQUIRE(w && geom && (fwd || dx), "cnn.pack_conv_same: null buffer");
+    const IgGeom g{geom->IC, geom->IH, geom->IW, geom->OC, geom->OH, geom->OW, geom->KH, geom->KW, geom->S};
+    PFA_REQUIRE(g.S == 1 && g.KH == g.KW && g.KH % 2 == 1 && g.IC >= 1 && g.OC >= 1, "cnn.pack_conv_same: stride 1 and an odd square kernel");
+    PFA_REQUIRE(!fwd || ldf >= g.KH * g.KW * g.IC, "cnn.pack_conv_same: ldf must hold KH*KW*IC columns");
+    const long long total = (long long)g.OC * g.IC * g.KH * g.KW;
+    hipLaunchKernelGGL(ig_pack_conv_same_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, g, (int)u8, fwd, (int)ldf, dx);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pfa_maxpool3s2_forward(const float *in, int64_t frames, int32_t H, int32_t W, int32_t channels, float *out, pfa_stream_t stream) {
+    PFA_REQUIRE(in && out && frames >= 0 && H >= 1 && W >= 1 && channels >= 4 && channels % 4 == 0, "maxpool3s2.forward: bad arguments (channels a multiple of 4)");
+    PFA_REQUIRE((((uintptr_t)in | (uintptr_t)out) & 15) == 0, "maxpool3s2.forward: buffers must be 16-byte aligned");
+    const long long total = (long long)frames * ((H + 1) / 2) * ((W + 1) / 2) * (channels / 4);
+    if (total == 0) return 0;
+    PFA_REQUIRE((total + 255) / 256 < (1ll << 31), "maxpool3s2.forward: too many elements for one launch");
+    hipLaunchKernelGGL(ig_maxpool_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, total, (int)H, (int)W,
+                       (int)(channels / 4), out);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pfa_maxpool3s2_backward(const float *in, const float *out, const float *dout, int64_t frames, int32_t H, int32_t W, int32_t channels,
+                                       float *din, pfa_stream_t stream) {
+    PFA_REQUIRE(in && out && dout && din && frames >= 0 && H >= 1 && W >= 1 && channels >= 4 && channels % 4 == 0,
+                "maxpool3s2.backward: bad arguments (channels a multiple of 4)");
+    PFA_REQUIRE((((uintptr_t)in | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)din) & 15) == 0, "maxpool3s2.backward: buffers must be 16-byte aligned");
+    const long long total = (long long)frames * H * W * (channels / 4);
+    if (total == 0) return 0;
+    PFA_REQUIRE((total + 255) / 256 < (1ll << 31), "maxpool3s2.backward: too many elements for one launch");
+    hipLaunchKernelGGL(ig_maxpool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, dout, total, (int)H, (int)W,
+                       (int)(channels / 4), din);
     PFA_LAUNCH_CHECK();
     return 0;
 }

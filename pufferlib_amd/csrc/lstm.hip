@@ -57,6 +57,9 @@ __global__ void __launch_bounds__(256) store_step_kernel(pfa_experience ex, int 
 // reference appends rows as they arrive and later sorts them by (env_id, step); here row i of the batch goes straight to
 // its sorted position env_id*T + (rows this env has contributed so far).  16 rows per workgroup; rows with mask == 0
 // are skipped, rows of an env that already holds T rows are dropped and counted.  env_ids must be unique within a call.
+// BYTES (pfa_store_rows_bytes): the rows are uint8 frames of `dp` BYTES each, any size, copied byte by byte; the float4 form is the
+// instantiation every other caller gets, with the code it always had.
+template <bool BYTES>
 __global__ void __launch_bounds__(256) store_rows_kernel(pfa_experience ex, int rows, int num_slots, int dp, const float *obs,
                                                         const float *rewards, const uint8_t *dones, const long long *actions,
                                                         const float *logprob, const float *value, const int *env_ids,
@@ -82,13 +85,24 @@ __global__ void __launch_bounds__(256) store_rows_kernel(pfa_experience ex, int 
         s_slot[threadIdx.x] = slot;
     }
     __syncthreads();
-    const int V = dp / 4;
-    for (int idx = threadIdx.x; idx < 16 * V; idx += 256) {
-        const int rl = idx / V, c4 = idx - rl * V;
-        const int t = s_t[rl];
-        if (t < 0) continue;
-        *reinterpret_cast<float4 *>(ex.obs + ((size_t)s_slot[rl] * ex.horizon_T + t) * dp + 4 * c4) =
-            *reinterpret_cast<const float4 *>(obs + (size_t)(r0 + rl) * dp + 4 * c4);
+    if constexpr (BYTES) {
+        uint8_t *dst = reinterpret_cast<uint8_t *>(ex.obs);
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(obs);
+        for (int idx = threadIdx.x; idx < 16 * dp; idx += 256) {
+            const int rl = idx / dp, b = idx - rl * dp;
+            const int t = s_t[rl];
+            if (t < 0) continue;
+            dst[((size_t)s_slot[rl] * ex.horizon_T + t) * dp + b] = src[(size_t)(r0 + rl) * dp + b];
+        }
+    } else {
+        const int V = dp / 4;
+        for (int idx = threadIdx.x; idx < 16 * V; idx += 256) {
+            const int rl = idx / V, c4 = idx - rl * V;
+            const int t = s_t[rl];
+            if (t < 0) continue;
+            *reinterpret_cast<float4 *>(ex.obs + ((size_t)s_slot[rl] * ex.horizon_T + t) * dp + 4 * c4) =
+                *reinterpret_cast<const float4 *>(obs + (size_t)(r0 + rl) * dp + 4 * c4);
+        }
     }
     if (threadIdx.x < 16 && s_t[threadIdx.x] >= 0) {
         const int i = r0 + threadIdx.x, slot = s_slot[threadIdx.x], t = s_t[threadIdx.x];
@@ -385,8 +399,21 @@ extern "C" int pfa_store_rows(const pfa_experience *exp, int32_t rows, int32_t n
     PFA_REQUIRE(exp && obs && rewards && dones && actions && logprob && value && counters && stored_dropped, "store_rows: null buffer");
     PFA_REQUIRE(rows >= 0 && num_slots >= 1 && obs_stride >= 4 && obs_stride % 4 == 0 && exp->horizon_T >= 1, "store_rows: bad arguments");
     if (rows == 0) return 0;
-    hipLaunchKernelGGL(store_rows_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, *exp, (int)rows,
+    hipLaunchKernelGGL(store_rows_kernel<false>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, *exp, (int)rows,
                        (int)num_slots, (int)obs_stride, obs, rewards, dones, (const long long *)actions, logprob, value, env_ids, mask,
+                       counters, stored_dropped);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pfa_store_rows_bytes(const pfa_experience *exp, int32_t rows, int32_t num_slots, int32_t row_bytes, const uint8_t *obs, const float *rewards,
+                                    const uint8_t *dones, const int64_t *actions, const float *logprob, const float *value, const int32_t *env_ids,
+                                    const uint8_t *mask, int32_t *counters, int32_t *stored_dropped, pfa_stream_t stream) {
+    PFA_REQUIRE(exp && obs && rewards && dones && actions && logprob && value && counters && stored_dropped, "store_rows_bytes: null buffer");
+    PFA_REQUIRE(rows >= 0 && num_slots >= 1 && row_bytes >= 1 && exp->horizon_T >= 1, "store_rows_bytes: bad arguments");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(store_rows_kernel<true>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, *exp, (int)rows, (int)num_slots,
+                       (int)row_bytes, reinterpret_cast<const float *>(obs), rewards, dones, (const long long *)actions, logprob, value, env_ids, mask,
                        counters, stored_dropped);
     PFA_LAUNCH_CHECK();
     return 0;

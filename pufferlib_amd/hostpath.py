@@ -208,9 +208,13 @@ def evaluate(data):
                 vecenv.send(actions_np)
             continue
         with profile.eval_misc:
-            # (frame rows are bytes: the copy moves them as obs_dim / 4 four-byte words)
-            _lib.check(L.pfa_store_rows(C.byref(experience.c), n, bridge.total_agents,
-                                        fp.obs_dim // 4 if (data.cnn_engine is not None or (data.gen_engine is not None and data.gen_engine.net.kind == 'cnn')) else fp.obs_stride, _lib.ptr(bridge.obs),
+            # (frame rows are bytes: pfa_store_rows moves them as obs_dim / 16 float4s with a stride of obs_dim / 4 floats, which wants
+            # whole 16-byte units; every other frame size is copied byte by byte)
+            frame_rows = data.cnn_engine is not None or (data.gen_engine is not None and data.gen_engine.net.kind == 'cnn')
+            odd_bytes = frame_rows and fp.obs_dim % 16 != 0
+            store = L.pfa_store_rows_bytes if odd_bytes else L.pfa_store_rows
+            _lib.check(store(C.byref(experience.c), n, bridge.total_agents,
+                             fp.obs_dim if odd_bytes else fp.obs_dim // 4 if frame_rows else fp.obs_stride, _lib.ptr(bridge.obs),
                                         _lib.ptr(bridge.rew), _lib.ptr(bridge.done), _lib.ptr(actions), _lib.ptr(logprob),
                                         _lib.ptr(value), _lib.ptr(bridge.ids), _lib.ptr(bridge.mask), _lib.ptr(bridge.counters),
                                         _lib.ptr(bridge.stored_dropped), stream), 'store_rows')

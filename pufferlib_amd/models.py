@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .conv_geometry import ConvGeometry, default_obs_shape
+from .conv_geometry import ConvGeometry, ResnetGeometry, default_obs_shape
 
 HIDDEN = 128
 
@@ -112,6 +112,155 @@ class Convolutional(nn.Module):
     def forward(self, observations):
         raise RuntimeError('pufferlib_amd.models.Convolutional is a parameter container: call it through '
                            'pufferlib_amd.cleanrl.Policy / pufferlib_amd.clean_pufferl (HIP kernels)')
+
+
+class _ResidualBlock(nn.Module):
+    """Two 3 x 3 padding-1 convolutions around a skip connection: x + conv1(relu(conv0(relu(x)))) (models.py:198-210)."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.conv0 = nn.Conv2d(channels, channels, 3, padding=1)
+        self.conv1 = nn.Conv2d(channels, channels, 3, padding=1)
+
+
+class _ConvSequence(nn.Module):
+    """Conv2d(3 x 3, padding 1) -> max_pool2d(3, stride 2, padding 1) -> two residual blocks (models.py:212-231)."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv = nn.Conv2d(in_channels, out_channels, 3, padding=1)
+        self.res_block0 = _ResidualBlock(out_channels)
+        self.res_block1 = _ResidualBlock(out_channels)
+
+
+class ProcgenResnet(nn.Module):
+    """pufferlib.models.ProcgenResnet (models.py:159-196), the IMPALA ResNet environments/procgen/torch.py exports as Policy: the same
+    signature, submodule names (``network.{0,1,2}.conv``, ``.res_block{0,1}.conv{0,1}``, ``network.5``, ``actor``, ``value``) and
+    initialisation calls in the same order (torch's defaults for the convolutions and the big Linear, layer_init 0.01 / 1 for the
+    heads), so state_dicts load in either direction.  Frames are uint8 (H, W, C).  Parameter container: the arithmetic runs in
+    csrc/igemm.hip (modes 5 / 6, max-pool) / csrc/cnn_heads.hip through pufferlib_amd.resnet.Engine."""
+
+    def __init__(self, env, cnn_width=16, mlp_width=256):
+        super().__init__()
+        space = env.single_observation_space
+        shape = tuple(int(x) for x in space.shape)
+        check_resnet_limits(shape, getattr(space, 'dtype', None), cnn_width, mlp_width, int(env.single_action_space.n))
+        geom = ResnetGeometry(shape, cnn_width)
+        self.obs_shape = shape
+        self.cnn_width, self.mlp_width = int(cnn_width), int(mlp_width)
+        seqs = [_ConvSequence(ic, oc) for ic, _, _, oc, _, _ in geom.seqs]
+        self.network = nn.Sequential(*seqs, nn.Flatten(), nn.ReLU(), nn.Linear(geom.flat_size, mlp_width), nn.ReLU())
+        self.actor = layer_init(nn.Linear(mlp_width, env.single_action_space.n), std=0.01)
+        self.value = layer_init(nn.Linear(mlp_width, 1), std=1)
+
+    def forward(self, observations):
+        raise RuntimeError('pufferlib_amd.models.ProcgenResnet is a parameter container: call it through '
+                           'pufferlib_amd.cleanrl.Policy / pufferlib_amd.clean_pufferl (HIP kernels)')
+
+
+def check_resnet_limits(obs_shape, dtype, cnn_width, mlp_width, num_actions):
+    """What the ResNet engine is built for; each limit named where it is exceeded."""
+    if len(obs_shape) != 3 or not 1 <= obs_shape[2] <= 4:
+        raise NotImplementedError(f'models.ProcgenResnet: channel-last frames (H, W, C) with 1..4 channels (got shape {obs_shape}); the first '
+                                  'layer loads up to four bytes per pixel')
+    if dtype is not None and np.dtype(dtype) != np.uint8:
+        raise NotImplementedError(f'models.ProcgenResnet: uint8 frames (got {np.dtype(dtype)})')
+    if cnn_width < 16 or cnn_width % 16 != 0:
+        raise ValueError(f'models.ProcgenResnet: cnn_width must be a multiple of 16 (got {cnn_width}): the conv kernels write 16-column tiles')
+    if mlp_width < 16 or mlp_width % 16 != 0 or mlp_width > 1024:
+        raise ValueError(f'models.ProcgenResnet: mlp_width must be a multiple of 16 up to 1024 (got {mlp_width}): the head kernels\' widths')
+    if num_actions > 15:
+        raise NotImplementedError(f'models.ProcgenResnet: {num_actions} actions; the 16-lane head kernels take up to 15')
+
+
+def find_resnet(module):
+    """The ProcgenResnet-shaped submodule of a policy wrapper (ours or the reference's): network (of ConvSequences) / actor / value."""
+    for m in module.modules():
+        if all(hasattr(m, n) for n in ('network', 'actor', 'value')) and isinstance(getattr(m, 'network'), nn.Sequential) \
+                and len(m.network) >= 1 and all(hasattr(m.network[0], n) for n in ('conv', 'res_block0', 'res_block1')):
+            return m
+    return None
+
+
+def set_resnet_obs_shape(policy_module, obs_shape):
+    """Record the env's frame shape on a ProcgenResnet-shaped module built elsewhere (the reference's keeps none)."""
+    net = find_resnet(policy_module)
+    if net is not None and obs_shape is not None and len(tuple(obs_shape)) == 3:
+        net.__dict__['_pfa_obs_shape'] = tuple(int(x) for x in obs_shape)
+
+
+class _ResnetViews(dict):
+    """name -> view; ``value_fn.*`` (what cnn.Engine's head code asks for) answers with the ``value.*`` entry without being one."""
+
+    def __missing__(self, key):
+        if key.startswith('value_fn.'):
+            return self['value.' + key[len('value_fn.'):]]
+        raise KeyError(key)
+
+
+class ResnetParams:
+    """One flat fp32 device buffer holding the ProcgenResnet parameters in named_parameters() order, every module parameter re-pointed
+    at its view.  The interface of ConvParams; the value head's views are also reachable as ``value_fn.*`` (the names cnn.Engine's
+    head code reads).  The frame shape is not in the weights: `obs_shape`, else what the module recorded (ours: its env's)."""
+    multidiscrete = False
+
+    def __init__(self, policy_module, device, obs_shape=None):
+        net = find_resnet(policy_module)
+        if net is None:
+            raise ValueError('policy has no network/actor/value (models.ProcgenResnet shape)')
+        self.net = net
+        seqs = [m for m in net.network if hasattr(m, 'res_block0')]
+        fc = [m for m in net.network if isinstance(m, nn.Linear)]
+        if len(seqs) != 3 or len(fc) != 1:
+            raise NotImplementedError('models.ProcgenResnet shape: three ConvSequences and one Linear in network')
+        convs = [c for s in seqs for c in (s.conv, s.res_block0.conv0, s.res_block0.conv1, s.res_block1.conv0, s.res_block1.conv1)]
+        for cv in convs:
+            if tuple(cv.kernel_size) != (3, 3) or tuple(cv.stride) != (1, 1) or tuple(cv.padding) != (1, 1):
+                raise NotImplementedError(f'conv layer {tuple(cv.weight.shape)} stride {cv.stride} padding {cv.padding}: only 3 x 3, stride 1, padding 1 is built')
+        widths = [int(s.conv.weight.shape[0]) for s in seqs]
+        if widths != [widths[0], 2 * widths[0], 2 * widths[0]]:
+            raise NotImplementedError(f'ConvSequence widths {widths}: (w, 2w, 2w) is built')
+        if obs_shape is None:
+            obs_shape = net.__dict__.get('_pfa_obs_shape') or getattr(net, 'obs_shape', None)
+        if obs_shape is None:
+            raise ValueError('models.ProcgenResnet: the frame shape is not in the weights; pass obs_shape or build through clean_pufferl.create')
+        self.hidden = int(fc[0].weight.shape[0])
+        self.num_actions = int(net.actor.weight.shape[0])
+        check_resnet_limits(tuple(obs_shape), None, widths[0], self.hidden, self.num_actions)
+        self.geometry = ResnetGeometry(obs_shape, widths[0])
+        if self.geometry.channels != int(seqs[0].conv.weight.shape[1]):
+            raise ValueError(f'frames of shape {self.geometry.obs_shape} have {self.geometry.channels} channels, the first conv layer reads '
+                             f'{int(seqs[0].conv.weight.shape[1])}')
+        if int(fc[0].weight.shape[1]) != self.geometry.flat_size or tuple(net.value.weight.shape) != (1, self.hidden) \
+                or tuple(net.actor.weight.shape[1:]) != (self.hidden,):
+            raise ValueError(f'Linear({int(fc[0].weight.shape[1])}, {self.hidden}) but the conv stack on frames of shape {self.geometry.obs_shape} '
+                             f'yields {self.geometry.out_shape} = {self.geometry.flat_size}')
+        self.framestack = self.geometry.channels
+        self.nvec = [self.num_actions]
+        self.names = [n for n, _ in net.named_parameters()]
+        self.count = int(sum(p.numel() for _, p in net.named_parameters()))
+        self.flat = torch.zeros(self.count, dtype=torch.float32, device=device)
+        self.views = self.split(self.flat)
+        with torch.no_grad():
+            for name, p in net.named_parameters():
+                v = self.views[name]
+                v.copy_(p.detach().to(device=device, dtype=torch.float32))
+                p.data = v
+        self.obs_dim = self.obs_stride = self.geometry.frame_bytes
+
+    def split(self, flat):
+        out, o = _ResnetViews(), 0
+        for name, p in self.net.named_parameters():
+            n = p.numel()
+            out[name] = flat[o:o + n].view(p.shape)
+            o += n
+        return out
+
+    def flat_like(self):
+        return torch.zeros_like(self.flat)
+
+    def unpack_actions(self, packed):
+        return packed
 
 
 def find_cnn(module):
