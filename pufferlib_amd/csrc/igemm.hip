@@ -29,12 +29,10 @@
 // for A and B alike), 2 lanes per bank.  weight form: (64 KJ) x (16 NI) tile of G per workgroup (KJ = 1..4: the height that pads K
 // least) and a chunk of rows; the partial sums
 // of the row splits are reduced in f64 in a fixed order (deterministic) and scattered into torch's parameter layout.
+#include <type_traits>
+
 #include "common.hpp"
 #include "mlp_tile.hpp"
-
-#ifndef PFA_IG_TILE64
-#define PFA_IG_TILE64 0
-#endif
 
 namespace pfa {
 
@@ -1100,6 +1098,21 @@ static size_t ig_partial_bytes(const IgWeightPlan &p, int K, int N) { return ali
 
 using namespace pfa;
 
+template <int V>
+using IgInt = std::integral_constant<int, V>;   // tile sizes as arguments of the generic launch lambdas
+// Turns the run-time operand mode into a template argument: f(integral_constant<IgAMode, M>) for the M of the list that `mode`
+// equals, the LAST one otherwise (ig_check_a has let only the enum's values through).  A generic callable is instantiated for every
+// mode it is offered, so each site lists exactly the modes its kernel is built for.
+template <IgAMode M, IgAMode... Rest, typename F>
+static void ig_with_mode(int mode, F &&f) {
+    if constexpr (sizeof...(Rest) == 0) {
+        f(std::integral_constant<IgAMode, M>{});
+    } else {
+        if (mode == M) f(std::integral_constant<IgAMode, M>{});
+        else ig_with_mode<Rest...>(mode, f);
+    }
+}
+
 static int ig_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc, int32_t epilogue,
                    const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd, pfa_stream_t stream);
 
@@ -1139,66 +1152,43 @@ static int ig_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float
     }
     PFA_REQUIRE(Kp % kIgBK == 0 && ldb >= Kp, "igemm.rows: the contraction length (per phase) must be a multiple of 16 and ldb >= it");
     ScopedKernelTimer timer("igemm_rows", (hipStream_t)stream);
-#define PFA_IG_ROWS(MODE, MI, NI)                                                                                                          \
-    hipLaunchKernelGGL((igemm_rows_kernel<MODE, MI, NI>), dim3((unsigned)(((Mp + 64 * MI - 1) / (64 * MI) + 7) / 8 * 8), N / (16 * NI), phases), \
-                       dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue, \
-                       bias, mask, (int)ldmask, addend, (int)ldadd)
-#define PFA_IG_ROWS_MODE(MI, NI)                   \
-    switch (A.mode) {                              \
-        case kAIm2colPad: PFA_IG_ROWS(kAIm2colPad, MI, NI); break;   \
-        case kAIm2colU8P: PFA_IG_ROWS(kAIm2colU8P, MI, NI); break;   \
-        case kADense: PFA_IG_ROWS(kADense, MI, NI); break;           \
-        case kAIm2colF32: PFA_IG_ROWS(kAIm2colF32, MI, NI); break;   \
-        case kAIm2colU8: PFA_IG_ROWS(kAIm2colU8, MI, NI); break;     \
-        case kAIm2colU8S: PFA_IG_ROWS(kAIm2colU8S, MI, NI); break;   \
-        default: PFA_IG_ROWS(kACol2im, MI, NI); break;               \
-    }
+    auto rows = [&](auto mode, auto mi, auto ni) {   // the fp32 kernel on (64 MI) x (16 NI) tiles
+        constexpr int MI = decltype(mi)::value, NI = decltype(ni)::value;
+        hipLaunchKernelGGL((igemm_rows_kernel<decltype(mode)::value, MI, NI>), dim3((unsigned)(((Mp + 64 * MI - 1) / (64 * MI) + 7) / 8 * 8), N / (16 * NI), phases),
+                           dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue,
+                           bias, mask, (int)ldmask, addend, (int)ldadd);
+    };
+    auto rows_any = [&](auto mi, auto ni) {   // ... for whatever operand mode A has
+        ig_with_mode<kAIm2colPad, kAIm2colU8P, kADense, kAIm2colF32, kAIm2colU8, kAIm2colU8S, kACol2im>(A.mode, [&](auto mode) { rows(mode, mi, ni); });
+    };
+    auto split = [&](auto ni) {   // the six-term bf16 form on 128 x (16 NI) tiles
+        ig_with_mode<kADense, kAIm2colF32, kAIm2colU8, kAIm2colU8S, kACol2im>(A.mode, [&](auto mode) {
+            hipLaunchKernelGGL((igemm_rows_split_kernel<decltype(mode)::value, 2, decltype(ni)::value>),
+                               dim3((unsigned)(((Mp + 127) / 128 + 7) / 8 * 8), N / (16 * decltype(ni)::value), phases), dim3(kIgThreads), 0, (hipStream_t)stream,
+                               A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue, bias, mask, (int)ldmask);
+        });
+    };
+    constexpr IgInt<1> i1{};
+    constexpr IgInt<2> i2{};
+    constexpr IgInt<4> i4{};
     // A dense product over few rows (one rollout step of the width-general policies: 4096 rows) fills the chip only with 64-row tiles.
     const int tn = N % 64 == 0 ? 64 : N % 32 == 0 ? 32 : 16;
     const bool few = A.mode == kADense && ((Mp + (tn == 16 ? 255 : 127)) / (tn == 16 ? 256 : 128)) * (N / tn) < 256;
     if (g_ig_products == 1 && !few && tn >= 32 && Kp % kIgSplitBK == 0 && A.mode <= kAIm2colU8S) {   // opt-in: the six-term bf16 form of the same products (modes 5, 6: always the fp32 kernel)
-#define PFA_IG_SPLIT(MODE, NI)                                                                                                             \
-    hipLaunchKernelGGL((igemm_rows_split_kernel<MODE, 2, NI>), dim3((unsigned)(((Mp + 127) / 128 + 7) / 8 * 8), N / (16 * NI), phases),    \
-                       dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue,   \
-                       bias, mask, (int)ldmask)
-#define PFA_IG_SPLIT_MODE(NI)                                        \
-    switch (A.mode) {                                                \
-        case kADense: PFA_IG_SPLIT(kADense, NI); break;              \
-        case kAIm2colF32: PFA_IG_SPLIT(kAIm2colF32, NI); break;      \
-        case kAIm2colU8: PFA_IG_SPLIT(kAIm2colU8, NI); break;        \
-        case kAIm2colU8S: PFA_IG_SPLIT(kAIm2colU8S, NI); break;      \
-        default: PFA_IG_SPLIT(kACol2im, NI); break;                  \
-    }
-        if (tn == 64) {
-            PFA_IG_SPLIT_MODE(4)
-        } else {
-            PFA_IG_SPLIT_MODE(2)
-        }
-#undef PFA_IG_SPLIT_MODE
-#undef PFA_IG_SPLIT
+        if (tn == 64) split(i4);
+        else split(i2);
     } else if (few) {
-        if (tn == 64) {
-            PFA_IG_ROWS(kADense, 1, 4);
-        } else if (tn == 32) {
-            PFA_IG_ROWS(kADense, 1, 2);
-        } else {
-            PFA_IG_ROWS(kADense, 1, 1);
-        }
+        constexpr std::integral_constant<IgAMode, kADense> dense{};
+        if (tn == 64) rows(dense, i1, i4);
+        else if (tn == 32) rows(dense, i1, i2);
+        else rows(dense, i1, i1);
     } else if (N % 64 == 0) {
-#if PFA_IG_TILE64 == 1     // experiment (tools/igemm_bench.py): 64 x 64 tiles, 20 KB of LDS per workgroup -> 8 instead of 5 waves per SIMD
-        PFA_IG_ROWS_MODE(1, 4)
-#elif PFA_IG_TILE64 == 2   // ... or 128 x 32: 25.6 KB, 6 waves per SIMD
-        PFA_IG_ROWS_MODE(2, 2)
-#else
-        PFA_IG_ROWS_MODE(2, 4)
-#endif
+        rows_any(i2, i4);
     } else if (N % 32 == 0) {
-        PFA_IG_ROWS_MODE(2, 2)   // (128 x 32 beats 256 x 32: the smaller stage keeps more workgroups per CU)
+        rows_any(i2, i2);   // (128 x 32 beats 256 x 32: the smaller stage keeps more workgroups per CU)
     } else {
-        PFA_IG_ROWS_MODE(4, 1)
+        rows_any(i4, i1);
     }
-#undef PFA_IG_ROWS_MODE
-#undef PFA_IG_ROWS
     PFA_LAUNCH_CHECK();
     return 0;
 }
@@ -1230,34 +1220,25 @@ extern "C" int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t 
     const dim3 grid(p.tiles, p.splits);
     {
         ScopedKernelTimer timer("igemm_weights", (hipStream_t)stream);
-#define PFA_IG_WEIGHTS(MODE, KJ, NI)                                                                                                             \
-    hipLaunchKernelGGL((igemm_weights_kernel<MODE, KJ, NI>), grid, dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)M, (int)K, D, (int)ldd, (int)N, \
-                       p.rows_per_split, partial, colpart)
-#define PFA_IG_WEIGHTS_KJ(MODE, NI)                                  \
-    if (p.kj == 4) PFA_IG_WEIGHTS(MODE, 4, NI);                      \
-    else if (p.kj == 3) PFA_IG_WEIGHTS(MODE, 3, NI);                 \
-    else if (p.kj == 1 && MODE == kADense) PFA_IG_WEIGHTS(kADense, 1, NI); \
-    else if (p.kj == 1 && MODE == kAIm2colU8S) PFA_IG_WEIGHTS(kAIm2colU8S, 1, NI); \
-    else PFA_IG_WEIGHTS(MODE, 2, NI);
-#define PFA_IG_WEIGHTS_MODE(NI)                                        \
-    switch (A.mode) {                                                  \
-        case kADense: PFA_IG_WEIGHTS_KJ(kADense, NI) break;            \
-        case kAIm2colF32: PFA_IG_WEIGHTS_KJ(kAIm2colF32, NI) break;    \
-        case kAIm2colU8S: PFA_IG_WEIGHTS_KJ(kAIm2colU8S, NI) break;    \
-        case kAIm2colPad: PFA_IG_WEIGHTS_KJ(kAIm2colPad, NI) break;    \
-        case kAIm2colU8P: PFA_IG_WEIGHTS_KJ(kAIm2colU8P, NI) break;    \
-        default: PFA_IG_WEIGHTS_KJ(kAIm2colU8, NI) break;              \
-    }
-        if (p.tn == 64) {
-            PFA_IG_WEIGHTS_MODE(4)
-        } else if (p.tn == 32) {
-            PFA_IG_WEIGHTS_MODE(2)
-        } else {
-            PFA_IG_WEIGHTS_MODE(1)
-        }
-#undef PFA_IG_WEIGHTS_KJ
-#undef PFA_IG_WEIGHTS_MODE
-#undef PFA_IG_WEIGHTS
+        auto weights = [&](auto ni) {
+            ig_with_mode<kADense, kAIm2colF32, kAIm2colU8S, kAIm2colPad, kAIm2colU8P, kAIm2colU8>(A.mode, [&](auto mode) {
+                constexpr IgAMode MODE = decltype(mode)::value;
+                constexpr int NI = decltype(ni)::value;
+                auto go = [&](auto kj) {
+                    hipLaunchKernelGGL((igemm_weights_kernel<MODE, decltype(kj)::value, NI>), grid, dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)M, (int)K, D,
+                                       (int)ldd, (int)N, p.rows_per_split, partial, colpart);
+                };
+                if (p.kj == 4) return go(IgInt<4>{});
+                if (p.kj == 3) return go(IgInt<3>{});
+                if constexpr (MODE == kADense || MODE == kAIm2colU8S) {   // the only operands whose K comes this small
+                    if (p.kj == 1) return go(IgInt<1>{});
+                }
+                go(IgInt<2>{});
+            });
+        };
+        if (p.tn == 64) weights(IgInt<4>{});
+        else if (p.tn == 32) weights(IgInt<2>{});
+        else weights(IgInt<1>{});
         PFA_LAUNCH_CHECK();
     }
     const long long total = (long long)K * N + N;

@@ -31,20 +31,6 @@
 #include "ppo_tile.hpp"
 #include "p2p_ll.hpp"
 
-#ifndef PFA_GRAD_FCOL
-#define PFA_GRAD_FCOL 1   // 0 = the trailing column through a full MFMA k-step in the forward (A/B timing)
-#endif
-#ifndef PFA_GRAD_GLDS
-// 1 = the next X tile by direct-to-LDS loads (global_load_lds_dwordx4, swizzled chunk layout, third tile slot) instead of the
-// 16-register prefetch + 8 ds_writes.  Built and measured in round 4 (profiles/r04_grad_variants.txt): identical bits, 54.75 vs
-// 54.73 us per launch — the register allocation is set by the consumer branch (dW1 accumulators), so the producer's freed
-// prefetch registers change neither the occupancy nor the three loop-invariant dwords that spill.  Kept as a variant, off.
-#define PFA_GRAD_GLDS 0
-#endif
-#ifndef PFA_GRAD_PIPE
-#define PFA_GRAD_PIPE 1   // 0 = the round-2 instruction order (kept for A/B timing with tools/variant_bench.py)
-#endif
-
 namespace pfa {
 
 // (producer, consumer) wavefront pairs per workgroup.  Rows of up to 64 floats: 4 pairs = 8 waves, two per SIMD, two workgroups
@@ -61,40 +47,21 @@ constexpr int grad_waves_per_simd(int dp) { return dp <= 64 ? 2 : 1; }
 // Shared by all waves: lane-major MFMA fragment tables, every fragment read one conflict-free ds_read_b128:
 //   w1t[m][lane][KS(+4)] A frags of the forward GEMM: W1[16m + c][4kk + g]
 //   b1t[m][lane][4] accumulator init   w2t[m][lane][4] A frags of the heads   w2bt[m][lane][4] B frags of dh = dout.W2v
-// GL (64-float rows in the pipelined form): the X tiles are filled by direct-to-LDS loads (global_load_lds_dwordx4: the data never
-// passes through registers).  Such a load writes wave-uniform base + lane x 16 B, so the tile is stored as 16-byte chunks in the
-// order the lanes issue them, and which (row, column quad) a lane fetches is chosen so that both fragment reads stay free of bank
-// conflicts: chunk (row, kk) — columns 4 kk .. 4 kk + 3 of a row — sits in 1 KB block kk / 4 at position
-//   16 (kk & 3) + (row & 12) + ((row + kk) & 3)
-// (the forward's B fragment reads 16 rows x one kk per instruction, the consumer's A fragment 4 rows x 4 kk: either way the 64
-// lanes hit 64 different banks; the padded [row][DP + 2] tile of the register-staged form has 2-way conflicts on the second).
-// A third slot: the load of X(j+1) is issued at the top of tile j, while the consumer still reads X(j-1).
-constexpr bool grad_glds(int dp, int ktm) { return PFA_GRAD_GLDS && PFA_GRAD_PIPE && dp == 64 && ktm <= 3; }
-template <int DP, bool GL = false>
+template <int DP>
 struct GradLds {
     static constexpr int XS = XTile<DP>::XS;
     static constexpr int KS = DP / 4;
     static constexpr int W1S = KS + 4;        // lane stride of w1t (16 B aligned, spreads 16 lanes over all banks)
     static constexpr int HS = kHidden + 4;    // row stride of the hidden tile (16 B aligned rows, conflict-free reads)
     static constexpr int DS = 20;             // dout tile row stride
-    static constexpr int kXSlot = GL ? 16 * DP : 16 * XS;   // floats per X tile
-    static constexpr int kXSlots = GL ? 3 : 2;
-    static constexpr int kXT = 0;                        // + slot * kXSlot          X tiles (ring)
-    static constexpr int kHT = kXSlots * kXSlot;         // hidden tile [row][u] (post-relu) of the published tile
+    static constexpr int kXSlot = 16 * XS;    // floats per X tile [row][XS]
+    static constexpr int kXT = 0;                        // + slot * kXSlot          two X tiles (ring)
+    static constexpr int kHT = 2 * kXSlot;               // hidden tile [row][u] (post-relu) of the published tile
     static constexpr int kDT = kHT + 16 * HS;            // dout tile [row][o] of the published tile
     static constexpr int kPairFloats = kDT + 16 * DS;
     static constexpr int kW1Floats = kMT * 64 * W1S;
     static constexpr int kTabFloats = kMT * 64 * 4;
     static constexpr int kFloats = grad_pairs(DP) * kPairFloats + kW1Floats + 3 * kTabFloats;
-    // float index of X[row][col] inside a tile
-    __device__ static __forceinline__ int xi(int row, int col) {
-        if constexpr (GL) {
-            const int kk = col >> 2;
-            return (kk >> 2) * 256 + (((kk & 3) << 4) + (row & 12) + ((row + kk) & 3)) * 4 + (col & 3);
-        } else {
-            return row * XS + col;
-        }
-    }
 };
 
 // "Native" layout of one workgroup partial: gradients in MFMA C-fragment order (conflict-free LDS reduction and
@@ -110,6 +77,40 @@ struct NativeLayout {
     static constexpr int kDb2 = kDb1 + kHidden;              // o (16)
     static constexpr int kStats = kDb2 + kOut;               // 8
     static constexpr int kCount = kStats + kNumStats;
+};
+
+// One instantiation of ppo_mlp_grad_kernel and everything the host derives from it: what its launch needs, the layout of the
+// partials it writes — which names the reduce kernels that may read them — and its MFMA count.  with_grad_shape (below, in front of
+// the launches) is the table of the shapes that exist and the one place that maps a policy's dimensions to one of them.
+//   KKU  k-steps of the forward that carry data (ceil(obs_dim / 4))        MH   MultiDiscrete heads
+//   KTM / COL  dW1 on MFMA for the first KTM 16-column tiles, COL: + the one trailing column on the VALU (the 7x7 grid's column 48)
+//   PERM  the head outputs in permuted fragment rows (ppo_tile.hpp)
+constexpr int kGradShapes = 13;
+template <int DP, int KKU, bool MH, int KTM, bool COL, bool PERM>
+struct GradShape {
+    static constexpr int kDP = DP, kKKU = KKU, kKTM = KTM;
+    static constexpr bool kMH = MH, kCol = COL, kPerm = PERM;
+    using Lds = GradLds<DP>;
+    using Layout = NativeLayout<DP, KTM, COL>;
+    // the software-pipelined instruction order costs ~40 registers (double-buffered fragments, all eight dh / hidden-tile fragments
+    // live at once): taken where the instantiation stays inside its register budget without spilling (checked in the ISA); the
+    // other shapes run the plain order
+    static constexpr bool kPipe = DP <= 32 || (DP == 64 && KTM <= 3);
+    // FCOL: with COL the forward, too, runs the trailing observation column (k = 16 KTM, the 7x7 grid's column 48) as 32 VALU fmas on
+    // the accumulators instead of a whole k-step of 8 MFMAs that multiplies three padding columns with it: KKM k-steps on MFMA
+    static constexpr bool kFcol = COL && kPipe && KKU > 4 * KTM;
+    static constexpr int kKKM = kFcol ? 4 * KTM : KKU;
+    static_assert(!PERM || (kPipe && !MH), "the permuted head layout is wired into the pipelined single-head form");
+    static constexpr int kThreads = grad_threads(DP);
+    static constexpr size_t kLdsBytes = (size_t)Lds::kFloats * sizeof(float);
+    static_assert((size_t)2 * Layout::kCount * sizeof(float) <= kLdsBytes, "the two reduction buffers must fit in the tile/table area");
+    static constexpr int kReduceGrid = (Layout::kCount + 63) / 64;   // workgroups of the reduce launch = f64 pieces of sum(g^2) it leaves
+    // MFMA instructions per 16-row tile: forward KKM x kMT, heads 4 x kMT, dW2v 4 x kMT, dh 4 (PERM: 3) x kMT, dW1 KTM x 4 x kMT
+    static constexpr int kMfmaPerTile = (kKKM + (PERM ? 11 : 12) + 4 * KTM) * kMT;
+    // dense number for per-shape caches: two per row width other than 64 (MH), then the five forms of 64-float rows
+    static constexpr int kIndex = DP != 64 ? 2 * (DP == 16 ? 0 : DP == 32 ? 1 : DP == 96 ? 2 : 3) + (MH ? 1 : 0)
+                                           : 8 + (PERM ? 0 : COL ? 1 : KKU == 13 ? 2 : MH ? 3 : 4);
+    static_assert(kIndex < kGradShapes, "kGradShapes");
 };
 
 }  // namespace pfa
@@ -149,21 +150,15 @@ template <int DP, int ABL = 0, int KKU = DP / 4, bool MH = false, int KTM = DP /
 __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
     ppo_mlp_grad_kernel(pfa_experience ex, RowMap map, long long mb_rows, const float *params, int a, uint32_t heads,
                         pfa_ppo_hparams hp, const double *adv_stats /* [nmb][2] */, double global_rows, float *partials) {
-    constexpr bool kGlds = grad_glds(DP, KTM);
-    using L = GradLds<DP, kGlds>;
-    using NL = NativeLayout<DP, KTM, COL>;
+    using GS = GradShape<DP, KKU, MH, KTM, COL, PERM>;
+    using L = typename GS::Lds;
+    using NL = typename GS::Layout;
     constexpr int XS = L::XS, HS = L::HS, DS = L::DS, KS = DP / 4, V = DP / 4, W1S = L::W1S;
     constexpr int NLD = (16 * V + 63) / 64;  // float4 loads per lane per tile
     constexpr int kGradPairs = grad_pairs(DP), kGradThreads = grad_threads(DP);
     constexpr bool kQuad = kGradPairs == 4 && 4 * NL::kCount <= L::kFloats;   // epilogue: four reduction buffers side by side
-    // the software-pipelined instruction order costs ~40 registers (double-buffered fragments, all eight dh / hidden-tile fragments
-    // live at once): taken where the instantiation stays inside its register budget without spilling (checked in the ISA)
-    constexpr bool kPipe = PFA_GRAD_PIPE && (DP <= 32 || (DP == 64 && KTM <= 3));
-    // FCOL: with COL the forward, too, runs the trailing observation column (k = 16 KTM, the 7x7 grid's column 48) as 32 VALU fmas on
-    // the accumulators instead of a whole k-step of 8 MFMAs that multiplies three padding columns with it: KKM k-steps on MFMA
-    constexpr bool FCOL = PFA_GRAD_FCOL && COL && kPipe && KKU > 4 * KTM;
-    constexpr int KKM = FCOL ? 4 * KTM : KKU;
-    static_assert(!PERM || (kPipe && !MH), "the permuted head layout is wired into the pipelined single-head form");
+    constexpr bool kPipe = GS::kPipe, FCOL = GS::kFcol;   // instruction order and the forward's trailing column: GradShape
+    constexpr int KKM = GS::kKKM;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = lane_id(), wv = wave_id(), c = lane & 15, g = lane >> 4;   // (wv is a scalar: common.hpp)
     const int pair = wv & (kGradPairs - 1);
@@ -176,7 +171,6 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
     const MlpOffsets off = mlp_offsets(DP, a);
 
     // Build the fragment tables.  All global loads of a thread are issued before the first LDS store so they pipeline.
-#ifndef PFA_DBG_SKIP_TABLES   // (timing experiments only, tools/variant_bench.py: what the table build costs per launch)
     {
         constexpr int N1 = kMT * 64 * KS / kGradThreads, N2 = kMT * 64 * 4 / kGradThreads;
         static_assert(kMT * 64 * KS % kGradThreads == 0 && kMT * 64 * 4 % kGradThreads == 0, "table sizes");
@@ -230,7 +224,6 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
             }
         }
     }
-#endif
 
     const long long tiles = mb_rows / 16;
     const long long pair_global = (long long)blockIdx.x * kGradPairs + pair;
@@ -265,9 +258,9 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
 #pragma unroll
         for (int i = 0; i < 6; ++i) stats[i] = 0.0f;
 
-        float4 xpre[kGlds ? 1 : NLD];  // register prefetch of the next tile's X rows (GL: none, the rows go straight to LDS)
+        float4 xpre[NLD];  // register prefetch of the next tile's X rows
         RowScalars rspre;
-        auto prefetch = [&](long long tile, float *xdst) {   // xdst: the LDS slot of `tile` (GL)
+        auto prefetch = [&](long long tile) {
             const bool ok = tile < tiles;
             const unsigned first = ok ? map.tile_first((unsigned)tile) : 0u;
             rspre = RowScalars{0, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -275,20 +268,6 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
                 const unsigned fr = map.tile_row((unsigned)tile, first, c, aligned);
                 rspre = RowScalars{ex.actions[fr], ex.logprobs[fr], ex.values[fr], ex.advantages[fr], ex.returns[fr], 1.0f};
             }
-            if constexpr (kGlds) {
-                // lane l of block b fetches chunk (row, kk = 4b + (l >> 4)) with row = (l & 12) + ((l - (l >> 4)) & 3): position l of the block
-                const int kl = lane >> 4, row = (lane & 12) + ((lane - kl) & 3);
-                if (ok) {
-                    const unsigned frow = map.tile_row((unsigned)tile, first, row, aligned);
-                    const float *src = ex.obs + (size_t)frow * DP + 4 * kl;
-#pragma unroll
-                    for (int b = 0; b < DP / 16; ++b)
-                        __builtin_amdgcn_global_load_lds(src + 16 * b, (__attribute__((address_space(3))) void *)(xdst + 256 * b), 16, 0, 0);
-                } else {   // a pair's padding tile: zeros (its rows carry weight 0, but whatever the slot held must not reach the loss)
-#pragma unroll
-                    for (int b = 0; b < DP / 16; ++b) *reinterpret_cast<float4 *>(xdst + 256 * b + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            } else {
 #pragma unroll
             for (int j = 0; j < NLD; ++j) {
                 const int idx = lane + 64 * j;
@@ -299,17 +278,15 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
                     xpre[j] = *reinterpret_cast<const float4 *>(ex.obs + (size_t)row * DP + 4 * c4);
                 }
             }
-            }
         };
-        prefetch(pair_global, pl + L::kXT);
-        __syncthreads();  // fragment tables ready (GL: and X(0) landed — a workgroup barrier drains the direct-to-LDS loads)
+        prefetch(pair_global);
+        __syncthreads();  // fragment tables ready
 
         float *hsP = pl + L::kHT, *dsP = pl + L::kDT;
         for (int j = 0; j < J; ++j) {
-            float *xs = pl + L::kXT + (j % L::kXSlots) * L::kXSlot;
+            float *xs = pl + L::kXT + (j % 2) * L::kXSlot;
             PFA_STAMP(j, 0);
             // ---- stage X(j), forward, heads, loss (registers + this tile's X slot only) ------------------------------
-            if constexpr (!kGlds) {
 #pragma unroll
             for (int q = 0; q < NLD; ++q) {
                 const int idx = lane + 64 * q;
@@ -320,10 +297,8 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
                     d[1] = make_float2(xpre[q].z, xpre[q].w);
                 }
             }
-            }
             const RowScalars rs = rspre;
-            // lands during this tile's ~10k cycles (GL: in the slot X(j-2) used; the barrier pair of this tile drains it)
-            prefetch(pair_global + (long long)(j + 1) * pair_count, pl + L::kXT + ((j + 1) % L::kXSlots) * L::kXSlot);
+            prefetch(pair_global + (long long)(j + 1) * pair_count);   // lands during this tile's ~10k cycles
             wave_lds_fence();
             PFA_STAMP(j, 1);
 
@@ -340,7 +315,7 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
             float xb[2][4];
             auto load_group = [&](int k4, int b) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) xb[b][q] = xs[L::xi(c, 4 * (4 * k4 + q) + g)];
+                for (int q = 0; q < 4; ++q) xb[b][q] = xs[c * XS + 4 * (4 * k4 + q) + g];
 #pragma unroll
                 for (int m = 0; m < kMT; ++m) wq[b][m] = *reinterpret_cast<const f32x4 *>(w1t + (m * 64 + lane) * W1S + 4 * k4);
             };
@@ -359,7 +334,7 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (FCOL) {
-                const float xcol = xs[L::xi(c, 16 * KTM)];     // X[row = c][16 KTM]
+                const float xcol = xs[c * XS + 16 * KTM];     // X[row = c][16 KTM]
 #pragma unroll
                 for (int m = 0; m < kMT; ++m) {
                     const f32x4 wc = *reinterpret_cast<const f32x4 *>(w1t + (m * 64 + lane) * W1S + KS);
@@ -558,14 +533,14 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
         auto backward_tile = [&](int jj) {
             const long long tile = pair_global + (long long)jj * pair_count;
             if ((ABL & 2) || tile >= tiles) return;
-            const float *xs = pl + L::kXT + (jj % L::kXSlots) * L::kXSlot;
+            const float *xs = pl + L::kXT + (jj % 2) * L::kXSlot;
             const f32x4 dout = *reinterpret_cast<const f32x4 *>(dsP + c * DS + 4 * g);
             float xa[KTM][4], xc[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
 #pragma unroll
-                for (int kt = 0; kt < KTM; ++kt) xa[kt][r] = xs[L::xi(4 * g + r, 16 * kt + c)];
-                xc[r] = COL ? xs[L::xi(4 * g + r, 16 * KTM)] : 0.0f;
+                for (int kt = 0; kt < KTM; ++kt) xa[kt][r] = xs[(4 * g + r) * XS + 16 * kt + c];
+                xc[r] = COL ? xs[(4 * g + r) * XS + 16 * KTM] : 0.0f;
             }
             if constexpr (kPipe) {
             // every LDS read of the tile is issued up front (dout, the X fragments above, the W2v fragments, the hidden tile for
@@ -694,9 +669,6 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
             __syncthreads();
         }
     }
-#ifdef PFA_DBG_SKIP_STORE
-    if (blockIdx.x != 0xFFFF) return;
-#endif
     float *dst = partials + (size_t)blockIdx.x * NL::kCount;
     if constexpr (kQuad) {
         for (int i = threadIdx.x; i < NL::kCount; i += kGradThreads)
@@ -709,10 +681,7 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
 // Fixed-order sum of the workgroup partials (native layout) + scatter into the flat gradient layout, plus one
 // f64 partial of sum(g^2) per block for the gradient-norm clip.  Block = 64 native slots x 4 slices of the
 // partial index; 16 independent loads in flight per thread.
-#ifndef PFA_REDUCE_SLICES
-#define PFA_REDUCE_SLICES 16   // slices of the partial index per slot (4 = the round-2 shape, for A/B timing)
-#endif
-constexpr int kRedSl = PFA_REDUCE_SLICES;
+constexpr int kRedSl = 16;   // slices of the partial index per slot
 // (16 slices: 163 workgroups x 16 waves, every thread's 16 loads in flight at once — the reduction is a latency chain over the
 // L2-resident partials, and 4 waves per workgroup left most SIMDs without a wave to hide it)
 template <int DP, int KTM = DP / 16, bool COL = false, bool PERM = false>
@@ -1182,23 +1151,45 @@ static int check_update_args(const pfa_experience *ex, int64_t batch_rows, const
     return 0;
 }
 
-// the 7x7 grid behind one Discrete head on 64-float rows runs the instantiation with 3 dW1 k-tiles + the column-48 accumulator
-static bool grad_trimmed(const pfa_mlp_dims *dims) { return dims->obs_stride == 64 && !dims->heads && dims->obs_dim == 49; }
-#ifndef PFA_GRAD_PERM
-#define PFA_GRAD_PERM 1   // 0 = head outputs in natural fragment rows everywhere (A/B timing)
-#endif
-// ... and, with at most 11 actions (12 outputs with the value), the permuted head rows: three k-steps of dh instead of four
-static bool grad_perm(const pfa_mlp_dims *dims) { return PFA_GRAD_PERM && dims->num_actions <= 11; }
-// the opt-in product form (pfa_igemm_set_products(1): every fp32 product as six bf16 partial products, fp32 accumulate) covers the
-// headline shape: the 7x7 grid on 64-float rows behind one Discrete head, minibatches of whole 32-row tiles
-static bool grad_bf16(const pfa_mlp_dims *dims, int64_t mbs) { return pfa_igemm_get_products() == 1 && grad_trimmed(dims) && mbs >= 32 && mbs % 32 == 0; }
-static int norm_blocks(const pfa_mlp_dims *dims) {   // workgroups of the reduce launch = f64 pieces of sum(g^2) it leaves
-    const int count = grad_trimmed(dims) ? NativeLayout<64, 3, true>::kCount
-                                         : (dims->obs_stride / 16) * kMT * 4 * 64 + kMT * 4 * 64 + kHidden + kOut + kNumStats;
-    return (count + 63) / 64;
+// THE TABLE of gradient shapes: every instantiation of ppo_mlp_grad_kernel the library launches, and the one place that maps a policy's
+// dimensions to one of them — f(shape) is called with the GradShape these dimensions run.  Everything that has to agree with the
+// gradient launch (the reduce kernels that read its partials, their grids, the MFMA count) reads it off that shape.  The caller
+// has checked obs_stride (16 / 32 / 64 / 96 / 128).
+template <typename F>
+static auto with_grad_shape(const pfa_mlp_dims *dims, F &&f) {
+    const bool mh = dims->heads != 0;
+    switch (dims->obs_stride) {
+        case 16: return mh ? f(GradShape<16, 4, true, 1, false, false>{}) : f(GradShape<16, 4, false, 1, false, false>{});
+        case 32: return mh ? f(GradShape<32, 8, true, 2, false, false>{}) : f(GradShape<32, 8, false, 2, false, false>{});
+        case 96: return mh ? f(GradShape<96, 24, true, 6, false, false>{}) : f(GradShape<96, 24, false, 6, false, false>{});
+        case 128: return mh ? f(GradShape<128, 32, true, 8, false, false>{}) : f(GradShape<128, 32, false, 8, false, false>{});
+        default: break;
+    }
+    if (mh) return f(GradShape<64, 16, true, 4, false, false>{});
+    // the 7x7 grid behind one Discrete head: 13 of 16 forward k-steps, dW1 = 3 k-tiles + the column-48 accumulator ...
+    if (dims->obs_dim == 49) {
+        // ... and, with at most 11 actions (12 outputs with the value), the permuted head rows: three k-steps of dh instead of four
+        if (dims->num_actions <= 11) return f(GradShape<64, 13, false, 3, true, true>{});
+        return f(GradShape<64, 13, false, 3, true, false>{});
+    }
+    if ((dims->obs_dim + 3) / 4 == 13) return f(GradShape<64, 13, false, 4, false, false>{});
+    return f(GradShape<64, 16, false, 4, false, false>{});
 }
-static size_t native_count(int dp) { return (size_t)(dp / 16) * kMT * 4 * 64 + kMT * 4 * 64 + kHidden + kOut + kNumStats; }
-static size_t partials_bytes(const pfa_mlp_dims *dims) {   // (the opt-in bf16 form runs two workgroups per CU: kBfMaxGrid partials)
+// the opt-in product form (pfa_igemm_set_products(1): every fp32 product as six bf16 partial products, fp32 accumulate) covers the
+// headline shape: the 7x7 grid on 64-float rows behind one Discrete head (the trimmed shapes), minibatches of whole 32-row tiles
+static bool grad_bf16(const pfa_mlp_dims *dims, int64_t mbs) {
+    return pfa_igemm_get_products() == 1 && mbs >= 32 && mbs % 32 == 0 && with_grad_shape(dims, [](auto s) { return decltype(s)::kCol; });
+}
+static int norm_blocks(const pfa_mlp_dims *dims) {   // workgroups of the reduce launch = f64 pieces of sum(g^2) it leaves
+    return with_grad_shape(dims, [](auto s) { return decltype(s)::kReduceGrid; });
+}
+// Workspace sizing.  Deliberately NOT per shape: native_count is the UNTRIMMED layout of the row width (the trimmed 7x7 shapes need
+// less), and 64-float rows are sized for the kBfMaxGrid partials of the opt-in bf16 form (two workgroups per CU) whether or not it is
+// switched on — a workspace stays valid whatever shape or product form the same trainer runs later.
+constexpr size_t native_count(int dp) { return (size_t)(dp / 16) * kMT * 4 * 64 + kMT * 4 * 64 + kHidden + kOut + kNumStats; }
+static_assert(native_count(16) == NativeLayout<16>::kCount && native_count(64) == NativeLayout<64>::kCount && native_count(128) == NativeLayout<128>::kCount,
+              "native_count is NativeLayout's count without trimming");
+static size_t partials_bytes(const pfa_mlp_dims *dims) {
     return align_up((size_t)(dims->obs_stride == 64 ? kBfMaxGrid : 256) * native_count(dims->obs_stride) * sizeof(float), 256);
 }
 static double *norm_partials_of(void *workspace, const pfa_mlp_dims *dims) {  // after the gradient partials
@@ -1216,7 +1207,6 @@ static size_t tail_bytes(const pfa_mlp_dims *dims, int nmb) {   // what follows 
     const size_t normp = align_up(((native + 63) / 64) * 2 * sizeof(double), 256);   // (the one-launch form: two 8-byte words per piece)
     return advp > normp ? advp : normp;
 }
-
 
 static int grad_grid(int64_t mb_rows, int dp) {
     const int64_t tiles = mb_rows / 16;
@@ -1253,6 +1243,27 @@ extern "C" int pfa_ppo_adv_stats(const pfa_experience *exp, int64_t batch_rows, 
     return 0;
 }
 
+template <class S, int ABL = 0>   // the kernel of a GradShape
+constexpr auto grad_kernel_of = &ppo_mlp_grad_kernel<S::kDP, ABL, S::kKKU, S::kMH, S::kKTM, S::kCol, S::kPerm>;
+// One launch of a gradient kernel with `lds_bytes` of dynamic LDS.  KERNEL is a template argument, so the once-only attribute call
+// is once per instantiation.
+struct GradLaunch {
+    hipStream_t stream;
+    bool timed;   // with events around the dispatch
+    hipEvent_t ev0, ev1;
+};
+template <auto KERNEL, typename... Args>
+static int launch_grad_kernel(const GradLaunch &at, int grid, int threads, size_t lds_bytes, Args... args) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        attr_set = true;
+    }
+    if (at.timed) hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), lds_bytes, at.stream, at.ev0, at.ev1, 0, args...);
+    else hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), lds_bytes, at.stream, args...);
+    return 0;
+}
+
 // Kernel A of one optimizer step: validates the arguments and launches the fused forward + loss + backward over minibatch `mb`;
 // leaves *grid_out workgroup partials in the workspace.
 static int launch_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb, const float *params,
@@ -1276,85 +1287,29 @@ static int launch_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb
     PFA_REQUIRE(global_mb_rows >= mbs, "ppo.grad: global_mb_rows < local minibatch rows");
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     float *partials = (float *)workspace;
+    // bench.py's roofline leg: the launch carries its own events (stamped with the dispatch's begin and end)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    const bool timed = timing_pair("ppo_mlp_grad", &ev0, &ev1);
+    ScopedKernelTimer timer(timing_ext_mode() ? nullptr : "ppo_mlp_grad", (hipStream_t)stream);
+    const GradLaunch at{(hipStream_t)stream, timed, ev0, ev1};
+    int grid;
     if (grad_bf16(dims, mbs)) {   // opt-in product form (pfa_igemm_set_products(1)): the same step on the bf16 matrix path, csrc/ppo_bf16.hpp
         const int64_t tiles32 = mbs / 32;
-        const int grid = (int)(tiles32 < kBfMaxGrid ? tiles32 : kBfMaxGrid);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        const bool timed = timing_pair("ppo_mlp_grad", &ev0, &ev1);
-        ScopedKernelTimer timer(timing_ext_mode() ? nullptr : "ppo_mlp_grad", (hipStream_t)stream);
-#define PFA_LAUNCH_GRAD_BF16(PERMV)                                                                                                       \
-    {                                                                                                                                    \
-        static bool attr_set = false;                                                                                                    \
-        if (!attr_set) {                                                                                                                 \
-            PFA_CHECK_HIP(hipFuncSetAttribute((const void *)ppo_mlp_grad_bf16_kernel<PERMV>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                              (int)BfLds::kBytes));                                                                      \
-            attr_set = true;                                                                                                             \
-        }                                                                                                                                \
-        if (timed)                                                                                                                       \
-            hipExtLaunchKernelGGL((ppo_mlp_grad_bf16_kernel<PERMV>), dim3(grid), dim3(kBfThreads), BfLds::kBytes, (hipStream_t)stream,    \
-                                  ev0, ev1, 0, *exp, map, (long long)mbs, params, dims->num_actions, *hp, adv_stats,                     \
-                                  (double)global_mb_rows, partials);                                                                     \
-        else                                                                                                                             \
-            hipLaunchKernelGGL((ppo_mlp_grad_bf16_kernel<PERMV>), dim3(grid), dim3(kBfThreads), BfLds::kBytes, (hipStream_t)stream, *exp, \
-                               map, (long long)mbs, params, dims->num_actions, *hp, adv_stats, (double)global_mb_rows, partials);        \
+        grid = (int)(tiles32 < kBfMaxGrid ? tiles32 : kBfMaxGrid);
+        const int rc = with_grad_shape(dims, [&](auto s) {
+            return launch_grad_kernel<ppo_mlp_grad_bf16_kernel<decltype(s)::kPerm>>(at, grid, kBfThreads, BfLds::kBytes, *exp, map, (long long)mbs, params,
+                                                                                    dims->num_actions, *hp, adv_stats, (double)global_mb_rows, partials);
+        });
+        if (rc) return rc;
+    } else {
+        grid = grad_grid(mbs, dims->obs_stride);
+        const int rc = with_grad_shape(dims, [&](auto s) {
+            using S = decltype(s);
+            return launch_grad_kernel<grad_kernel_of<S>>(at, grid, S::kThreads, S::kLdsBytes, *exp, map, (long long)mbs, params, dims->num_actions,
+                                                         dims->heads, *hp, adv_stats, (double)global_mb_rows, partials);
+        });
+        if (rc) return rc;
     }
-        if (grad_perm(dims)) PFA_LAUNCH_GRAD_BF16(true)
-        else PFA_LAUNCH_GRAD_BF16(false)
-#undef PFA_LAUNCH_GRAD_BF16
-        PFA_LAUNCH_CHECK();
-        *grid_out = grid;
-        return 0;
-    }
-    const int grid = grad_grid(mbs, dims->obs_stride);
-#define PFA_LAUNCH_GRAD_FULL(DPV, KKUV, MHV, KTMV, COLV) PFA_LAUNCH_GRAD_PERM(DPV, KKUV, MHV, KTMV, COLV, false)
-#define PFA_LAUNCH_GRAD_PERM(DPV, KKUV, MHV, KTMV, COLV, PERMV)                                                             \
-    {                                                                                                                      \
-        constexpr size_t lds_bytes = (size_t)GradLds<DPV, grad_glds(DPV, KTMV)>::kFloats * sizeof(float);                       \
-        static_assert((size_t)2 * NativeLayout<DPV, KTMV, COLV>::kCount * sizeof(float) <= lds_bytes,                       \
-                      "the two reduction buffers must fit in the tile/table area");                                       \
-        static bool attr_set = false;                                                                                      \
-        if (!attr_set) {                                                                                                   \
-            PFA_CHECK_HIP(hipFuncSetAttribute((const void *)ppo_mlp_grad_kernel<DPV, 0, KKUV, MHV, KTMV, COLV, PERMV>,     \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                \
-            attr_set = true;                                                                                               \
-        }                                                                                                                  \
-        if (grad_timed)                                                                                                    \
-            hipExtLaunchKernelGGL((ppo_mlp_grad_kernel<DPV, 0, KKUV, MHV, KTMV, COLV, PERMV>), dim3(grid), dim3(grad_threads(DPV)), \
-                                  lds_bytes, (hipStream_t)stream, grad_ev0, grad_ev1, 0, *exp, map, (long long)mbs, params,  \
-                                  dims->num_actions, dims->heads, *hp, adv_stats, (double)global_mb_rows, partials);      \
-        else                                                                                                               \
-            hipLaunchKernelGGL((ppo_mlp_grad_kernel<DPV, 0, KKUV, MHV, KTMV, COLV, PERMV>), dim3(grid), dim3(grad_threads(DPV)), \
-                               lds_bytes, (hipStream_t)stream, *exp, map, (long long)mbs, params, dims->num_actions,       \
-                               dims->heads, *hp, adv_stats, (double)global_mb_rows, partials);                             \
-    }
-#define PFA_LAUNCH_GRAD_KM(DPV, KKUV, MHV) PFA_LAUNCH_GRAD_FULL(DPV, KKUV, MHV, DPV / 16, false)
-#define PFA_LAUNCH_GRAD_K(DPV, KKUV) PFA_LAUNCH_GRAD_KM(DPV, KKUV, false)
-#define PFA_LAUNCH_GRAD(DPV)                                        \
-    if (dims->heads) PFA_LAUNCH_GRAD_KM(DPV, DPV / 4, true)         \
-    else PFA_LAUNCH_GRAD_KM(DPV, DPV / 4, false)
-    {
-        // bench.py's roofline leg: the launch carries its own events (stamped with the dispatch's begin and end); with
-        hipEvent_t grad_ev0 = nullptr, grad_ev1 = nullptr;
-        const bool grad_timed = timing_pair("ppo_mlp_grad", &grad_ev0, &grad_ev1);
-        ScopedKernelTimer timer(timing_ext_mode() ? nullptr : "ppo_mlp_grad", (hipStream_t)stream);
-        switch (dims->obs_stride) {
-            case 16: PFA_LAUNCH_GRAD(16) break;
-            case 32: PFA_LAUNCH_GRAD(32) break;
-            case 96: PFA_LAUNCH_GRAD(96) break;
-            case 128: PFA_LAUNCH_GRAD(128) break;
-            default:
-                if (grad_trimmed(dims) && grad_perm(dims)) PFA_LAUNCH_GRAD_PERM(64, 13, false, 3, true, true)   // + the permuted head rows (<= 11 actions)
-                else if (grad_trimmed(dims)) PFA_LAUNCH_GRAD_FULL(64, 13, false, 3, true)   // 7x7 grid: 13 of 16 forward k-steps, dW1 = 3 k-tiles + column 48
-                else if (!dims->heads && (dims->obs_dim + 3) / 4 == 13) PFA_LAUNCH_GRAD_K(64, 13)
-                else PFA_LAUNCH_GRAD(64)
-                break;
-        }
-    }
-#undef PFA_LAUNCH_GRAD_KM
-#undef PFA_LAUNCH_GRAD_FULL
-#undef PFA_LAUNCH_GRAD_PERM
-#undef PFA_LAUNCH_GRAD
-#undef PFA_LAUNCH_GRAD_K
     PFA_LAUNCH_CHECK();
     *grid_out = grid;
     return 0;
@@ -1368,40 +1323,23 @@ extern "C" int pfa_ppo_mlp_grad(const pfa_experience *exp, int64_t batch_rows, i
     float *partials = (float *)workspace;
     double *normp = norm_partials_of(workspace, dims);
     ScopedKernelTimer timer2("ppo_reduce", (hipStream_t)stream);
-#define PFA_LAUNCH_REDUCE(DPV, KTMV, COLV) PFA_LAUNCH_REDUCE_P(DPV, KTMV, COLV, false)
-#define PFA_LAUNCH_REDUCE_P(DPV, KTMV, COLV, PERMV)                                                                             \
-    hipLaunchKernelGGL((ppo_reduce_kernel<DPV, KTMV, COLV, PERMV>), dim3((NativeLayout<DPV, KTMV, COLV>::kCount + 63) / 64),     \
-                       dim3(64 * kRedSl), 0, (hipStream_t)stream, partials, grid, dims->num_actions, dims->obs_dim, grads, normp)
-    switch (dims->obs_stride) {   // the same instantiation choice as the gradient launch above: the partial layout belongs to it
-        case 16: PFA_LAUNCH_REDUCE(16, 1, false); break;
-        case 32: PFA_LAUNCH_REDUCE(32, 2, false); break;
-        case 96: PFA_LAUNCH_REDUCE(96, 6, false); break;
-        case 128: PFA_LAUNCH_REDUCE(128, 8, false); break;
-        default:
-            if (grad_trimmed(dims) && grad_perm(dims)) PFA_LAUNCH_REDUCE_P(64, 3, true, true);
-            else if (grad_trimmed(dims)) PFA_LAUNCH_REDUCE(64, 3, true);
-            else PFA_LAUNCH_REDUCE(64, 4, false);
-            break;
-    }
-#undef PFA_LAUNCH_REDUCE
-#undef PFA_LAUNCH_REDUCE_P
+    with_grad_shape(dims, [&](auto s) {   // the layout of the partials belongs to the shape that wrote them
+        using S = decltype(s);
+        hipLaunchKernelGGL((ppo_reduce_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm>), dim3(S::kReduceGrid), dim3(64 * kRedSl), 0, (hipStream_t)stream,
+                           partials, grid, dims->num_actions, dims->obs_dim, grads, normp);
+    });
     PFA_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int pfa_ppo_mlp_grad_path(const pfa_mlp_dims *dims, int64_t mb_rows) { return dims && grad_bf16(dims, mb_rows) ? 1 : 0; }
 
-// MFMA instructions per 16-row tile of the instantiation pfa_ppo_mlp_grad dispatches for these dimensions (see the switch there):
-// forward KKU x kMT, heads 4 x kMT, dW2v 4 x kMT, dh 4 x kMT, dW1 KTM x 4 x kMT.
+// MFMA instructions per 16-row tile of the instantiation pfa_ppo_mlp_grad dispatches for these dimensions behind one Discrete head
 extern "C" int pfa_ppo_mlp_grad_mfma_per_tile(int32_t obs_dim, int32_t obs_stride, int32_t num_actions) {
     if (num_actions < 1 || num_actions > 15) return 0;
     if (obs_stride != 16 && obs_stride != 32 && obs_stride != 64 && obs_stride != 96 && obs_stride != 128) return 0;
-    int kku = obs_stride / 4, ktm = obs_stride / 16;
-    if (obs_stride == 64 && (obs_dim + 3) / 4 == 13) kku = 13;
-    if (obs_stride == 64 && obs_dim == 49) ktm = 3;
-    if (PFA_GRAD_FCOL && obs_stride == 64 && obs_dim == 49) kku = 12;   // the forward's column 48 runs on the VALU (FCOL)
-    const bool perm = PFA_GRAD_PERM && obs_stride == 64 && obs_dim == 49 && num_actions <= 11;   // (one Discrete head assumed, as everywhere in this helper)
-    return kku * kMT + (perm ? 11 : 12) * kMT + ktm * 4 * kMT;
+    const pfa_mlp_dims dims{obs_dim, obs_stride, kHidden, num_actions, 0u};
+    return with_grad_shape(&dims, [](auto s) { return decltype(s)::kMfmaPerTile; });
 }
 
 extern "C" int pfa_adam_clip_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t count, float lr,
@@ -1475,27 +1413,17 @@ static bool coresident(K kernel, int blocks) {
     return (long long)per_cu * cus >= blocks;
 }
 static bool reduce_adam_coresident(const pfa_mlp_dims *dims, bool dist) {
-    static int cache[2][8] = {};   // [dist][shape slot]: 0 unknown, 1 yes, 2 no
-    const int slot = dims->obs_stride == 16 ? 0 : dims->obs_stride == 32 ? 1 : dims->obs_stride == 96 ? 2 : dims->obs_stride == 128 ? 3
-                   : (grad_trimmed(dims) && grad_perm(dims)) ? 4 : grad_trimmed(dims) ? 5 : 6;
-    int &c = cache[dist ? 1 : 0][slot];
-    if (c) return c == 1;
-    const int blocks = norm_blocks(dims);
-    bool ok;
-#define PFA_CO(DPV, KTMV, COLV, PERMV) \
-    ok = dist ? coresident(ppo_reduce_adam_kernel<DPV, KTMV, COLV, PERMV, true>, blocks) : coresident(ppo_reduce_adam_kernel<DPV, KTMV, COLV, PERMV, false>, blocks)
-    switch (slot) {
-        case 0: PFA_CO(16, 1, false, false); break;
-        case 1: PFA_CO(32, 2, false, false); break;
-        case 2: PFA_CO(96, 6, false, false); break;
-        case 3: PFA_CO(128, 8, false, false); break;
-        case 4: PFA_CO(64, 3, true, true); break;
-        case 5: PFA_CO(64, 3, true, false); break;
-        default: PFA_CO(64, 4, false, false); break;
-    }
-#undef PFA_CO
-    c = ok ? 1 : 2;
-    return ok;
+    static int cache[2][kGradShapes] = {};   // [dist][shape]: 0 unknown, 1 yes, 2 no
+    return with_grad_shape(dims, [&](auto s) {
+        using S = decltype(s);
+        int &c = cache[dist ? 1 : 0][S::kIndex];
+        if (!c) {
+            const bool ok = dist ? coresident(ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, true>, S::kReduceGrid)
+                                 : coresident(ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, false>, S::kReduceGrid);
+            c = ok ? 1 : 2;
+        }
+        return c == 1;
+    });
 }
 static int launch_reduce_adam(const pfa_mlp_dims *dims, int nmb, int grid, float *params, float *grads, float *exp_avg, float *exp_avg_sq,
                               float lr, float beta1, float beta2, float eps, int64_t step, float max_grad_norm, double *losses,
@@ -1518,26 +1446,14 @@ static int launch_reduce_adam(const pfa_mlp_dims *dims, int nmb, int grid, float
     const GridWords gw{gwords, gen, gstatus, grid_timeout_ticks()};
     const LlArgs none{};
     ScopedKernelTimer timer("ppo_reduce_adam", stream);
-#define PFA_LAUNCH_RA(DPV, KTMV, COLV, PERMV)                                                                                        \
-    {                                                                                                                               \
-        const dim3 g((NativeLayout<DPV, KTMV, COLV>::kCount + 63) / 64), b(64 * kRedSl);                                            \
-        if (ll) hipLaunchKernelGGL((ppo_reduce_adam_kernel<DPV, KTMV, COLV, PERMV, true>), g, b, 0, stream, partials, grid,          \
-                                   dims->num_actions, dims->obs_dim, grads, gw, ad, *ll);                                   \
-        else hipLaunchKernelGGL((ppo_reduce_adam_kernel<DPV, KTMV, COLV, PERMV, false>), g, b, 0, stream, partials, grid,            \
-                                dims->num_actions, dims->obs_dim, grads, gw, ad, none);                                     \
-    }
-    switch (dims->obs_stride) {   // the instantiation choice of the gradient launch: the partial layout belongs to it
-        case 16: PFA_LAUNCH_RA(16, 1, false, false) break;
-        case 32: PFA_LAUNCH_RA(32, 2, false, false) break;
-        case 96: PFA_LAUNCH_RA(96, 6, false, false) break;
-        case 128: PFA_LAUNCH_RA(128, 8, false, false) break;
-        default:
-            if (grad_trimmed(dims) && grad_perm(dims)) PFA_LAUNCH_RA(64, 3, true, true)
-            else if (grad_trimmed(dims)) PFA_LAUNCH_RA(64, 3, true, false)
-            else PFA_LAUNCH_RA(64, 4, false, false)
-            break;
-    }
-#undef PFA_LAUNCH_RA
+    with_grad_shape(dims, [&](auto s) {   // the layout of the partials belongs to the shape that wrote them
+        using S = decltype(s);
+        const dim3 g(S::kReduceGrid), b(64 * kRedSl);
+        if (ll) hipLaunchKernelGGL((ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, true>), g, b, 0, stream, partials, grid,
+                                   dims->num_actions, dims->obs_dim, grads, gw, ad, *ll);
+        else hipLaunchKernelGGL((ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, false>), g, b, 0, stream, partials, grid,
+                                dims->num_actions, dims->obs_dim, grads, gw, ad, none);
+    });
     PFA_LAUNCH_CHECK();
     return 0;
 }
@@ -1659,13 +1575,12 @@ extern "C" int pfa_probe_grad(const pfa_experience *exp, int64_t batch_rows, int
     const int grid = grad_grid(mbs, 64);
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     float *partials = (float *)workspace;
-    constexpr size_t lds_bytes = (size_t)GradLds<64, grad_glds(64, 3)>::kFloats * sizeof(float);
-#define PFA_PROBE_CASE(A)                                                                                              \
-    case A:                                                                                                            \
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)ppo_mlp_grad_kernel<64, A, 13, false, 3, true>,                                \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                \
-        hipLaunchKernelGGL((ppo_mlp_grad_kernel<64, A, 13, false, 3, true>), dim3(grid), dim3(grad_threads(64)), lds_bytes, (hipStream_t)stream, \
-                           *exp, map, (long long)mbs, params, dims->num_actions, 0u, *hp, adv_stats, (double)mbs, partials); \
+    using S = GradShape<64, 13, false, 3, true, false>;   // the 7x7 grid, head rows in natural order
+#define PFA_PROBE_CASE(A)                                                                                                                      \
+    case A:                                                                                                                                    \
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)grad_kernel_of<S, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLdsBytes)); \
+        hipLaunchKernelGGL((grad_kernel_of<S, A>), dim3(grid), dim3(S::kThreads), S::kLdsBytes, (hipStream_t)stream, *exp, map, (long long)mbs, \
+                           params, dims->num_actions, 0u, *hp, adv_stats, (double)mbs, partials);                                              \
         break;
     switch (abl) {
         PFA_PROBE_CASE(0) PFA_PROBE_CASE(1) PFA_PROBE_CASE(2) PFA_PROBE_CASE(4) PFA_PROBE_CASE(6) PFA_PROBE_CASE(7)

@@ -21,6 +21,7 @@
 // partial; ppo_wide_reduce_kernel sums the partials in a fixed order and scatters into torch's tensor shapes through a second
 // view (the gradient buffer of general.GeneralParams: named_parameters() order).  Clip + Adam: pfa_adam_clip_step on the flat buffer.
 #include <cmath>
+#include <type_traits>
 
 #include "common.hpp"
 #include "mlp_tile.hpp"
@@ -29,40 +30,28 @@
 
 namespace pfa {
 
-#ifndef PFA_WIDE_OCC
-#define PFA_WIDE_OCC 1   // 0 = one workgroup per CU for every width (the first form of this kernel; A/B timing with tools/wide_variant_bench.py)
-#endif
 // Workgroups per CU.  A workgroup is one wave per SIMD, all four on the same tile behind two barriers per tile: nothing of its own
 // covers a wave's LDS round trips, barrier waits and the (VALU-only) loss.  Where the register budget allows, a second (third,
 // fourth) workgroup on the CU does: MS = 1 fits four (<= 128 registers), MS = 2 / 4 two (<= 256; at MS = 4 with the heads' A
 // fragments in LDS instead of registers and two hidden tiles per backward pass instead of four); MS = 8 needs the whole file.
 // (KKU = k-steps of the forward: MS KKU W1 fragments + 4 MS KTM dW1 accumulators set the budget; 64 full columns at MS = 4 do not fit twice.)
-__host__ __device__ constexpr int wide_wgs_per_cu(int ms, int kku) { return !PFA_WIDE_OCC ? 1 : ms == 1 ? 4 : (ms <= 4 && ms * kku <= 52) ? 2 : 1; }
-#ifndef PFA_WIDE_8W
-#define PFA_WIDE_8W 1    // 0 = hidden 512 as four waves of MS = 8 (the first form; A/B timing)
-#endif
-#ifndef PFA_WIDE_DEDUP
-#define PFA_WIDE_DEDUP 1 // 0 = in the eight-wave form every wave computes the loss for itself (A/B timing)
-#endif
+__host__ __device__ constexpr int wide_wgs_per_cu(int ms, int kku) { return ms == 1 ? 4 : (ms <= 4 && ms * kku <= 52) ? 2 : 1; }
 // Waves per workgroup (NW) and hidden tiles per wave (MS = hidden / (16 NW)).  Hidden 512 at four waves needs the whole register file
 // (MS = 8: 459-498 registers), so nothing covers its latencies either; as EIGHT waves of MS = 4 — two per SIMD, <= 256 registers each,
 // the same budget as hidden 256 with two workgroups per CU — each SIMD has a second wave to issue from.  The two waves of a SIMD would
 // both spend the loss's VALU time (MFMA and VALU do not overlap on a SIMD: DESIGN.md 3.4), so only waves 0-3 compute it and hand
 // d loss / d out to their SIMD partner (wave w + 4) through LDS behind a third barrier (DEDUP).
-__host__ __device__ constexpr int wide_waves(int hidden, int kku) { return PFA_WIDE_8W && hidden == 512 && 4 * kku <= 52 ? 8 : 4; }
+__host__ __device__ constexpr int wide_waves(int hidden, int kku) { return hidden == 512 && 4 * kku <= 52 ? 8 : 4; }
 __host__ __device__ constexpr int wide_waves_per_simd(int ms, int kku, int nw) { return nw == 8 ? 2 : wide_wgs_per_cu(ms, kku); }
 __host__ __device__ constexpr bool wide_heads_in_lds(int ms, int kku, int nw) { return ms == 4 && wide_waves_per_simd(ms, kku, nw) > 1; }
 __host__ __device__ constexpr bool wide_small_pass(int ms, int kku, int nw) { return wide_waves_per_simd(ms, kku, nw) > 1; }
-#ifndef PFA_WIDE_STREAMS
-#define PFA_WIDE_STREAMS 1   // 0 = the co-resident tile streams of a CU as separate workgroups, each with its own gradient partial (round 5)
-#endif
 // Tile STREAMS per workgroup.  Where a CU holds two (four) four-wave groups, they used to be two (four) workgroups — and every
 // workgroup leaves its own gradient partial: 512 x 67.6 KB at hidden 256 = 34.6 MB written per launch and read again by the reduce
 // launch, as much as the minibatch's rows themselves (2.07x the algorithmic traffic by the counters, VERDICT rounds 4 and 5).  As ONE
 // workgroup of ST four-wave streams — each stream its own tiles, X / hidden / dout patches and partial out^T, all streams behind
 // the same two barriers per tile — the streams add their accumulators up through LDS at the end (fixed order) and the workgroup
 // writes ONE partial: half (a quarter) of the partial traffic in both launches.
-__host__ __device__ constexpr int wide_streams(int ms, int kku, int nw) { return PFA_WIDE_STREAMS && nw == 4 ? wide_wgs_per_cu(ms, kku) : 1; }
+__host__ __device__ constexpr int wide_streams(int ms, int kku, int nw) { return nw == 4 ? wide_wgs_per_cu(ms, kku) : 1; }
 
 // One workgroup partial (floats), fragment order.  MT = H / 16 hidden tiles, KTM 16-column tiles of dW1 on MFMA (+ COL: the
 // one trailing column 16 KTM, for rows of 16 KTM + 1 real columns like the 7x7 grid's 49).
@@ -112,7 +101,7 @@ __global__ void __launch_bounds__(64 * NW * wide_streams(MS, KKU, NW), wide_wave
                                                                     const double *adv_stats /* [nmb][2] */, double global_rows, float *partials) {
     using LD = WideLds<DP, MS, KKU, NW, KTM>;
     constexpr int XS = LD::XS, V = DP / 4, HSW = LD::HSW, DSW = LD::DSW, MT = NW * MS, ST = LD::ST;
-    constexpr bool DEDUP = PFA_WIDE_DEDUP && NW == 8;
+    constexpr bool DEDUP = NW == 8;
     constexpr bool LATE_PREFETCH = NW == 8;
     static_assert(NW == 4 || NW == 8, "waves per workgroup");
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
@@ -124,7 +113,7 @@ __global__ void __launch_bounds__(64 * NW * wide_streams(MS, KKU, NW), wide_wave
     const int lane = lane_id(), c = lane & 15, g = lane >> 4;
     const int a = pv.a;
     // (eight-wave form with DEDUP: wave w + 4 reads the dout patch its SIMD partner w wrote)
-    float *hs = lds + LD::kHs + wv * 16 * HSW, *ds = lds + LD::kDs + ((PFA_WIDE_DEDUP && NW == 8) ? (wv & 3) : wv) * 16 * DSW;
+    float *hs = lds + LD::kHs + wv * 16 * HSW, *ds = lds + LD::kDs + (DEDUP ? (wv & 3) : wv) * 16 * DSW;
     float *wbt = lds_all + LD::kWb, *b1s = lds_all + LD::kB1;
     constexpr bool W2L = wide_heads_in_lds(MS, KKU, NW);
     float *wat = lds_all + LD::kWa;
@@ -487,17 +476,22 @@ __global__ void __launch_bounds__(64 * kWideRedSl) ppo_wide_reduce_kernel(const 
     }
 }
 
-static int wide_shape(const pfa_mlp_view *p, int *ktm, bool *col, int *kku) {
+// What the row width decides: k-steps of the forward, 16-column tiles of dW1 on MFMA, + the trailing column.  COL is the 7x7 grid's
+// 49 columns on a 64-float row: three 16-column tiles on MFMA + the one trailing column on the VALU, 13 k-steps.
+constexpr int wide_kku(int dp, bool col) { return col ? 13 : dp / 4; }
+constexpr int wide_ktm(int dp, bool col) { return col ? 3 : dp / 16; }
+struct WideShape {
+    int kku, ktm;
+    bool col;
+};
+static int wide_shape(const pfa_mlp_view *p, WideShape *s) {
     PFA_REQUIRE(p && p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv, "ppo.wide: null view / tensor");
     PFA_REQUIRE(p->hidden == 64 || p->hidden == 256 || p->hidden == 512, "ppo.wide: hidden %d is not one of 64 / 256 / 512 (128: pfa_ppo_mlp_grad)", p->hidden);
     PFA_REQUIRE(p->obs_stride == 16 || p->obs_stride == 32 || p->obs_stride == 64, "ppo.wide: obs_stride %d is not one of 16 / 32 / 64", p->obs_stride);
     PFA_REQUIRE(p->obs_dim >= 1 && p->obs_dim <= p->obs_stride && p->ldw1 >= p->obs_dim, "ppo.wide: obs_dim %d / ldw1 %d out of range", p->obs_dim, p->ldw1);
     PFA_REQUIRE(p->num_actions >= 1 && p->num_actions <= 15, "ppo.wide: num_actions must be in 1..15 (got %d)", p->num_actions);
-    // the 7x7 grid's 49 columns on a 64-float row: three 16-column tiles on MFMA + the one trailing column on the VALU, 13 k-steps
-    const bool grid49 = p->obs_stride == 64 && p->obs_dim == 49;
-    *ktm = grid49 ? 3 : p->obs_stride / 16;
-    *col = grid49;
-    *kku = grid49 ? 13 : p->obs_stride / 4;
+    const bool col = p->obs_stride == 64 && p->obs_dim == 49;
+    *s = WideShape{wide_kku(p->obs_stride, col), wide_ktm(p->obs_stride, col), col};
     return 0;
 }
 static int wide_streams_of(int hidden, int kku) {
@@ -513,29 +507,46 @@ static int wide_grid(int64_t mb_rows, int hidden, int kku) {   // one workgroup 
     return (int)(wgs < slots ? (wgs < 1 ? 1 : wgs) : slots);
 }
 
+// The gradient launch of one (row width, COL, hidden) combination; the shape constants come from the same functions wide_shape uses.
+template <int DP, bool COL, int H, typename... Args>
+static int wide_launch(int grid, hipStream_t stream, Args... args) {
+    constexpr int KKU = wide_kku(DP, COL), KTM = wide_ktm(DP, COL), NW = wide_waves(H, KKU), MS = H / (16 * NW), ST = wide_streams(MS, KKU, NW);
+    constexpr size_t lds_bytes = (size_t)WideLds<DP, MS, KKU, NW, KTM>::kFloats * sizeof(float);
+    static bool attr_set = false;
+    if (!attr_set) {
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)ppo_wide_grad_kernel<DP, KKU, KTM, COL, MS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds_bytes));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((ppo_wide_grad_kernel<DP, KKU, KTM, COL, MS, NW>), dim3(grid), dim3(64 * NW * ST), lds_bytes, stream, args...);
+    return 0;
+}
+template <int H, typename... Args>
+static int wide_launch_rows(int obs_stride, bool col, Args... args) {
+    if (col) return wide_launch<64, true, H>(args...);
+    return obs_stride == 64 ? wide_launch<64, false, H>(args...) : obs_stride == 32 ? wide_launch<32, false, H>(args...) : wide_launch<16, false, H>(args...);
+}
+
 }  // namespace pfa
 
 using namespace pfa;
 
 extern "C" size_t pfa_ppo_wide_workspace_bytes(const pfa_mlp_view *view) {
-    int ktm, kku;
-    bool col;
-    if (wide_shape(view, &ktm, &col, &kku)) return 0;
-    return align_up((size_t)wide_slots(view->hidden, kku) * wide_layout(view->hidden, ktm, col).kCount * sizeof(float), 256);
+    WideShape s;
+    if (wide_shape(view, &s)) return 0;
+    return align_up((size_t)wide_slots(view->hidden, s.kku) * wide_layout(view->hidden, s.ktm, s.col).kCount * sizeof(float), 256);
 }
 
 extern "C" int pfa_ppo_wide_supported(const pfa_mlp_view *view) {
-    int ktm, kku;
-    bool col;
-    return wide_shape(view, &ktm, &col, &kku) == 0 ? 1 : 0;
+    WideShape s;
+    return wide_shape(view, &s) == 0 ? 1 : 0;
 }
 
 extern "C" int pfa_ppo_wide_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb, const pfa_mlp_view *params, const pfa_mlp_view *grads,
                                  float *tail16, const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, void *workspace,
                                  pfa_stream_t stream) {
-    int ktm, kku;
-    bool col;
-    if (int rc = wide_shape(params, &ktm, &col, &kku)) return rc;
+    WideShape s;
+    if (int rc = wide_shape(params, &s)) return rc;
     PFA_REQUIRE(exp && hp && grads && tail16 && workspace, "ppo.wide: null argument");
     PFA_REQUIRE(grads->w1 && grads->b1 && grads->w2 && grads->b2 && grads->wv && grads->bv && grads->ldw1 >= params->obs_dim,
                 "ppo.wide: the gradient view must name the same six tensors");
@@ -548,38 +559,20 @@ extern "C" int pfa_ppo_wide_grad(const pfa_experience *exp, int64_t batch_rows, 
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     const MlpView pv{params->w1, params->ldw1, params->obs_dim, params->b1, params->w2, params->b2, params->wv, params->bv, params->num_actions, params->hidden};
     float *partials = (float *)workspace;
-    const int grid = wide_grid(mbs, params->hidden, kku);
+    const int grid = wide_grid(mbs, params->hidden, s.kku);
     {
         ScopedKernelTimer timer("ppo_wide_grad", (hipStream_t)stream);
-#define PFA_WIDE_LAUNCH(DPV, KKUV, KTMV, COLV, HV)                                                                                        \
-    {                                                                                                                                    \
-        constexpr int NWV = wide_waves(HV, KKUV), MSV = HV / (16 * NWV);                                                                 \
-        constexpr size_t lds_bytes = (size_t)WideLds<DPV, MSV, KKUV, NWV, KTMV>::kFloats * sizeof(float);                                \
-        constexpr int STV = wide_streams(MSV, KKUV, NWV);                                      \
-        static bool attr_set = false;                                                                                                    \
-        if (!attr_set) {                                                                                                                 \
-            PFA_CHECK_HIP(hipFuncSetAttribute((const void *)ppo_wide_grad_kernel<DPV, KKUV, KTMV, COLV, MSV, NWV>,                        \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                              \
-            attr_set = true;                                                                                                             \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((ppo_wide_grad_kernel<DPV, KKUV, KTMV, COLV, MSV, NWV>), dim3(grid), dim3(64 * NWV * STV), lds_bytes,                \
-                           (hipStream_t)stream, *exp, map, (long long)mbs, pv, *hp, adv_stats, (double)global_mb_rows, partials);        \
-    }
-#define PFA_WIDE_DP(HV)                                                                \
-    if (col) PFA_WIDE_LAUNCH(64, 13, 3, true, HV)                                      \
-    else if (params->obs_stride == 64) PFA_WIDE_LAUNCH(64, 16, 4, false, HV)           \
-    else if (params->obs_stride == 32) PFA_WIDE_LAUNCH(32, 8, 2, false, HV)            \
-    else PFA_WIDE_LAUNCH(16, 4, 1, false, HV)
-        switch (params->hidden) {
-            case 64: PFA_WIDE_DP(64) break;
-            case 256: PFA_WIDE_DP(256) break;
-            default: PFA_WIDE_DP(512) break;
-        }
-#undef PFA_WIDE_DP
-#undef PFA_WIDE_LAUNCH
+        auto launch = [&](auto hidden) {
+            return wide_launch_rows<decltype(hidden)::value>(params->obs_stride, s.col, grid, (hipStream_t)stream, *exp, map, (long long)mbs, pv, *hp,
+                                                             adv_stats, (double)global_mb_rows, partials);
+        };
+        using std::integral_constant;
+        const int rc = params->hidden == 64 ? launch(integral_constant<int, 64>{}) : params->hidden == 256 ? launch(integral_constant<int, 256>{})
+                                                                                                           : launch(integral_constant<int, 512>{});
+        if (rc) return rc;
         PFA_LAUNCH_CHECK();
     }
-    const WideLayout L = wide_layout(params->hidden, ktm, col);
+    const WideLayout L = wide_layout(params->hidden, s.ktm, s.col);
     ScopedKernelTimer timer("ppo_wide_reduce", (hipStream_t)stream);
     hipLaunchKernelGGL(ppo_wide_reduce_kernel, dim3((L.kCount + 63) / 64), dim3(64 * kWideRedSl), 0, (hipStream_t)stream, partials, grid, L,
                        params->obs_dim, params->num_actions, params->hidden, (float *)grads->w1, grads->ldw1, (float *)grads->b1, (float *)grads->w2,

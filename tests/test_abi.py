@@ -54,6 +54,38 @@ def test_weight_gradient_workspace_never_shrinks_with_more_rows(L):
     assert L.pfa_gemm_tn_workspace_bytes(128, 160, 131072) > 0 and L.pfa_gemm_tn_workspace_bytes(128, 24, 4096) == 0
 
 
+# recorded from the library built at commit 39f66d4, before the host dispatch of csrc/ppo_update.hip went through one shape table
+_MFMA_PER_TILE_39F66D4 = {   # (obs_dim, obs_stride): values for num_actions 1, 8, 11, 12, 15
+    (16, 16): [160] * 5, (13, 16): [160] * 5, (32, 32): [224] * 5, (29, 32): [224] * 5,
+    (64, 64): [352] * 5, (61, 64): [352] * 5, (49, 64): [280, 280, 280, 288, 288], (50, 64): [328] * 5, (52, 64): [328] * 5, (53, 64): [352] * 5,
+    (96, 96): [480] * 5, (93, 96): [480] * 5, (128, 128): [608] * 5, (125, 128): [608] * 5}
+_WORKSPACE_BYTES_39F66D4 = {   # obs_stride: bytes for num_minibatches 1, 4, 64
+    16: [4351488, 4354304, 4415744], 32: [6449152, 6451456, 6512896], 64: [21285888, 21287168, 21348608],
+    96: [14839808, 14840064, 14901504], 128: [19035136, 19035136, 19095808]}
+
+
+def test_gradient_shape_helpers_return_what_they_returned_at_39f66d4(L):
+    """pfa_ppo_mlp_grad_mfma_per_tile and pfa_ppo_workspace_bytes read their numbers off the shape table of csrc/ppo_update.hip
+    (with_grad_shape / GradShape).  The literals were recorded from the library of the parent commit 39f66d4, where both were
+    hand-kept restatements of the launch's choice; the bench shape (49, 64, 8) is 12*8 + 11*8 + 3*4*8 = 280 by that formula.  The
+    workspace is deliberately sized for the untrimmed layout (and, on 64-float rows, for the bf16 form's grid): the trimmed 7x7
+    shape (obs_dim 49) gets the same bytes as a full 64-column row."""
+    assert set(s for _, s in _MFMA_PER_TILE_39F66D4) == set(_WORKSPACE_BYTES_39F66D4) == {16, 32, 64, 96, 128}
+    for (obs_dim, stride), want in _MFMA_PER_TILE_39F66D4.items():
+        got = [L.pfa_ppo_mlp_grad_mfma_per_tile(obs_dim, stride, a) for a in (1, 8, 11, 12, 15)]
+        assert got == want, (obs_dim, stride, got, want)
+    assert L.pfa_ppo_mlp_grad_mfma_per_tile(49, 64, 8) == 12 * 8 + 11 * 8 + 3 * 4 * 8
+    assert L.pfa_ppo_mlp_grad_mfma_per_tile(49, 64, 0) == 0 and L.pfa_ppo_mlp_grad_mfma_per_tile(49, 64, 16) == 0      # num_actions outside 1..15
+    assert L.pfa_ppo_mlp_grad_mfma_per_tile(48, 48, 8) == 0                                                             # no such row width
+    for stride, want in _WORKSPACE_BYTES_39F66D4.items():
+        for obs_dim in {stride, 49 if stride == 64 else stride}:
+            got = []
+            for nmb in (1, 4, 64):
+                hp = _lib.PpoHparams(0.1, 0.1, 0.5, 0.01, 1, 1, nmb, 16)
+                got.append(L.pfa_ppo_workspace_bytes(C.byref(_lib.MlpDims(obs_dim, stride, 128, 8, 0)), 131072 * nmb, C.byref(hp)))
+            assert got == want, (obs_dim, stride, got, want)
+
+
 def test_no_cpu_fallback():
     """The product path must fail loudly without a GPU."""
     import torch

@@ -253,19 +253,23 @@ def test_native_data_parallel_path_single_rank_equals_plain():
         np.testing.assert_allclose(l1[k], l0[k], rtol=1e-5, atol=1e-7)
 
 
-@pytest.mark.parametrize('n,horizon,nmb,nt', [(256, 64, 4, 1), (64, 32, 2, 2), (4096, 32, 4, 1)])
-def test_one_launch_reduce_and_adam_equals_the_two_kernel_form_bit_for_bit(monkeypatch, n, horizon, nmb, nt):
+@pytest.mark.parametrize('n,horizon,nmb,nt,d', [
+    pytest.param(256, 64, 4, 1, 3, id='256-64-4-1'), pytest.param(64, 32, 2, 2, 3, id='64-32-2-2'), pytest.param(4096, 32, 4, 1, 3, id='4096-32-4-1'),
+    # the other row widths (obs_stride 16 / 32 / 96 / 128): each pairs its own gradient instantiation with both reduce forms
+    (64, 32, 2, 2, 1), (64, 32, 2, 2, 2), (64, 32, 2, 2, 4), (64, 32, 2, 2, 5)])
+def test_one_launch_reduce_and_adam_equals_the_two_kernel_form_bit_for_bit(monkeypatch, n, horizon, nmb, nt, d):
     """pfa_ppo_mlp_train sums the workgroup partials, takes the clip norm and applies Adam in ONE launch (grid barrier inside,
     csrc/ppo_update.hip ppo_reduce_adam_kernel); PFA_FUSED_ADAM=0 runs the two kernels pfa_ppo_mlp_grad + pfa_adam_clip_step are
     made of.  Same arithmetic in the same order: parameters, moments, gradient bucket and losses must be identical bits, over
-    several updates (the barrier's generation word carries over between launches)."""
+    several updates (the barrier's generation word carries over between launches).  Both forms read the partials the gradient
+    launch left, so a reduce kernel paired with another shape's layout shows here, at every row width."""
     from pufferlib_amd import clean_pufferl
     hp = [2.5e-3, 0.99, 0.95, 0.1, 0.5, 0.1, 0.5, 0.01]
     runs = []
     for fused in ('1', '0'):
         monkeypatch.setenv('PFA_FUSED_ADAM', fused)
         torch.manual_seed(11)
-        vec, pol = _make(n, nt=nt)
+        vec, pol = _make(n, d, nt)
         data = clean_pufferl.create(_config(n, horizon, n * horizon // nmb, 16, 3, n * horizon * 8, hp, seed=9), vec, pol)
         for _ in range(3):
             clean_pufferl.evaluate(data)
