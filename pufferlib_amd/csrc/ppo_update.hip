@@ -126,9 +126,30 @@ __device__ int g_trace_tiles = 0;
         if (g_trace && blockIdx.x == 0 && lane == 0 && (j) < g_trace_tiles)                                     \
             g_trace[((size_t)wv * g_trace_tiles + (j)) * 8 + (k)] = __builtin_amdgcn_s_memtime();               \
     } while (0)
+// tools/probe_handoff.py: 100 MHz wall-clock stamps (one clock for the whole device, so workgroups and the two launches compare) of
+// the hand-off of the partials, thread 0 of every workgroup: [row][8], rows 0.. the gradient launch, kHandoffReduceRow.. the reduce launch
+__device__ unsigned long long *g_handoff = nullptr;
+constexpr int kHandoffReduceRow = 512;
+#define PFA_HSTAMP(row, k)                                                                                      \
+    do {                                                                                                        \
+        if (g_handoff && threadIdx.x == 0) g_handoff[(size_t)(row) * 8 + (k)] = wall_clock64();                 \
+    } while (0)
+#define PFA_HSTAMP_DRAINED(row, k)   /* after everything this wave has in flight has landed */                  \
+    do {                                                                                                        \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                             \
+        PFA_HSTAMP(row, k);                                                                                     \
+    } while (0)
 #else
 #define PFA_STAMP(j, k) do { } while (0)
+#define PFA_HSTAMP(row, k) do { } while (0)
+#define PFA_HSTAMP_DRAINED(row, k) do { } while (0)
 #endif
+
+// The gradient launch writes every partial once and the reduce launch reads it once, from other CUs: the store carries the
+// streaming hint (the lines do not stay behind dirty in the writer's L2 for the end of the launch to write back; measured on the
+// bench shape, -0.5 us on the gradient launch, +0.5 on the reduce launch, -0.6 per optimizer step end to end).  The same hint on
+// the loads of the reduce kernels made them 0.5 us slower and is not taken (lab notebook, section 14).
+__device__ __forceinline__ void handoff_store(f32x4 *p, f32x4 v) { __builtin_nontemporal_store(v, p); }
 
 // ABL: ablation mask for tools/probe_grad.py (-DPFA_PROBES builds only; the product always runs ABL = 0):
 //   1 skip the loss math   2 skip the consumer's dW1 MFMAs   4 skip the forward MFMAs
@@ -471,6 +492,7 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
         }
         __syncthreads();  // alpha_J: matches the consumer's trailing barrier pair
         __syncthreads();  // beta_J
+        PFA_HSTAMP(blockIdx.x, 0);   // last tile done
 
         // ---- epilogue: producers own dW2v, db2v, stats --------------------------------------------------------------
 #pragma unroll
@@ -669,49 +691,77 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
             __syncthreads();
         }
     }
-    float *dst = partials + (size_t)blockIdx.x * NL::kCount;
-    if constexpr (kQuad) {
-        for (int i = threadIdx.x; i < NL::kCount; i += kGradThreads)
-            dst[i] = (lds[i] + lds[2 * NL::kCount + i]) + (lds[NL::kCount + i] + lds[3 * NL::kCount + i]);
-    } else {
-        for (int i = threadIdx.x; i < NL::kCount; i += kGradThreads) dst[i] = lds[i] + lds[NL::kCount + i];
+    PFA_HSTAMP(blockIdx.x, 1);   // reduction buffers written
+    // The partial leaves in 16-byte pieces: four consecutive entries per thread, one ds_read_b128 per reduction buffer and one
+    // global_store_dwordx4 (every CU's store tail at once is bound by the number of store instructions, not by their bytes).  The
+    // sum per entry is the one it always was: (p0 + p2) + (p1 + p3).
+    static_assert(NL::kCount % 4 == 0, "a partial is whole 16-byte pieces: every workgroup's partial and every reduction buffer starts 16-byte aligned");
+    constexpr int kCount4 = NL::kCount / 4;
+    const f32x4 *red4 = reinterpret_cast<const f32x4 *>(lds);
+    f32x4 *dst4 = reinterpret_cast<f32x4 *>(partials + (size_t)blockIdx.x * NL::kCount);
+    for (int i = threadIdx.x; i < kCount4; i += kGradThreads) {
+        f32x4 o;
+        if constexpr (kQuad) o = (red4[i] + red4[2 * kCount4 + i]) + (red4[kCount4 + i] + red4[3 * kCount4 + i]);
+        else o = red4[i] + red4[kCount4 + i];
+        handoff_store(dst4 + i, o);
     }
+    PFA_HSTAMP_DRAINED(blockIdx.x, 2);   // partial stored
 }
 
 // Fixed-order sum of the workgroup partials (native layout) + scatter into the flat gradient layout, plus one
-// f64 partial of sum(g^2) per block for the gradient-norm clip.  Block = 64 native slots x 4 slices of the
-// partial index; 16 independent loads in flight per thread.
+// f64 partial of sum(g^2) per block for the gradient-norm clip.  Block = 64 native slots x 16 slices of the
+// partial index; 16 independent 16-byte loads in flight per thread.
 constexpr int kRedSl = 16;   // slices of the partial index per slot
-// (16 slices: 163 workgroups x 16 waves, every thread's 16 loads in flight at once — the reduction is a latency chain over the
-// L2-resident partials, and 4 waves per workgroup left most SIMDs without a wave to hide it)
-template <int DP, int KTM = DP / 16, bool COL = false, bool PERM = false>
-__global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_kernel(const float *partials, int nparts, int a, int obs_dim, float *grads,
-                                                                double *norm_partials) {
-    using NL = NativeLayout<DP, KTM, COL>;
-    __shared__ float sh[kRedSl][64];
-    __shared__ double shd[kRedSl][64];   // the loss-sum slots are carried in f64
-    const int ql = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int q = blockIdx.x * 64 + ql;
-    float acc = 0.0f;
-    double dacc = 0.0;
-    if (q < NL::kCount) {
+// (16 slices, every thread's 16 loads in flight at once.  Stamped, the load phase is 64 KB per CU at the rate one CU reads from beyond
+// its L2, ~13 B/cycle: ~2 us that neither wider loads nor more waves shorten; tools/probe_handoff.py, lab notebook section 14)
+// A lane of the summing phase owns FOUR consecutive native slots: one 16-byte load per partial, so the 64 entries of a workgroup
+// take 16 lanes per slice and the workgroup is 16 lanes x 16 slices = 4 waves (a quarter of the waves to ramp up and of the load
+// instructions of the 4-byte form, the same bytes in flight per workgroup).  The four components are summed separately, each in the
+// order a one-slot lane would: slice sl takes partials sl, sl + 16, ... in sequence; the slices meet in the fixed tree of the tail.
+constexpr int kRedLanes = 16;                       // lanes per slice
+constexpr int kRedThreads = kRedLanes * kRedSl;     // workgroup of both reduce kernels; wave 0 runs the tail, one entry per lane
+static_assert(4 * kRedLanes == 64 && kRedThreads >= 128, "64 entries per workgroup; wave 1 writes the padding zeros");
+template <class NL>
+__device__ __forceinline__ void reduce_slices(const float *partials, int nparts, float (*sh)[64], double (*shd)[64]) {
+    static_assert(NL::kCount % 4 == 0 && NL::kStats % 4 == 0, "a lane's four slots are inside the partial, and loss sums, together");
+    constexpr int kCount4 = NL::kCount / 4;
+    const int l = threadIdx.x % kRedLanes, sl = threadIdx.x / kRedLanes;
+    const int q4 = blockIdx.x * 64 + 4 * l;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    double dacc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (q4 < NL::kCount) {
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(partials + q4);
         for (int i0 = sl; i0 < nparts; i0 += 16 * kRedSl) {
-            float v[16];
+            f32x4 v[16];
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const int i = i0 + kRedSl * u;
-                v[u] = i < nparts ? partials[(size_t)i * NL::kCount + q] : 0.0f;
+                v[u] = i < nparts ? src[(size_t)i * kCount4] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             }
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 acc += v[u];
-                if (q >= NL::kStats) dacc += (double)v[u];
+                if (q4 >= NL::kStats) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) dacc[k] += (double)v[u][k];
+                }
             }
         }
     }
-    sh[sl][ql] = acc;
-    shd[sl][ql] = dacc;
+    *reinterpret_cast<f32x4 *>(&sh[sl][4 * l]) = acc;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) shd[sl][4 * l + k] = dacc[k];
+}
+template <int DP, int KTM = DP / 16, bool COL = false, bool PERM = false>
+__global__ void __launch_bounds__(kRedThreads) ppo_reduce_kernel(const float *partials, int nparts, int a, int obs_dim, float *grads,
+                                                                double *norm_partials) {
+    using NL = NativeLayout<DP, KTM, COL>;
+    __shared__ __attribute__((aligned(16))) float sh[kRedSl][64];
+    __shared__ double shd[kRedSl][64];   // the loss-sum slots are carried in f64
+    reduce_slices<NL>(partials, nparts, sh, shd);
     __syncthreads();
+    const int ql = threadIdx.x & 63, sl = threadIdx.x >> 6;   // from here on a wave is 64 entries: wave 0 the tail, wave 1 the padding
+    const int q = blockIdx.x * 64 + ql;
     const MlpOffsets off = mlp_offsets(DP, a);
     if (sl == 1) {
         // W1 columns no partial slot covers (k-tiles >= KTM past the COL column: observation padding): their gradient is zero by
@@ -823,12 +873,13 @@ struct AdamArgs {
     double *log_out10;
 };
 template <int DP, int KTM, bool COL, bool PERM, bool DIST>
-__global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_adam_kernel(const float *partials, int nparts, int a, int obs_dim, float *grads,
+__global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const float *partials, int nparts, int a, int obs_dim, float *grads,
                                                                      GridWords gw, AdamArgs ad, LlArgs ll) {
     using NL = NativeLayout<DP, KTM, COL>;
-    __shared__ float sh[kRedSl][64];
+    __shared__ __attribute__((aligned(16))) float sh[kRedSl][64];
     __shared__ double shd[kRedSl][64];   // the loss-sum slots are carried in f64
-    const int ql = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    PFA_HSTAMP(kHandoffReduceRow + blockIdx.x, 0);   // entry
+    const int ql = threadIdx.x & 63, sl = threadIdx.x >> 6;   // past the partial sums a wave is 64 entries: wave 0 the tail, wave 1 the padding
     const int q = blockIdx.x * 64 + ql;
     // data parallel: one lane of the launch reads this rank's status word (host-pinned: a PCIe round trip) and publishes it to the peers
     // NOW, under the partial sums; the peers' words are collected behind the norm hand-off's publish further down (p2p_ll.hpp)
@@ -837,25 +888,8 @@ __global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_adam_kernel(const floa
     if constexpr (DIST) {
         if (status_lane) status_mine = ll_status_push(ll);
     }
-    float acc = 0.0f;
-    double dacc = 0.0;
-    if (q < NL::kCount) {
-        for (int i0 = sl; i0 < nparts; i0 += 16 * kRedSl) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int i = i0 + kRedSl * u;
-                v[u] = i < nparts ? partials[(size_t)i * NL::kCount + q] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                acc += v[u];
-                if (q >= NL::kStats) dacc += (double)v[u];
-            }
-        }
-    }
-    sh[sl][ql] = acc;
-    shd[sl][ql] = dacc;
+    reduce_slices<NL>(partials, nparts, sh, shd);
+    PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 1);   // this wave's partial loads landed and summed
     __syncthreads();
     const MlpOffsets off = mlp_offsets(DP, a);
     if (sl == 1) {   // observation-padding columns of W1 no partial slot covers: gradient zero by definition (see ppo_reduce_kernel)
@@ -902,6 +936,7 @@ __global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_adam_kernel(const floa
             lo = (float)(t2 - (double)hi);
         }
     }
+    PFA_HSTAMP(kHandoffReduceRow + blockIdx.x, 2);   // past the barrier and the tree: this entry's sum is known
     // this entry's parameter and moments: in flight across the exchange and the barrier
     float p_i = 0.0f, m_i = 0.0f, v_i = 0.0f;
     if (p >= 0) {
@@ -937,6 +972,7 @@ __global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_adam_kernel(const floa
         const unsigned half = ql == 0 ? (unsigned)bits : (unsigned)(bits >> 32);
         __hip_atomic_store(gw.words + 2 * blockIdx.x + ql, ((unsigned long long)gw.gen << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 3);   // norm word published (and the entry's gradient, parameter and moments here)
     if constexpr (DIST) {   // the ranks' status words ride the exchange: this workgroup's norm piece is out, nobody waits for this lane
         if (status_lane) ll_status_wait(ll, status_mine);
     }
@@ -981,6 +1017,7 @@ __global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_adam_kernel(const floa
         for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
         tot += ss;
     }
+    PFA_HSTAMP(kHandoffReduceRow + blockIdx.x, 4);   // every workgroup's norm word seen
     const float clip = clip_factor(tot, ad.max_grad_norm);
     if (p >= 0) {
         adam_element(p_i, m_i, v_i, s, clip, ad.neg_step_size, ad.bc2_sqrt, ad.beta1, ad.beta2, ad.eps);
@@ -1005,6 +1042,7 @@ __global__ void __launch_bounds__(64 * kRedSl) ppo_reduce_adam_kernel(const floa
             }
         }
     }
+    PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 5);   // exit: Adam's stores out
 }
 
 // Per-minibatch advantage sums (f64).  grid = (chunks, nmb); deterministic two-stage reduction.
@@ -1281,6 +1319,7 @@ static int launch_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb
     PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->advantages && exp->returns && params && grads &&
                     workspace,
                 "ppo.grad: null buffer");
+    PFA_REQUIRE(((uintptr_t)workspace & 15) == 0, "ppo.grad: the workspace must be 16-byte aligned (the partials travel in 16-byte pieces)");
     PFA_REQUIRE(!hp->norm_adv || adv_stats, "ppo.grad: norm_adv needs adv_stats");
     const int64_t mbs = batch_rows / hp->num_minibatches;
     PFA_REQUIRE(mbs % 16 == 0, "ppo.grad: minibatch_size must be a multiple of 16 (got %lld)", (long long)mbs);
@@ -1325,7 +1364,7 @@ extern "C" int pfa_ppo_mlp_grad(const pfa_experience *exp, int64_t batch_rows, i
     ScopedKernelTimer timer2("ppo_reduce", (hipStream_t)stream);
     with_grad_shape(dims, [&](auto s) {   // the layout of the partials belongs to the shape that wrote them
         using S = decltype(s);
-        hipLaunchKernelGGL((ppo_reduce_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm>), dim3(S::kReduceGrid), dim3(64 * kRedSl), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((ppo_reduce_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm>), dim3(S::kReduceGrid), dim3(kRedThreads), 0, (hipStream_t)stream,
                            partials, grid, dims->num_actions, dims->obs_dim, grads, normp);
     });
     PFA_LAUNCH_CHECK();
@@ -1409,7 +1448,7 @@ static bool coresident(K kernel, int blocks) {
     int per_cu = 0, cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return false;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, 64 * kRedSl, 0) != hipSuccess) return false;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, kRedThreads, 0) != hipSuccess) return false;
     return (long long)per_cu * cus >= blocks;
 }
 static bool reduce_adam_coresident(const pfa_mlp_dims *dims, bool dist) {
@@ -1448,7 +1487,7 @@ static int launch_reduce_adam(const pfa_mlp_dims *dims, int nmb, int grid, float
     ScopedKernelTimer timer("ppo_reduce_adam", stream);
     with_grad_shape(dims, [&](auto s) {   // the layout of the partials belongs to the shape that wrote them
         using S = decltype(s);
-        const dim3 g(S::kReduceGrid), b(64 * kRedSl);
+        const dim3 g(S::kReduceGrid), b(kRedThreads);
         if (ll) hipLaunchKernelGGL((ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, true>), g, b, 0, stream, partials, grid,
                                    dims->num_actions, dims->obs_dim, grads, gw, ad, *ll);
         else hipLaunchKernelGGL((ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, false>), g, b, 0, stream, partials, grid,
@@ -1563,6 +1602,10 @@ extern "C" int pfa_probe_bf16_trace(unsigned long long *buf, int tiles) {   // t
 #endif
 #ifdef PFA_PROBES
 // Probe-only entry (tools/probe_grad.py): same launch as pfa_ppo_mlp_grad for obs_stride 64 with an ablation mask.
+extern "C" int pfa_probe_set_handoff(unsigned long long *buf) {   // tools/probe_handoff.py: [kHandoffReduceRow + reduce grid][8], or null
+    PFA_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_handoff), &buf, sizeof(buf)));
+    return 0;
+}
 extern "C" int pfa_probe_set_trace(unsigned long long *buf, int tiles) {
     PFA_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &buf, sizeof(buf)));
     PFA_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_tiles), &tiles, sizeof(tiles)));
