@@ -705,16 +705,14 @@ int pfa_dist_info(int64_t *out8);
  *                    Flatten from NHWC rows (IC, IH, IW of the operand = the flattened tensor); bias_out (nullable) (+)= the column
  *                    sums of D (the bias gradient, from the same pass over D); split over rows, f64 reduction of the splits
  *                    (deterministic).  workspace >= pfa_igemm_weights_workspace_bytes(M, K, N).
- * pfa_colsum:        out[n] (+)= sum_m D[m][n] on its own, f64, deterministic.
  * pfa_cnn_pack_conv / pfa_cnn_transpose: torch weights -> the matrices the loaders' patch orders need (after every optimizer
  *                    step): forward B [OC][k] (u8_order 1: torch's own order, weights / 255; 2: mode 4's order, weights / 255), dX B [S*S][IC][(KH/S)(KW/S)*OC] (nullable);
  *                    Linear [N][K] -> [K][N] (B of its dX).
  * pfa_cnn_heads_sample / pfa_cnn_heads_loss (csrc/cnn_heads.hip): decode_actions + sample_logits, and the PPO loss with its
- *                    gradients w.r.t. the head outputs [rows][16] and the hidden vector [rows][hidden] (512 for the unsuffixed entry points), for a chunk
- *                    [q0, q0 + rows) of minibatch mb; loss_pairs16 as in pfa_ppo_mlp_grad (accumulate != 0 adds chunks up).
- *                    pfa_cnn_heads_sample_w / pfa_cnn_heads_loss_w: the same kernels at hidden width `hidden` (a multiple of 16 up to
- *                    1024; the unsuffixed entry points are these at 512).  Up to 15 actions; wider action sets go through
- *                    pfa_heads_rows_* below on head outputs computed by pfa_igemm_rows.
+ *                    gradients w.r.t. the head outputs [rows][16] and the hidden vector [rows][hidden] (`hidden` a multiple of 16 up to
+ *                    1024), for a chunk [q0, q0 + rows) of minibatch mb; loss_pairs16 as in pfa_ppo_mlp_grad (accumulate != 0 adds
+ *                    chunks up).  Up to 15 actions; wider action sets go through pfa_heads_rows_* below on head outputs computed by
+ *                    pfa_igemm_rows.
  * pfa_cnn_gather_frames: the frames of such a chunk, contiguous.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -738,8 +736,6 @@ int pfa_igemm_get_products(void);
 size_t pfa_igemm_weights_workspace_bytes(int64_t M, int32_t K, int32_t N);
 int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *D, int32_t ldd, int32_t N, float *out,
                       int32_t perm, int32_t accumulate, float *bias_out, void *workspace, pfa_stream_t stream);
-size_t pfa_colsum_workspace_bytes(int32_t N);
-int pfa_colsum(const float *D, int64_t M, int32_t N, int32_t ldd, float *out, int32_t accumulate, void *workspace, pfa_stream_t stream);
 int pfa_cnn_pack_conv(const float *w, const pfa_igemm_operand *geom, int32_t u8_order, float *fwd, float *dx, pfa_stream_t stream);
 int pfa_igemm_rows_add(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
                        int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd,
@@ -752,21 +748,14 @@ int pfa_cnn_transpose(const float *w, int32_t N, int32_t K, float *out, pfa_stre
 /* Linear(channels*hw, N) behind nn.Flatten of an NCHW tensor (models.py:133) for NHWC activations: perm_out [N][K'] with the
  * columns in NHWC order (B of the forward), t_out [K'][N] (B of dX); pfa_igemm_weights perm 4 undoes the order for dW. */
 int pfa_cnn_pack_fc(const float *w, int32_t N, int32_t channels, int32_t hw, float *perm_out, float *t_out, pfa_stream_t stream);
-int pfa_cnn_heads_sample(const float *h, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+int pfa_cnn_heads_sample(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
                          const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
                          int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream);
-int pfa_cnn_heads_sample_w(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
-                           const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
-                           int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream);
 size_t pfa_cnn_heads_loss_workspace_bytes(void);
-int pfa_cnn_heads_loss(const float *h, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
+int pfa_cnn_heads_loss(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
                        const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
                        const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
                        float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream);
-int pfa_cnn_heads_loss_w(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
-                         const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
-                         const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
-                         float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream);
 int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t batch_rows, int32_t mb, const pfa_ppo_hparams *hp,
                           int64_t q0, int64_t rows, uint8_t *out, pfa_stream_t stream);
 

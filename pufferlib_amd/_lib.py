@@ -102,6 +102,21 @@ class IgemmOperand(C.Structure):
                 ('sc', C.c_int32), ('sy', C.c_int32), ('sx', C.c_int32), ('frame_bytes', C.c_int32)]   # modes 4 / 6 (strided uint8 frames) only
 
 
+# operand modes and epilogues of pfa_igemm_rows / pfa_igemm_rows_add / pfa_igemm_weights, numbered as in include/pufferlib_amd.h
+MODE_DENSE, MODE_IM2COL_F32, MODE_IM2COL_U8, MODE_COL2IM, MODE_IM2COL_U8S, MODE_IM2COL_PAD, MODE_IM2COL_U8P = range(7)
+EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_MASK, EPI_BIAS_ADD, EPI_BIAS_ADD_RELU, EPI_MASK_ADD = range(7)
+
+
+def operand(mode, tensor, lda=0, geom=(0,) * 9, strides=(0,) * 4, relu_in=0):
+    """geom: (IC, IH, IW, OC, OH, OW, KH, KW, S).  strides (modes 4 and 6 only): (sc, sy, sx, frame_bytes) — byte strides of channel /
+    row / column of a frame, bytes per frame.  relu_in (mode 5 only): 1 = the operand is relu(tensor)."""
+    return IgemmOperand(mode, relu_in, tensor.data_ptr(), lda, *geom, *strides)
+
+
+def round_up(x, a):
+    return (x + a - 1) // a * a
+
+
 class MlpDims(C.Structure):
     _fields_ = [('obs_dim', C.c_int32), ('obs_stride', C.c_int32), ('hidden', C.c_int32), ('num_actions', C.c_int32),
                 ('heads', C.c_uint32)]       # MultiDiscrete head sizes, 4 bits each (0 = one Discrete head)
@@ -280,8 +295,6 @@ _SIGNATURES = {
     'pfa_igemm_rows': (C.c_int, [C.POINTER(IgemmOperand), C.c_int64, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, P, C.c_int32, P]),
     'pfa_igemm_weights_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     'pfa_igemm_weights': (C.c_int, [C.POINTER(IgemmOperand), C.c_int64, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, P, P]),
-    'pfa_colsum_workspace_bytes': (C.c_size_t, [C.c_int32]),
-    'pfa_colsum': (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, P, P]),
     'pfa_cnn_pack_conv': (C.c_int, [P, C.POINTER(IgemmOperand), C.c_int32, P, P, P]),
     'pfa_igemm_rows_add': (C.c_int, [C.POINTER(IgemmOperand), C.c_int64, C.c_int32, P, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, P, P, C.c_int32, P,
                                      C.c_int32, P]),
@@ -290,13 +303,10 @@ _SIGNATURES = {
     'pfa_maxpool3s2_backward': (C.c_int, [P, P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P]),
     'pfa_cnn_transpose': (C.c_int, [P, C.c_int32, C.c_int32, P, P]),
     'pfa_cnn_pack_fc': (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
-    'pfa_cnn_heads_sample': (C.c_int, [P, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
-    'pfa_cnn_heads_sample_w': (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
-    'pfa_cnn_heads_loss_w': (C.c_int, [P, C.c_int32, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P, P, C.c_int32,
-                                       C.POINTER(PpoHparams), P, C.c_int64, P, P, P, C.c_int32, P, P]),
-    'pfa_cnn_heads_loss_workspace_bytes': (C.c_size_t, []),
-    'pfa_cnn_heads_loss': (C.c_int, [P, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P, P, C.c_int32,
+    'pfa_cnn_heads_sample': (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
+    'pfa_cnn_heads_loss': (C.c_int, [P, C.c_int32, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P, P, C.c_int32,
                                      C.POINTER(PpoHparams), P, C.c_int64, P, P, P, C.c_int32, P, P]),
+    'pfa_cnn_heads_loss_workspace_bytes': (C.c_size_t, []),
     'pfa_cnn_gather_frames': (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, C.POINTER(PpoHparams), C.c_int64, C.c_int64, P, P]),
     'pfa_p2p_alloc': (C.c_int, [C.c_int64, C.c_int32, P]),
     'pfa_p2p_open': (C.c_int, [P, C.c_int32, C.c_int32]),

@@ -44,7 +44,7 @@ from . import dist as pdist
 from .cleanrl import Policy, RecurrentPolicy
 from .models import FlatParams  # noqa: F401  (re-exported: callers of create() type-check the trainer's parameter buffer against it)
 from .namespace import namespace
-from .vector import Bandit, Frames, Memory, Multiagent, Spaces, Squared, Stochastic, Synthetic, _DeviceVecEnv
+from .vector import Frames, Spaces, Squared, Stochastic, _DeviceVecEnv
 
 
 def seed_everything(seed, torch_deterministic=True):
@@ -80,6 +80,23 @@ class HipAdam:
 
     def zero_grad(self):
         pass
+
+    def step(self, grads, max_grad_norm, loss_acc, loss_scale, norm_partials=None):
+        """clip_grad_norm_ + optimizer.step() (clean_pufferl.py:240-244) on the flat buffer.  grads: the gradient and, behind it, the 8
+        loss sums as float pairs (added to loss_acc, scaled by loss_scale).  norm_partials: the caller's f64 buffer that takes
+        sum(g^2) in as many pieces as it has entries (the number fixes the split, and with it the bits of the norm); None: the Adam
+        launch takes the norm itself."""
+        L, stream, fp = _lib.lib(), _lib.stream_handle(), self.fp
+        n = 0 if norm_partials is None else norm_partials.numel()
+        if n:
+            _lib.check(L.pfa_sumsq_partials(_lib.ptr(grads), fp.count, _lib.ptr(norm_partials), n, stream), 'sumsq')
+        self.step_count += 1
+        g = self.param_groups[0]
+        _lib.check(L.pfa_adam_clip_step(
+            _lib.ptr(fp.flat), _lib.ptr(grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), fp.count,
+            float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), self.step_count,
+            float(max_grad_norm), 1.0, C.c_void_p(grads.data_ptr() + 4 * fp.count),
+            _lib.ptr(loss_acc), loss_scale, _lib.ptr(norm_partials), n, stream), 'adam')
 
     def state_dict(self):
         m, v = self.fp.split(self.exp_avg), self.fp.split(self.exp_avg_sq)
@@ -407,10 +424,23 @@ def _make_hparams(config, experience):
                            experience.num_minibatches, int(config.bptt_horizon))
 
 
+STEPWISE, FUSED_LSTM, FUSED_MLP = 'stepwise', 'fused recurrent', 'fused MLP'
+
+
+def rollout_form(vecenv_class, gen_engine, lstm_engine, mlp_view):
+    """Which rollout evaluate() runs for a device vecenv class and the engines create() built: one persistent kernel where the env
+    class declares one for the policy kind (ROLLOUT_LSTM, fused_rollout_mlp), else policy step + store + send per step."""
+    if gen_engine:       # GEMM-path policy: its Default(64 / 256 / 512) shapes share the Squared rollout kernel (general.tile_view),
+        #                  whose state layout is Squared's own: exactly that class, not a subclass
+        return FUSED_MLP if mlp_view and vecenv_class is Squared else STEPWISE
+    if lstm_engine:
+        return FUSED_LSTM if vecenv_class.ROLLOUT_LSTM is not None else STEPWISE
+    return FUSED_MLP if vecenv_class.fused_rollout_mlp is not None else STEPWISE
+
+
 @utils.profile
 def evaluate(data):
     config, profile, experience, vecenv = data.config, data.profile, data.experience, data.vecenv
-    L = _lib.lib()
     fp = data.flat_params
     if data.host_bridge is not None:      # host vecenv: the reference's recv/forward/store/send loop (hostpath.py)
         from . import hostpath
@@ -426,88 +456,79 @@ def evaluate(data):
             noise = noise.to(device=vecenv.device, dtype=torch.float32).contiguous()
             assert tuple(noise.shape) == (T, N, fp.num_actions), noise.shape
         key = _lib.NoiseKey(policy.noise_seed, policy.noise_step)
-    wide_view = data.gen_engine.mlp_view if data.gen_engine is not None else None
-    if data.gen_engine is not None and not (wide_view is not None and type(vecenv) is Squared):
-        # a policy shape outside the fused kernels: policy step + store + send per step
+    gen = data.gen_engine
+    form = rollout_form(type(vecenv), gen is not None, data.lstm_engine is not None, gen is not None and gen.mlp_view is not None)
+    if form == STEPWISE:     # no fused kernel for this (env, policy) pair: policy step + store + send per step, still no host sync per step
         with profile.eval_forward:
             _rollout_stepwise(data, noise, T, N)
         return _finish_evaluate(data, N, T)
-    if isinstance(vecenv, (Memory, Synthetic)) and data.lstm_engine is not None:   # recurrent policy: one persistent kernel
-        with profile.env:
-            if hasattr(vecenv, 'ensure_tape'):
-                vecenv.ensure_tape(T)
-        with profile.eval_forward:
+    prefetch = vecenv.PREFETCH        # Squared: the next rollout's reset tape and action noise are drawn on the side stream under this one
+    with profile.env:
+        if hasattr(vecenv, 'ensure_tape'):
+            vecenv.ensure_tape(T)                # waits for the prefetch (vecenv.tape_event); draws nothing when it covered T
+        if prefetch:
+            start_point = torch.cuda.Event()
+            start_point.record(torch.cuda.current_stream())   # everything before this rollout (incl. the rollout before it) is done
+    with profile.eval_forward:           # one persistent kernel for all T steps, either policy
+        if form == FUSED_LSTM:
             data.lstm_engine.rollout(T, noise, policy.noise_seed, policy.noise_step, vecenv.env_offset)
             vecenv.sends += T
-        return _finish_evaluate(data, N, T)
-    if isinstance(vecenv, (Memory, Bandit, Multiagent, Spaces, Synthetic)):   # no fused kernel for these (env, policy) pairs: protocol-level pieces, still no host sync per step
-        with profile.eval_forward:
-            _rollout_stepwise(data, noise, T, N)
-        return _finish_evaluate(data, N, T)
-    if isinstance(vecenv, Stochastic):    # no reset tape: the env draws no random numbers
-        with profile.eval_forward:
-            vecenv.fused_rollout_mlp(fp, experience, noise, key, _lib.stream_handle())
-        return _finish_evaluate(data, N, T)
-    with profile.env:
-        main = torch.cuda.current_stream()
-        vecenv.ensure_tape(T)                    # waits for the prefetch (vecenv.tape_event); draws nothing when it covered T
-        start_point = torch.cuda.Event()
-        start_point.record(main)                 # everything before this rollout (incl. the rollout before it) is done
-    with profile.eval_forward:           # one persistent kernel for all T steps, either policy
-        if data.lstm_engine is not None:
-            data.lstm_engine.rollout(T, noise, policy.noise_seed, policy.noise_step, vecenv.env_offset)
         else:
-            if noise is None:
-                # the whole rollout's Philox action noise in one launch (same numbers the kernel would draw in place): keeps 40
-                # quarter-rate integer multiplies per step off the rollout's dependent chain; the kernel prefetches a step ahead.
-                # The stream is a pure function of (seed, step, global env index), so the previous evaluate() already drew THIS
-                # rollout's numbers on the side stream behind the reset tape (vecenv.tape_event, waited for in ensure_tape above,
-                # covers them); anything that moved the stream position in between (policy(obs) calls, a checkpoint load, another
-                # seed) fails the tag comparison and the numbers are drawn here, on the compute stream, as before.
-                tag = (int(policy.noise_seed), int(policy.noise_step), T, N, int(fp.num_actions), int(vecenv.env_offset))
-                pre = getattr(data, '_noise_next', None)
-                if pre is not None and pre[0] == tag:
-                    noise = pre[1]
-                else:
-                    noise = _noise_buffer(data, T, N, fp.num_actions, vecenv.device)
-                    _lib.check(L.pfa_philox_exp_noise(_lib.ptr(noise), T, N, fp.num_actions, C.byref(key), vecenv.env_offset,
-                                                      _lib.stream_handle()), 'philox_exp_noise')
-                data._noise_next = None
-                data._noise_cur = noise
-            if wide_view is not None:     # Default(hidden 64 / 256 / 512): the same persistent kernel, W1 fragments of that width in registers
-                _lib.check(L.pfa_rollout_mlp_view_squared(
-                    _lib.ptr(vecenv.state), C.byref(vecenv.cfg), C.byref(wide_view), C.byref(experience.c),
-                    _lib.ptr(noise), C.byref(key), vecenv.env_offset, _lib.ptr(vecenv.obs_buf), _lib.ptr(vecenv.rewards),
-                    _lib.ptr(vecenv.terminals_u8), _lib.ptr(vecenv.truncations_u8), _lib.ptr(vecenv.masks_u8),
-                    _lib.stream_handle()), 'rollout')
+            if prefetch and noise is None:
+                noise = _rollout_noise(data, key, T, N)
+            if gen is not None:      # Default(hidden 64 / 256 / 512): the same persistent kernel, W1 fragments of that width in registers
+                vecenv.fused_rollout_mlp(fp, experience, noise, key, _lib.stream_handle(), view=gen.mlp_view)
             else:
-                _lib.check(L.pfa_rollout_mlp_squared(
-                    _lib.ptr(vecenv.state), C.byref(vecenv.cfg), _lib.ptr(fp.flat), C.byref(fp.dims), C.byref(experience.c),
-                    _lib.ptr(noise), C.byref(key), vecenv.env_offset, _lib.ptr(vecenv.obs_buf), _lib.ptr(vecenv.rewards),
-                    _lib.ptr(vecenv.terminals_u8), _lib.ptr(vecenv.truncations_u8), _lib.ptr(vecenv.masks_u8),
-                    _lib.stream_handle()), 'rollout')
-    with profile.env:
-        vecenv.sends += T
-        # The tape does not depend on actions: draw the NEXT rollout's reset rounds on the side stream while THIS
-        # rollout runs (its small workgroup co-resides with the rollout's).  The ring slots it writes belong to the
-        # rollout before this one, which `start_point` guarantees has finished.
-        if 3 * (vecenv._rounds_needed(T) + 1) <= vecenv.tape_rounds:
-            with torch.cuda.stream(data.tape_stream):
-                data.tape_stream.wait_event(start_point)
-                vecenv.ensure_tape(T)
-                if data.noise is None and data.lstm_engine is None and getattr(data, '_noise_cur', None) is not None:
-                    # ... and the NEXT rollout's action noise (16.8 MB of writes that depend on nothing but the stream position),
-                    # into the buffer the running rollout is not reading
-                    nxt = _noise_buffer(data, T, N, fp.num_actions, vecenv.device, other_than=data._noise_cur)
-                    nkey = _lib.NoiseKey(policy.noise_seed, policy.noise_step + T)
-                    _lib.check(L.pfa_philox_exp_noise(_lib.ptr(nxt), T, N, fp.num_actions, C.byref(nkey), vecenv.env_offset,
-                                                      _lib.stream_handle()), 'philox_exp_noise (prefetch)')
-                    data._noise_next = ((int(policy.noise_seed), int(policy.noise_step) + T, T, N, int(fp.num_actions),
-                                         int(vecenv.env_offset)), nxt)
-                ev = torch.cuda.Event()
-                ev.record(data.tape_stream)
-                vecenv.tape_event = ev           # the vecenv owns it: send()/async_reset() outside evaluate() wait on it too
+                vecenv.fused_rollout_mlp(fp, experience, noise, key, _lib.stream_handle())
+    if prefetch:
+        with profile.env:
+            _prefetch_next_rollout(data, start_point, T, N)
     return _finish_evaluate(data, N, T)
+
+
+def _rollout_noise(data, key, T, N):
+    """The whole rollout's Philox action noise in one launch (same numbers the kernel would draw in place): keeps 40 quarter-rate
+    integer multiplies per step off the rollout's dependent chain; the kernel prefetches a step ahead.  The stream is a pure function
+    of (seed, step, global env index), so the previous evaluate() already drew THIS rollout's numbers on the side stream behind the
+    reset tape (vecenv.tape_event, waited for in ensure_tape, covers them); anything that moved the stream position in between
+    (policy(obs) calls, a checkpoint load, another seed) fails the tag comparison and the numbers are drawn here, on the compute
+    stream, as before."""
+    vecenv, policy, fp = data.vecenv, data.policy, data.flat_params
+    tag = (int(policy.noise_seed), int(policy.noise_step), T, N, int(fp.num_actions), int(vecenv.env_offset))
+    pre = getattr(data, '_noise_next', None)
+    if pre is not None and pre[0] == tag:
+        noise = pre[1]
+    else:
+        noise = _noise_buffer(data, T, N, fp.num_actions, vecenv.device)
+        _lib.check(_lib.lib().pfa_philox_exp_noise(_lib.ptr(noise), T, N, fp.num_actions, C.byref(key), vecenv.env_offset,
+                                                   _lib.stream_handle()), 'philox_exp_noise')
+    data._noise_next = None
+    data._noise_cur = noise
+    return noise
+
+
+def _prefetch_next_rollout(data, start_point, T, N):
+    """The tape does not depend on actions: draw the NEXT rollout's reset rounds on the side stream while THIS rollout runs (its small
+    workgroup co-resides with the rollout's).  The ring slots it writes belong to the rollout before this one, which `start_point`
+    guarantees has finished."""
+    vecenv, policy, fp = data.vecenv, data.policy, data.flat_params
+    if 3 * (vecenv._rounds_needed(T) + 1) > vecenv.tape_rounds:
+        return
+    with torch.cuda.stream(data.tape_stream):
+        data.tape_stream.wait_event(start_point)
+        vecenv.ensure_tape(T)
+        if data.noise is None and data.lstm_engine is None and getattr(data, '_noise_cur', None) is not None:
+            # ... and the NEXT rollout's action noise (16.8 MB of writes that depend on nothing but the stream position),
+            # into the buffer the running rollout is not reading
+            nxt = _noise_buffer(data, T, N, fp.num_actions, vecenv.device, other_than=data._noise_cur)
+            nkey = _lib.NoiseKey(policy.noise_seed, policy.noise_step + T)
+            _lib.check(_lib.lib().pfa_philox_exp_noise(_lib.ptr(nxt), T, N, fp.num_actions, C.byref(nkey), vecenv.env_offset,
+                                                       _lib.stream_handle()), 'philox_exp_noise (prefetch)')
+            data._noise_next = ((int(policy.noise_seed), int(policy.noise_step) + T, T, N, int(fp.num_actions),
+                                 int(vecenv.env_offset)), nxt)
+        ev = torch.cuda.Event()
+        ev.record(data.tape_stream)
+        vecenv.tape_event = ev           # the vecenv owns it: send()/async_reset() outside evaluate() wait on it too
 
 
 def _noise_buffer(data, T, N, A, device, other_than=None):
@@ -588,11 +609,8 @@ def _finish_evaluate(data, N, T):
             # data parallel: the episode statistics and what the sharded GAE needs from the other ranks (csrc/gae.hip: the first rows
             # of the shards that follow — all from every rank's own rows, complete once its rollout is) ride ONE all-reduce
             st = _publish_gae(data, st)
-        elif data.native_dp:
-            _lib.check(L.pfa_dist_all_reduce_f64(_lib.ptr(st), st.numel(), _lib.stream_handle()), 'stats all-reduce')
-        elif data.world_size > 1:
-            dist, _, _ = _dist()
-            dist.all_reduce(st)
+        else:
+            _all_reduce(data, st, 'stats all-reduce')
         # The sums ride a pinned buffer behind the rollout; the host waits for them here (default) or, with
         # PFA_LAZY_READBACK=1, when the dicts are first read — at the latest at the end of the next evaluate() (readback.py).
         stats, infos = readback.LazyDict(data._rb_eval), readback.LazyDict(data._rb_eval)
@@ -673,10 +691,14 @@ def _launch_gae_sums(data):
         _lib.ptr(data.workspace), _lib.stream_handle()), 'gae_sums')
 
 
-def _all_reduce_f64(data, buf, what):
+def _all_reduce(data, buf, what):
+    """Sum of an f32 or f64 device buffer over the ranks, in place, on the compute stream: the library's collective where create()
+    opened it (peer path or RCCL; the 1-rank communicator of force_native_dp too), else torch.distributed's; nothing on one rank."""
     if data.native_dp:
-        _lib.check(_lib.lib().pfa_dist_all_reduce_f64(_lib.ptr(buf), buf.numel(), _lib.stream_handle()), what)
-    else:
+        L = _lib.lib()
+        fn = L.pfa_dist_all_reduce_f64 if buf.dtype == torch.float64 else L.pfa_dist_all_reduce_f32
+        _lib.check(fn(_lib.ptr(buf), buf.numel(), _lib.stream_handle()), what)
+    elif data.world_size > 1:
         _dist()[0].all_reduce(buf)
 
 
@@ -704,7 +726,7 @@ def _publish_gae(data, extra=None):
     else:
         _lib.check(L.pfa_gae_shard_publish(*rows, B, gamma, lam, _lib.ptr(data.gae_ws), _lib.ptr(extra), n_extra, _lib.ptr(buf), rank, world,
                                            stream), 'gae publish')
-    _all_reduce_f64(data, buf, 'stats + gae all-reduce')
+    _all_reduce(data, buf, 'stats + gae all-reduce')
     data._gae_published = (H, n_extra)
     return buf[:n_extra]
 
@@ -750,9 +772,9 @@ def _finish_gae(data):
             _lib.check(L.pfa_train_ev_sums(C.byref(ex.c), B, ex.num_envs, ev4, _lib.ptr(data.workspace), stream), 'train_ev_sums')
         data.loss_acc.zero_()
     if with_ev:
-        _all_reduce_f64(data, data.dp_sums, 'adv + ev all-reduce')
+        _all_reduce(data, data.dp_sums, 'adv + ev all-reduce')
     elif config.norm_adv:
-        _all_reduce_f64(data, data.adv_stats, 'adv all-reduce')
+        _all_reduce(data, data.adv_stats, 'adv all-reduce')
 
 
 @utils.profile
@@ -806,10 +828,7 @@ def train(data):
                 with profile.train_forward:
                     eng.update(mb, hp, data.adv_stats, global_mb_rows, data.grads, B)
                 with profile.learn:
-                    if data.native_dp:
-                        _lib.check(L.pfa_dist_all_reduce_f32(_lib.ptr(data.grads), data.grads.numel(), stream), 'grad all-reduce')
-                    elif world > 1:
-                        dist.all_reduce(data.grads)
+                    _all_reduce(data, data.grads, 'grad all-reduce')
                     eng.clip_adam(data.grads, opt, config.max_grad_norm, data.loss_acc, loss_scale)
             if config.target_kl is not None:
                 if float(data.grads[fp.count + 8:fp.count + 10].double().sum().item()) / global_mb_rows > config.target_kl:
@@ -843,13 +862,7 @@ def train(data):
             with profile.learn:
                 if world > 1:
                     dist.all_reduce(data.grads)      # one flat bucket per optimizer step (RCCL over xGMI)
-                opt.step_count += 1
-                g = opt.param_groups[0]
-                _lib.check(L.pfa_adam_clip_step(
-                    _lib.ptr(fp.flat), _lib.ptr(data.grads), _lib.ptr(opt.exp_avg), _lib.ptr(opt.exp_avg_sq), fp.count,
-                    float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), opt.step_count,
-                    float(config.max_grad_norm), 1.0, C.c_void_p(data.grads.data_ptr() + 4 * fp.count),
-                    _lib.ptr(data.loss_acc), loss_scale, None, 0, stream), 'adam')
+                opt.step(data.grads, config.max_grad_norm, data.loss_acc, loss_scale)
         epochs_run += 1
         if config.target_kl is not None:
             # approx_kl of the LAST minibatch of this epoch (clean_pufferl.py:256-258) — needs a sync
@@ -882,12 +895,7 @@ def train(data):
                 yp, ad = data.arrival_values.double(), experience.advantages.double()
                 yt = ad + yp
                 data.log_sums[6:10] = torch.stack([yt.sum(), (yt * yt).sum(), ad.sum(), (ad * ad).sum()])
-            if data.native_dp:                                  # explained variance over the GLOBAL batch, like the (global) losses
-                _lib.check(L.pfa_dist_all_reduce_f64(C.c_void_p(data.log_sums.data_ptr() + 6 * 8), 4, stream), 'ev all-reduce')
-            elif world > 1:
-                ev_sums = data.log_sums[6:10].clone()
-                dist.all_reduce(ev_sums)
-                data.log_sums[6:10] = ev_sums
+            _all_reduce(data, data.log_sums[6:10], 'ev all-reduce')   # explained variance over the GLOBAL batch, like the (global) losses
         # one D2H of 10 f64 (the one sync of train(); with PFA_LAZY_READBACK=1 data.losses fills in when it is first read)
         Bg = B * world
 

@@ -17,15 +17,10 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import EPI_BIAS, EPI_BIAS_RELU, EPI_MASK, MODE_COL2IM, MODE_DENSE, MODE_IM2COL_F32, MODE_IM2COL_U8, MODE_IM2COL_U8S
+from ._lib import operand as _operand
 
 F32 = torch.float32
-MODE_DENSE, MODE_IM2COL_F32, MODE_IM2COL_U8, MODE_COL2IM, MODE_IM2COL_U8S = 0, 1, 2, 3, 4
-EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_MASK = 0, 1, 2, 3
-
-
-def _operand(mode, tensor, lda=0, geom=(0,) * 9, strides=(0,) * 4):
-    """strides (mode 4 only): (sc, sy, sx, frame_bytes) — byte strides of channel / row / column of a frame, bytes per frame."""
-    return _lib.IgemmOperand(mode, 0, tensor.data_ptr(), lda, *geom, *strides)
 
 
 class ConvLayer:
@@ -213,11 +208,11 @@ class Engine:
             m = min(self.chunk, n - lo)
             h = self.forward(frames[lo:lo + m], m)
             nz = None if noise is None else noise[lo:lo + m]
-            _lib.check(L.pfa_cnn_heads_sample_w(_lib.ptr(h), self.hidden, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']),
-                                                _lib.ptr(v['value_fn.bias']), self.cp.num_actions, _lib.ptr(nz), C.byref(key), row_offset + lo,
-                                                _lib.ptr(actions[lo:lo + m]), _lib.ptr(logprob[lo:lo + m]),
-                                                None if entropy is None else _lib.ptr(entropy[lo:lo + m]), _lib.ptr(value[lo:lo + m]),
-                                                _lib.stream_handle()), 'cnn_heads_sample')
+            _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(h), self.hidden, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']),
+                                              _lib.ptr(v['value_fn.bias']), self.cp.num_actions, _lib.ptr(nz), C.byref(key), row_offset + lo,
+                                              _lib.ptr(actions[lo:lo + m]), _lib.ptr(logprob[lo:lo + m]),
+                                              None if entropy is None else _lib.ptr(entropy[lo:lo + m]), _lib.ptr(value[lo:lo + m]),
+                                              _lib.stream_handle()), 'cnn_heads_sample')
 
     # ------------------------------------------------------------------------------------------------------------- update
     def backward(self, frames, m, dh_pre, gv, acc):
@@ -238,17 +233,7 @@ class Engine:
 
     def clip_adam(self, grads, opt, max_grad_norm, loss_acc, loss_scale):
         """clip_grad_norm_ + optimizer.step() (clean_pufferl.py:240-244) on the flat buffer; the packed weight forms go stale."""
-        L = _lib.lib()
-        stream = _lib.stream_handle()
-        cp = self.cp
-        n = self.norm_partials.numel()
-        _lib.check(L.pfa_sumsq_partials(_lib.ptr(grads), cp.count, _lib.ptr(self.norm_partials), n, stream), 'sumsq')
-        opt.step_count += 1
-        g = opt.param_groups[0]
-        _lib.check(L.pfa_adam_clip_step(_lib.ptr(cp.flat), _lib.ptr(grads), _lib.ptr(opt.exp_avg), _lib.ptr(opt.exp_avg_sq), cp.count,
-                                        float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), opt.step_count,
-                                        float(max_grad_norm), 1.0, C.c_void_p(grads.data_ptr() + 4 * cp.count), _lib.ptr(loss_acc), loss_scale,
-                                        _lib.ptr(self.norm_partials), n, stream), 'adam')
+        opt.step(grads, max_grad_norm, loss_acc, loss_scale, self.norm_partials)
         self.version += 1
 
     def update_from(self, exp_c, obs_u8, B, mb, hp, adv_stats, global_mb_rows, grads):
@@ -264,7 +249,7 @@ class Engine:
             acc = ci > 0
             _lib.check(L.pfa_cnn_gather_frames(_lib.ptr(obs_u8), self.frame_bytes, B, mb, C.byref(hp), q0, m, _lib.ptr(self.frames), stream), 'gather')
             h = self.forward(self.frames, m)
-            _lib.check(L.pfa_cnn_heads_loss_w(_lib.ptr(h), self.hidden, C.byref(exp_c), B, mb, q0, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']),
+            _lib.check(L.pfa_cnn_heads_loss(_lib.ptr(h), self.hidden, C.byref(exp_c), B, mb, q0, m, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']),
                                             _lib.ptr(v['value_fn.weight']), _lib.ptr(v['value_fn.bias']), cp.num_actions, C.byref(hp),
                                             _lib.ptr(adv_stats), global_mb_rows, _lib.ptr(self.dout), _lib.ptr(self.dh), _lib.ptr(tail),
                                             1 if acc else 0, _lib.ptr(self.ws_loss), stream), 'cnn_heads_loss')

@@ -8,8 +8,7 @@
 // 16 lanes per row (lane lo = head output lo), the row's hidden vector in LDS, head weights in LDS (padded rows: conflict-free),
 // the 16-lane log-softmax / arg-max pieces shared with the MLP and LSTM policies (sampler.hpp), so all three sample and score
 // with identical arithmetic.  The hidden width is a template argument (512: the Atari binding, 128: crafter / dm_lab / butterfly) or, for
-// any other multiple of 16 up to 1024, a run-time argument of the same code (pfa_cnn_heads_sample_w / _loss_w; the LDS carve follows
-// the width).  More than 15 actions: the row kernels of csrc/general.hip on head outputs computed by pfa_igemm_rows.  VALU work: 2 x H x (A + 1) flop per row against ~56 MFLOP in the conv stack.
+// any other multiple of 16 up to 1024, a run-time argument of the same code (the LDS carve follows the width).  More than 15 actions: the row kernels of csrc/general.hip on head outputs computed by pfa_igemm_rows.  VALU work: 2 x H x (A + 1) flop per row against ~56 MFLOP in the conv stack.
 #include "common.hpp"
 #include "lane_ops.hpp"
 #include "mlp_tile.hpp"
@@ -18,7 +17,6 @@
 
 namespace pfa {
 
-constexpr int kCnnH = 512;        // the Atari width: pfa_cnn_heads_sample / _loss; the _w entry points carry the width
 constexpr int kCnnMaxH = 1024;    // LDS: 16 head rows of H + 1 floats and 16 hidden rows of H floats (129 KB at 1024, of 160 KB)
 
 struct CnnHeads {   // actor.weight [A][H], actor.bias [A], value_fn.weight [1][H], value_fn.bias [1] (torch layout), H = the hidden width
@@ -283,7 +281,7 @@ static int cnn_launch_loss(int H, unsigned grid, hipStream_t stream, const float
 
 using namespace pfa;
 
-extern "C" int pfa_cnn_heads_sample_w(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+extern "C" int pfa_cnn_heads_sample(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
                                     const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
                                     int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream) {
     PFA_REQUIRE(rows >= 0 && h && actor_w && actor_b && value_w && value_b && actions && logprob && value, "cnn.heads_sample: null buffer");
@@ -303,16 +301,9 @@ extern "C" int pfa_cnn_heads_sample_w(const float *h, int32_t hidden, int64_t ro
 #undef PFA_CNN_SAMPLE
 }
 
-extern "C" int pfa_cnn_heads_sample(const float *h, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
-                                    const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
-                                    int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream) {
-    return pfa_cnn_heads_sample_w(h, kCnnH, rows, actor_w, actor_b, value_w, value_b, num_actions, noise, key, row_offset, actions, logprob, entropy,
-                                  value, stream);
-}
-
 extern "C" size_t pfa_cnn_heads_loss_workspace_bytes(void) { return (size_t)1024 * 8 * sizeof(double); }
 
-extern "C" int pfa_cnn_heads_loss_w(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
+extern "C" int pfa_cnn_heads_loss(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
                                   const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
                                   const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
                                   float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream) {
@@ -335,14 +326,6 @@ extern "C" int pfa_cnn_heads_loss_w(const float *h, int32_t hidden, const pfa_ex
     hipLaunchKernelGGL(cnn_stats_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, (int)grid, loss_pairs16, (int)accumulate);
     PFA_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int pfa_cnn_heads_loss(const float *h, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
-                                  const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,
-                                  const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, float *dout, float *dh,
-                                  float *loss_pairs16, int32_t accumulate, void *workspace, pfa_stream_t stream) {
-    return pfa_cnn_heads_loss_w(h, kCnnH, exp, batch_rows, mb, q0, rows, actor_w, actor_b, value_w, value_b, num_actions, hp, adv_stats,
-                                global_mb_rows, dout, dh, loss_pairs16, accumulate, workspace, stream);
 }
 
 extern "C" int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t batch_rows, int32_t mb, const pfa_ppo_hparams *hp,

@@ -806,28 +806,6 @@ __global__ void __launch_bounds__(256) igemm_weights_reduce_kernel(const float *
     out[p] = (accumulate ? out[p] : 0.0f) + (float)s;
 }
 
-// Column sums on their own (a bias gradient without a weight gradient next to it): out[n] (+)= sum_m D[m][n]; two deterministic stages.
-constexpr int kIgColChunks = 256;
-__global__ void __launch_bounds__(256) ig_colsum_partial_kernel(const float *__restrict__ D, long long M, int N, int ldd, double *__restrict__ partial) {
-    const long long per = (M + kIgColChunks - 1) / kIgColChunks;
-    const long long lo = (long long)blockIdx.y * per, hi = lo + per < M ? lo + per : M;
-    const int n = blockIdx.x * 64 + (threadIdx.x & 63), sl = threadIdx.x >> 6;
-    __shared__ double sh[4][64];
-    double s = 0.0;
-    if (n < N)
-        for (long long m = lo + sl; m < hi; m += 4) s += (double)D[(size_t)m * ldd + n];
-    sh[sl][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (sl == 0 && n < N) partial[(size_t)blockIdx.y * N + n] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
-__global__ void __launch_bounds__(256) ig_colsum_final_kernel(const double *__restrict__ partial, int N, float *__restrict__ out, int accumulate) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    double s = 0.0;
-    for (int q = 0; q < kIgColChunks; ++q) s += partial[(size_t)q * N + n];
-    out[n] = (accumulate ? out[n] : 0.0f) + (float)s;
-}
-
 // Weight re-packing after an optimizer step.  Conv [OC][IC][KH][KW] -> forward B [OC][k] with k in the loader's patch order
 // (the uint8 first layer keeps torch's order and takes the / 255 of the observations), and dX B [phase][IC][(jy*JW + jx)*OC + oc] with
 // phase = py*S + px and kernel tap (ky, kx) = (py + jy*S, px + jx*S).
@@ -1244,19 +1222,6 @@ extern "C" int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t 
     const long long total = (long long)K * N + N;
     hipLaunchKernelGGL(igemm_weights_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, (hipStream_t)stream, partial, colpart, p.splits,
                        (int)K, (int)N, out, bias_out, (int)perm, A.g, (int)accumulate);
-    PFA_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" size_t pfa_colsum_workspace_bytes(int32_t N) { return (size_t)kIgColChunks * (size_t)N * sizeof(double); }
-
-extern "C" int pfa_colsum(const float *D, int64_t M, int32_t N, int32_t ldd, float *out, int32_t accumulate, void *workspace, pfa_stream_t stream) {
-    PFA_REQUIRE(D && out && workspace && M >= 1 && N >= 1 && ldd >= N, "colsum: bad arguments");
-    hipLaunchKernelGGL(ig_colsum_partial_kernel, dim3((N + 63) / 64, kIgColChunks), dim3(256), 0, (hipStream_t)stream, D, (long long)M, (int)N, (int)ldd,
-                       (double *)workspace);
-    PFA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ig_colsum_final_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const double *)workspace, (int)N, out,
-                       (int)accumulate);
     PFA_LAUNCH_CHECK();
     return 0;
 }

@@ -252,30 +252,130 @@ __global__ void __launch_bounds__(256) philox_exp_noise_kernel(float *out, long 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side.  The two kernels above take a Default policy in two descriptor forms: the flat parameter buffer of the 128-wide family
+// with its pfa_mlp_dims (hidden 128; rows of 16 / 32 / 64 / 96 / 128 floats; MultiDiscrete head masks in the standalone forward),
+// and a pfa_mlp_view of a module's own tensors (models.py:24-39 with hidden_size 64 / 128 / 256 / 512 — what
+// environments/classic_control, nethack / nmmo and atari's MLP heads use; rows of 16 / 32 / 64 floats, one Discrete head).  Both
+// resolve to a TilePolicy; one checker, one dispatch and one launcher per kernel serve both.
+// ---------------------------------------------------------------------------------------------
+struct TilePolicy {
+    MlpView pv;
+    int obs_dim, obs_stride;
+    uint32_t heads;
+};
+
+static int check_shape(bool flat, int hidden, int obs_dim, int obs_stride, int a, uint32_t heads) {
+    if (flat) {
+        PFA_REQUIRE(hidden == kHidden, "mlp: hidden must be %d (got %d)", kHidden, hidden);
+    } else {
+        PFA_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256 || hidden == 512, "mlp view: hidden %d is not one of 64/128/256/512", hidden);
+    }
+    PFA_REQUIRE(obs_stride == 16 || obs_stride == 32 || obs_stride == 64 || (flat && (obs_stride == 96 || obs_stride == 128)),
+                "mlp: obs_stride must be one of %s (got %d)", flat ? "16/32/64/96/128" : "16/32/64", obs_stride);
+    PFA_REQUIRE(obs_dim >= 1 && obs_dim <= obs_stride, "mlp: obs_dim %d out of range", obs_dim);
+    PFA_REQUIRE(a >= 1 && a <= 15, "mlp: num_actions must be in 1..15 (got %d)", a);
+    PFA_REQUIRE(heads == 0 || (flat && heads_count(heads, a) >= 1), "mlp: head sizes 0x%x do not sum to num_actions %d", heads, a);
+    return 0;
+}
 static int check_dims(const pfa_mlp_dims *d) {
     PFA_REQUIRE(d != nullptr, "mlp: null dims");
-    PFA_REQUIRE(d->hidden == kHidden, "mlp: hidden must be %d (got %d)", kHidden, d->hidden);
-    PFA_REQUIRE(d->obs_stride == 16 || d->obs_stride == 32 || d->obs_stride == 64 || d->obs_stride == 96 ||
-                    d->obs_stride == 128,
-                "mlp: obs_stride must be one of 16/32/64/96/128 (got %d)", d->obs_stride);
-    PFA_REQUIRE(d->obs_dim >= 1 && d->obs_dim <= d->obs_stride, "mlp: obs_dim %d out of range", d->obs_dim);
-    PFA_REQUIRE(d->num_actions >= 1 && d->num_actions <= 15, "mlp: num_actions must be in 1..15 (got %d)", d->num_actions);
-    PFA_REQUIRE(d->heads == 0 || heads_count(d->heads, d->num_actions) >= 1, "mlp: head sizes 0x%x do not sum to num_actions %d",
-                d->heads, d->num_actions);
+    return check_shape(true, d->hidden, d->obs_dim, d->obs_stride, d->num_actions, d->heads);
+}
+static int check_view(const pfa_mlp_view *p) {
+    PFA_REQUIRE(p != nullptr, "mlp view: null");
+    PFA_REQUIRE(p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv, "mlp view: null tensor");
+    PFA_REQUIRE(p->ldw1 >= p->obs_dim, "mlp view: obs_dim %d / ldw1 %d out of range", p->obs_dim, p->ldw1);
+    return check_shape(false, p->hidden, p->obs_dim, p->obs_stride, p->num_actions, 0);
+}
+static int policy_of_flat(const float *params, const pfa_mlp_dims *d, TilePolicy *out) {
+    if (int rc = check_dims(d)) return rc;
+    PFA_REQUIRE(params, "mlp: null parameter buffer");
+    *out = TilePolicy{mlp_view_of_flat(params, d->obs_stride, d->num_actions), d->obs_dim, d->obs_stride, d->heads};
+    return 0;
+}
+static int policy_of_view(const pfa_mlp_view *p, TilePolicy *out) {
+    if (int rc = check_view(p)) return rc;
+    *out = TilePolicy{MlpView{p->w1, p->ldw1, p->obs_dim, p->b1, p->w2, p->b2, p->wv, p->bv, p->num_actions, p->hidden}, p->obs_dim,
+                      p->obs_stride, 0};
     return 0;
 }
 
-// DP = observation row stride, KS = forward k-steps: the 7x7 grid's 49 columns need 13 of the 64-float row's 16 (rollout_tile.hpp)
-#define PFA_DISPATCH_DP(dims_, CALL)                                                                     \
-    if ((dims_)->obs_stride == 64 && (dims_)->obs_dim > 48 && (dims_)->obs_dim <= 52) {                  \
-        constexpr int DP = 64, KS = 13; CALL;                                                            \
-    } else switch ((dims_)->obs_stride) {                                                                \
-        case 16: { constexpr int DP = 16, KS = 4; CALL; } break;                                          \
-        case 32: { constexpr int DP = 32, KS = 8; CALL; } break;                                          \
-        case 64: { constexpr int DP = 64, KS = 16; CALL; } break;                                         \
-        case 96: { constexpr int DP = 96, KS = 24; CALL; } break;                                         \
-        default: { constexpr int DP = 128, KS = 32; CALL; } break;                                        \
+// DP = observation row stride, KS = forward k-steps: the 7x7 grid's 49 columns need 13 of the 64-float row's 16 (rollout_tile.hpp),
+// MW = hidden tiles per wave (hidden = 64 MW).  `launch` is called with the Tile of the policy's shape.
+template <int DP_, int KS_, int MW_>
+struct Tile {
+    static constexpr int DP = DP_, KS = KS_, MW = MW_;
+};
+template <int MW, class Launch>
+static void dispatch_stride(const TilePolicy &p, Launch launch) {
+    if (p.obs_stride == 64 && p.obs_dim > 48 && p.obs_dim <= 52) return launch(Tile<64, 13, MW>{});
+    switch (p.obs_stride) {
+        case 16: return launch(Tile<16, 4, MW>{});
+        case 32: return launch(Tile<32, 8, MW>{});
+        case 64: return launch(Tile<64, 16, MW>{});
     }
+    if constexpr (MW == kMW) {   // rows of 96 / 128 floats: the 128-wide form only (check_shape)
+        if (p.obs_stride == 96) return launch(Tile<96, 24, MW>{});
+        return launch(Tile<128, 32, MW>{});
+    }
+}
+template <class Launch>
+static void dispatch_tile(const TilePolicy &p, Launch launch) {
+    switch (p.pv.hidden) {
+        case 64: return dispatch_stride<1>(p, launch);
+        case 128: return dispatch_stride<2>(p, launch);
+        case 256: return dispatch_stride<4>(p, launch);
+        default: return dispatch_stride<8>(p, launch);
+    }
+}
+
+static int launch_forward_sample(const TilePolicy &p, const float *obs, int64_t rows, const float *noise, const pfa_noise_key *key,
+                                 int64_t row_offset, int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream) {
+    PFA_REQUIRE(rows >= 0, "mlp.forward: negative rows");
+    if (rows == 0) return 0;
+    PFA_REQUIRE(obs && actions && logprob && value, "mlp.forward: null buffer");
+    PFA_REQUIRE(noise || key, "mlp.forward: need an explicit noise tensor or a Philox key");
+    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
+    const int64_t tiles = (rows + 15) / 16;
+    const unsigned grid = (unsigned)(tiles < 4096 ? tiles : 4096);
+    dispatch_tile(p, [&](auto tile) {
+        using T = decltype(tile);
+        hipLaunchKernelGGL((mlp_forward_sample_kernel<T::DP, T::KS, T::MW>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream, obs,
+                           (long long)rows, p.pv, p.pv.a, p.heads, noise, seed, step, (long long)row_offset, (long long *)actions, logprob,
+                           entropy, value);
+    });
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+static int launch_rollout_squared(const TilePolicy &p, void *state, const pfa_squared_config *cfg, const pfa_experience *exp,
+                                  const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
+                                  uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    PFA_REQUIRE(state && cfg && exp && obs && rewards && terminals && truncations && masks, "rollout: null buffer");
+    PFA_REQUIRE(p.heads == 0, "rollout: the fused rollout samples one Discrete head");
+    PFA_REQUIRE(cfg->obs_stride == p.obs_stride, "rollout: env obs_stride %d != policy obs_stride %d", cfg->obs_stride, p.obs_stride);
+    PFA_REQUIRE(exp->horizon_T >= 1, "rollout: horizon must be >= 1");
+    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
+                "rollout: null experience buffer");
+    PFA_REQUIRE(noise || key, "rollout: need an explicit noise tensor or a Philox key");
+    PFA_REQUIRE(cfg->num_targets <= kMaxTargets, "rollout: too many targets");
+    SquaredView v = squared_view(state, *cfg);
+    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
+    ScopedKernelTimer timer("rollout_mlp_squared", (hipStream_t)stream);
+    // 16 envs per workgroup (an 8-env variant — two workgroups per CU at N = 4096 — and four helper waves for the stores and the
+    // noise both measured no better in round 2: tools/probe_rollout.py); the single-target env form when it applies.
+    const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
+    const bool nt1 = cfg->num_targets == 1;
+    dispatch_tile(p, [&](auto tile) {
+        using T = decltype(tile);
+        auto *kernel = nt1 ? rollout_mlp_squared_kernel<T::DP, 16, true, T::KS, T::MW> : rollout_mlp_squared_kernel<T::DP, 16, false, T::KS, T::MW>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream, v, p.pv, p.pv.a, *exp, noise, seed, step,
+                           (long long)env_offset, obs, rewards, terminals, truncations, masks);
+    });
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
 
 }  // namespace pfa
 
@@ -298,20 +398,19 @@ extern "C" int64_t pfa_mlp_param_count(const pfa_mlp_dims *dims) {
 extern "C" int pfa_mlp_forward_sample(const float *obs, int64_t rows, const float *params, const pfa_mlp_dims *dims,
                                       const float *noise, const pfa_noise_key *key, int64_t row_offset, int64_t *actions,
                                       float *logprob, float *entropy, float *value, pfa_stream_t stream) {
-    if (int rc = check_dims(dims)) return rc;
-    PFA_REQUIRE(rows >= 0, "mlp.forward: negative rows");
-    if (rows == 0) return 0;
-    PFA_REQUIRE(obs && params && actions && logprob && value, "mlp.forward: null buffer");
-    PFA_REQUIRE(noise || key, "mlp.forward: need an explicit noise tensor or a Philox key");
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    const int64_t tiles = (rows + 15) / 16;
-    const unsigned grid = (unsigned)(tiles < 4096 ? tiles : 4096);
-    PFA_DISPATCH_DP(dims,
-                    hipLaunchKernelGGL((mlp_forward_sample_kernel<DP, KS>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream, obs,
-                                       (long long)rows, mlp_view_of_flat(params, DP, dims->num_actions), dims->num_actions, dims->heads, noise, seed,
-                                       step, (long long)row_offset, (long long *)actions, logprob, entropy, value));
-    PFA_LAUNCH_CHECK();
-    return 0;
+    TilePolicy p;
+    if (int rc = policy_of_flat(params, dims, &p)) return rc;
+    return launch_forward_sample(p, obs, rows, noise, key, row_offset, actions, logprob, entropy, value, stream);
+}
+
+extern "C" int pfa_mlp_view_supported(const pfa_mlp_view *p) { return check_view(p) == 0 ? 1 : 0; }
+
+extern "C" int pfa_mlp_view_forward_sample(const float *obs, int64_t rows, const pfa_mlp_view *view, const float *noise,
+                                           const pfa_noise_key *key, int64_t row_offset, int64_t *actions, float *logprob,
+                                           float *entropy, float *value, pfa_stream_t stream) {
+    TilePolicy p;
+    if (int rc = policy_of_view(view, &p)) return rc;
+    return launch_forward_sample(p, obs, rows, noise, key, row_offset, actions, logprob, entropy, value, stream);
 }
 
 extern "C" int pfa_philox_exp_noise(float *out, int64_t steps, int64_t rows, int32_t num_actions, const pfa_noise_key *key,
@@ -334,119 +433,15 @@ extern "C" int pfa_rollout_mlp_squared(void *state, const pfa_squared_config *cf
                                        const pfa_mlp_dims *dims, const pfa_experience *exp, const float *noise,
                                        const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
                                        uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    if (int rc = check_dims(dims)) return rc;
-    PFA_REQUIRE(state && cfg && params && exp && obs && rewards && terminals && truncations && masks, "rollout: null buffer");
-    PFA_REQUIRE(dims->heads == 0, "rollout: the fused rollout samples one Discrete head");
-    PFA_REQUIRE(cfg->obs_stride == dims->obs_stride, "rollout: env obs_stride %d != policy obs_stride %d", cfg->obs_stride,
-                dims->obs_stride);
-    PFA_REQUIRE(exp->horizon_T >= 1, "rollout: horizon must be >= 1");
-    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
-                "rollout: null experience buffer");
-    PFA_REQUIRE(noise || key, "rollout: need an explicit noise tensor or a Philox key");
-    PFA_REQUIRE(cfg->num_targets <= kMaxTargets, "rollout: too many targets");
-    SquaredView v = squared_view(state, *cfg);
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    ScopedKernelTimer timer("rollout_mlp_squared", (hipStream_t)stream);
-    // 16 envs per workgroup (an 8-env variant — two workgroups per CU at N = 4096 — and four helper waves for the stores and the
-    // noise both measured no better in round 2: tools/probe_rollout.py); the single-target env form when it applies.
-    const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
-    if (cfg->num_targets == 1) {
-        PFA_DISPATCH_DP(dims,
-                        hipLaunchKernelGGL((rollout_mlp_squared_kernel<DP, 16, true, KS>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream,
-                                           v, mlp_view_of_flat(params, DP, dims->num_actions), dims->num_actions, *exp, noise, seed, step,
-                                           (long long)env_offset, obs, rewards, terminals, truncations, masks));
-    } else {
-        PFA_DISPATCH_DP(dims,
-                        hipLaunchKernelGGL((rollout_mlp_squared_kernel<DP, 16, false, KS>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream,
-                                           v, mlp_view_of_flat(params, DP, dims->num_actions), dims->num_actions, *exp, noise, seed, step,
-                                           (long long)env_offset, obs, rewards, terminals, truncations, masks));
-    }
-    PFA_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same two kernels for a Default policy of another width (models.py:24-39: hidden_size 64 / 256 / 512 — what
-// environments/classic_control, nethack / nmmo and atari's MLP heads use), reading the module's own tensors through a
-// pfa_mlp_view: hidden = 64 MW with MW hidden tiles per wave, W1 fragments in registers for the whole launch like the 128-wide
-// instantiation.  One Discrete head of up to 15 actions, observation rows of 16 / 32 / 64 floats.
-// ---------------------------------------------------------------------------------------------
-static int check_view(const pfa_mlp_view *p) {
-    PFA_REQUIRE(p != nullptr, "mlp view: null");
-    PFA_REQUIRE(p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv, "mlp view: null tensor");
-    PFA_REQUIRE(p->hidden == 64 || p->hidden == 128 || p->hidden == 256 || p->hidden == 512, "mlp view: hidden %d is not one of 64/128/256/512", p->hidden);
-    PFA_REQUIRE(p->obs_stride == 16 || p->obs_stride == 32 || p->obs_stride == 64, "mlp view: obs_stride %d is not one of 16/32/64", p->obs_stride);
-    PFA_REQUIRE(p->obs_dim >= 1 && p->obs_dim <= p->obs_stride && p->ldw1 >= p->obs_dim, "mlp view: obs_dim %d / ldw1 %d out of range", p->obs_dim, p->ldw1);
-    PFA_REQUIRE(p->num_actions >= 1 && p->num_actions <= 15, "mlp view: num_actions must be in 1..15 (got %d)", p->num_actions);
-    return 0;
-}
-extern "C" int pfa_mlp_view_supported(const pfa_mlp_view *p) { return check_view(p) == 0 ? 1 : 0; }
-static MlpView device_view(const pfa_mlp_view *p) {
-    return MlpView{p->w1, p->ldw1, p->obs_dim, p->b1, p->w2, p->b2, p->wv, p->bv, p->num_actions, p->hidden};
-}
-// (variadic: the launch expression is macro-expanded before it reaches the inner dispatch and then holds top-level commas)
-#define PFA_DISPATCH_VIEW_DP(view_, ...)                                                                 \
-    if ((view_)->obs_stride == 64 && (view_)->obs_dim > 48 && (view_)->obs_dim <= 52) {                  \
-        constexpr int DP = 64, KS = 13; __VA_ARGS__;                                                     \
-    } else switch ((view_)->obs_stride) {                                                                \
-        case 16: { constexpr int DP = 16, KS = 4; __VA_ARGS__; } break;                                   \
-        case 32: { constexpr int DP = 32, KS = 8; __VA_ARGS__; } break;                                   \
-        default: { constexpr int DP = 64, KS = 16; __VA_ARGS__; } break;                                  \
-    }
-#define PFA_DISPATCH_VIEW(view_, ...)                                                                    \
-    switch ((view_)->hidden) {                                                                           \
-        case 64: { constexpr int MW = 1; PFA_DISPATCH_VIEW_DP(view_, __VA_ARGS__) } break;                \
-        case 128: { constexpr int MW = 2; PFA_DISPATCH_VIEW_DP(view_, __VA_ARGS__) } break;               \
-        case 256: { constexpr int MW = 4; PFA_DISPATCH_VIEW_DP(view_, __VA_ARGS__) } break;               \
-        default: { constexpr int MW = 8; PFA_DISPATCH_VIEW_DP(view_, __VA_ARGS__) } break;                \
-    }
-
-extern "C" int pfa_mlp_view_forward_sample(const float *obs, int64_t rows, const pfa_mlp_view *view, const float *noise,
-                                           const pfa_noise_key *key, int64_t row_offset, int64_t *actions, float *logprob,
-                                           float *entropy, float *value, pfa_stream_t stream) {
-    if (int rc = check_view(view)) return rc;
-    PFA_REQUIRE(rows >= 0, "mlp.forward: negative rows");
-    if (rows == 0) return 0;
-    PFA_REQUIRE(obs && actions && logprob && value, "mlp.forward: null buffer");
-    PFA_REQUIRE(noise || key, "mlp.forward: need an explicit noise tensor or a Philox key");
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    const int64_t tiles = (rows + 15) / 16;
-    const unsigned grid = (unsigned)(tiles < 4096 ? tiles : 4096);
-    const MlpView pv = device_view(view);
-    PFA_DISPATCH_VIEW(view,
-                      hipLaunchKernelGGL((mlp_forward_sample_kernel<DP, KS, MW>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream, obs,
-                                         (long long)rows, pv, view->num_actions, 0u, noise, seed, step, (long long)row_offset,
-                                         (long long *)actions, logprob, entropy, value));
-    PFA_LAUNCH_CHECK();
-    return 0;
+    TilePolicy p;
+    if (int rc = policy_of_flat(params, dims, &p)) return rc;
+    return launch_rollout_squared(p, state, cfg, exp, noise, key, env_offset, obs, rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_rollout_mlp_view_squared(void *state, const pfa_squared_config *cfg, const pfa_mlp_view *view, const pfa_experience *exp,
                                             const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
                                             uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    if (int rc = check_view(view)) return rc;
-    PFA_REQUIRE(state && cfg && exp && obs && rewards && terminals && truncations && masks, "rollout: null buffer");
-    PFA_REQUIRE(cfg->obs_stride == view->obs_stride, "rollout: env obs_stride %d != policy obs_stride %d", cfg->obs_stride, view->obs_stride);
-    PFA_REQUIRE(exp->horizon_T >= 1, "rollout: horizon must be >= 1");
-    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones, "rollout: null experience buffer");
-    PFA_REQUIRE(noise || key, "rollout: need an explicit noise tensor or a Philox key");
-    PFA_REQUIRE(cfg->num_targets <= kMaxTargets, "rollout: too many targets");
-    SquaredView v = squared_view(state, *cfg);
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    const MlpView pv = device_view(view);
-    ScopedKernelTimer timer("rollout_mlp_squared", (hipStream_t)stream);
-    const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
-    if (cfg->num_targets == 1) {
-        PFA_DISPATCH_VIEW(view,
-                          hipLaunchKernelGGL((rollout_mlp_squared_kernel<DP, 16, true, KS, MW>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream,
-                                             v, pv, view->num_actions, *exp, noise, seed, step, (long long)env_offset, obs, rewards, terminals,
-                                             truncations, masks));
-    } else {
-        PFA_DISPATCH_VIEW(view,
-                          hipLaunchKernelGGL((rollout_mlp_squared_kernel<DP, 16, false, KS, MW>), dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream,
-                                             v, pv, view->num_actions, *exp, noise, seed, step, (long long)env_offset, obs, rewards, terminals,
-                                             truncations, masks));
-    }
-    PFA_LAUNCH_CHECK();
-    return 0;
+    TilePolicy p;
+    if (int rc = policy_of_view(view, &p)) return rc;
+    return launch_rollout_squared(p, state, cfg, exp, noise, key, env_offset, obs, rewards, terminals, truncations, masks, stream);
 }

@@ -25,32 +25,23 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import EPI_BIAS, EPI_BIAS_RELU, EPI_MASK, EPI_NONE, MODE_DENSE, operand, round_up
 from .models import decoder_heads, find_cnn, find_lstm, find_mlp
 
-MODE_DENSE = 0
-EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_MASK = 0, 1, 2, 3
 MAX_LOGITS = 63
-
-
-def _round_up(x, a):
-    return (x + a - 1) // a * a
-
-
-def _operand(t, lda, geom=(0,) * 9):
-    return _lib.IgemmOperand(MODE_DENSE, 0, t.data_ptr(), lda, *geom)
 
 
 def gemm_rows(a, lda, rows, K, B, ldb, N, out, ldc, epi=EPI_NONE, bias=None, mask=None, ldmask=0):
     """out[rows][:N] (row stride ldc) = epilogue(a[rows][:K] B[N][:K]^T)."""
     if rows == 0:
         return
-    _lib.check(_lib.lib().pfa_igemm_rows(C.byref(_operand(a, lda)), rows, K, _lib.ptr(B), ldb, N, _lib.ptr(out), ldc, epi, _lib.ptr(bias),
+    _lib.check(_lib.lib().pfa_igemm_rows(C.byref(operand(MODE_DENSE, a, lda)), rows, K, _lib.ptr(B), ldb, N, _lib.ptr(out), ldc, epi, _lib.ptr(bias),
                                          _lib.ptr(mask), ldmask, _lib.stream_handle()), 'gemm_rows')
 
 
 def gemm_weights(a, lda, rows, K, D, ldd, N, out, accumulate, bias_out, ws):
     """out [N][K] (torch Linear layout) (+)= D[rows][:N]^T a[rows][:K]; bias_out [N] (+)= column sums of D."""
-    _lib.check(_lib.lib().pfa_igemm_weights(C.byref(_operand(a, lda)), rows, K, _lib.ptr(D), ldd, N, _lib.ptr(out), 1, 1 if accumulate else 0,
+    _lib.check(_lib.lib().pfa_igemm_weights(C.byref(operand(MODE_DENSE, a, lda)), rows, K, _lib.ptr(D), ldd, N, _lib.ptr(out), 1, 1 if accumulate else 0,
                                             _lib.ptr(bias_out), _lib.ptr(ws), _lib.stream_handle()), 'gemm_weights')
 
 
@@ -94,7 +85,7 @@ class GeneralParams:
             self.nvec = decoder_heads(self.mlp)
             self.multidiscrete = not isinstance(self.mlp.decoder, nn.Linear)
             self.features, self.obs_dim = (int(x) for x in self.mlp.encoder.weight.shape)
-            self.obs_stride = int(obs_stride) if obs_stride else _round_up(self.obs_dim, 16)     # the vecenv's row stride
+            self.obs_stride = int(obs_stride) if obs_stride else round_up(self.obs_dim, 16)     # the vecenv's row stride
             if self.obs_stride % 16 != 0 or self.obs_stride < self.obs_dim:
                 raise ValueError(f'observation row stride {self.obs_stride}: a multiple of 16 that holds {self.obs_dim} floats')
             if self.features % 16 != 0:
@@ -178,7 +169,7 @@ class Net:
         w_ih, w_hh, b_ih, b_hh (when lstm_sizes = (I, Hl))."""
         self.kind, self.views, self.names, self.dev = kind, views, names, device
         self.obs_dim, self.Kp, self.F, self.A, self.heads = obs_dim, obs_stride, features, num_actions, heads
-        self.NO = _round_up(num_actions + 1, 16)
+        self.NO = round_up(num_actions + 1, 16)
         self.lstm = lstm_sizes
         self.FH = lstm_sizes[1] if lstm_sizes else features
         self.conv = conv_engine
@@ -239,6 +230,16 @@ class Net:
             h = self.conv.forward(obs, rows)
             rows_perm(h, self.F, out, ldo, rows, self.F)
 
+    def encode_chunks(self, obs, rows, out, ldo, chunk=None):
+        """encode() of any number of rows: the MLP encoder takes them at once, the conv encoder `chunk` frames at a time (default and
+        at most: what conv._alloc last made room for)."""
+        if self.kind == 'mlp':
+            return self.encode(obs, rows, out, ldo)
+        chunk = chunk or self.conv.chunk
+        for lo in range(0, rows, chunk):
+            m = min(chunk, rows - lo)
+            self.encode(obs[lo:lo + m], m, out[lo:lo + m], ldo)
+
     def lstm_step(self, xh, gates, c_prev, c_out, h_out, ldh, h_out2=None, ldh2=0):
         """One nn.LSTM step on the rows of xh = [x | h_prev] [R][I + Hl]: gates [R][4 Hl] keeps the activated gates."""
         I, Hl = self.lstm
@@ -287,7 +288,7 @@ def net_for_flat(fp):
             names[role] = 'recurrent.' + attr
         lstm_sizes = (fp.lstm.input_size, fp.lstm.hidden_size)
     H = int(fp.views['encoder.bias'].shape[0])
-    return Net('mlp', views, names, fp.obs_dim, _round_up(fp.obs_dim, 16), H, fp.num_actions, fp.dims.heads, lstm_sizes, fp.flat.device)
+    return Net('mlp', views, names, fp.obs_dim, round_up(fp.obs_dim, 16), H, fp.num_actions, fp.dims.heads, lstm_sizes, fp.flat.device)
 
 
 class Evaluator:
@@ -334,7 +335,7 @@ class Evaluator:
             I, Hl = net.lstm
             xh = torch.zeros(TT + 1, B, I + Hl, device=dev)
             feat = torch.empty(rows, F, device=dev)
-            self._encode_chunks(src, rows, feat, F)
+            self._encode(src, rows, feat, F)
             rows_perm(feat, F, xh, I + Hl, rows, F, B, TT, True)             # (b, t) rows -> time-major, into the x columns
             c = torch.zeros(TT + 1, B, Hl, device=dev)
             if state is not None and state[0] is not None:
@@ -349,7 +350,7 @@ class Evaluator:
             new_state = (hs[TT - 1].unsqueeze(0).clone(), c[TT].unsqueeze(0).clone())
         else:
             head_in = torch.empty(rows, F, device=dev)
-            self._encode_chunks(src, rows, head_in, F)
+            self._encode(src, rows, head_in, F)
             new_state = None
         out = torch.empty(rows, NO, device=dev)
         net.head_outputs(head_in, FH, rows, out)
@@ -384,16 +385,10 @@ class Evaluator:
                                              _lib.ptr(value), _lib.stream_handle()), 'heads_rows_eval')
         return packed, logprob, entropy, value.unsqueeze(1), new_state
 
-    def _encode_chunks(self, src, rows, out, ldo):
-        net = self.net
-        if net.kind == 'mlp':
-            net.encode(src, rows, out, ldo)
-            return
-        step = 2048
-        net.conv._alloc(min(rows, step))
-        for lo in range(0, rows, step):
-            m = min(step, rows - lo)
-            net.encode(src[lo:lo + m], m, out[lo:lo + m], ldo)
+    def _encode(self, src, rows, out, ldo):
+        if self.net.kind == 'cnn':
+            self.net.conv._alloc(min(rows, 2048))
+        self.net.encode_chunks(src, rows, out, ldo, 2048)
 
 
 USE_TILE_VIEW = True
@@ -488,7 +483,7 @@ class Engine:
         if net.lstm:
             I, Hl = net.lstm
             xh = self.s_xh[:n]
-            self._encode(obs, n, xh, I + Hl)
+            net.encode_chunks(obs, n, xh, I + Hl)
             h_all, c_all = self.lstm_h[0], self.lstm_c[0]
             if ids is None and n == h_all.shape[0]:
                 xh[:, I:].copy_(h_all)
@@ -506,22 +501,12 @@ class Engine:
                 c_all.index_copy_(0, idx, self.s_c[:n])
             feat, ldf = self.s_h, Hl
         else:
-            self._encode(obs, n, self.s_feat, net.F)
+            net.encode_chunks(obs, n, self.s_feat, net.F)
             feat, ldf = self.s_feat, net.F
         net.head_outputs(feat, ldf, n, self.s_out)
         _lib.check(L.pfa_heads_rows_sample(_lib.ptr(self.s_out), net.NO, n, net.A, net.heads, _lib.ptr(noise), C.byref(key), row_offset,
                                            _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(entropy), _lib.ptr(value), _lib.stream_handle()),
                    'heads_rows_sample')
-
-    def _encode(self, obs, n, out, ldo):
-        net = self.net
-        if net.kind == 'mlp':
-            net.encode(obs, n, out, ldo)
-            return
-        step = net.conv.chunk
-        for lo in range(0, n, step):
-            m = min(step, n - lo)
-            net.encode(obs[lo:lo + m], m, out[lo:lo + m], ldo)
 
     # ------------------------------------------------------------------------------------------------------------- update
     def _alloc_update(self, R, Th):
@@ -700,15 +685,5 @@ class Engine:
 
     def clip_adam(self, grads, opt, max_grad_norm, loss_acc, loss_scale):
         """clip_grad_norm_ + optimizer.step() (clean_pufferl.py:240-244) on the flat buffer; the packed operand forms go stale."""
-        L = _lib.lib()
-        stream = _lib.stream_handle()
-        gp = self.gp
-        n = self.norm_partials.numel()
-        _lib.check(L.pfa_sumsq_partials(_lib.ptr(grads), gp.count, _lib.ptr(self.norm_partials), n, stream), 'sumsq')
-        opt.step_count += 1
-        g = opt.param_groups[0]
-        _lib.check(L.pfa_adam_clip_step(_lib.ptr(gp.flat), _lib.ptr(grads), _lib.ptr(opt.exp_avg), _lib.ptr(opt.exp_avg_sq), gp.count,
-                                        float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), opt.step_count,
-                                        float(max_grad_norm), 1.0, C.c_void_p(grads.data_ptr() + 4 * gp.count), _lib.ptr(loss_acc), loss_scale,
-                                        _lib.ptr(self.norm_partials), n, stream), 'adam')
+        opt.step(grads, max_grad_norm, loss_acc, loss_scale, self.norm_partials)
         self.net.version += 1

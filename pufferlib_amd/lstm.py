@@ -197,22 +197,5 @@ class Engine:
         _lib.check(L.pfa_lstm_finish_grads(_lib.ptr(grads), C.byref(fp.dims), _lib.ptr(self.g16), _lib.ptr(self.bsum16), stream),
                    'lstm_finish_grads')
 
-    def _gemm_tn(self, a, b, out):
-        """out[mo][no] = a[k][mo]^T b[k][no] — the weight-gradient contraction over the minibatch rows (csrc/gemm.hip)."""
-        L = _lib.lib()
-        _lib.check(L.pfa_gemm_tn_f32(_lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0), _lib.ptr(out), out.stride(0),
-                                     a.shape[1], b.shape[1], a.shape[0], _lib.ptr(self.gemm_ws[1]), _lib.stream_handle()), 'gemm_tn')
-        return out
-
     def clip_adam(self, grads, opt, max_grad_norm, loss_acc, loss_scale):
-        L = _lib.lib()
-        stream = _lib.stream_handle()
-        fp = self.fp
-        n = self.norm_partials.numel()
-        _lib.check(L.pfa_sumsq_partials(_lib.ptr(grads), fp.count, _lib.ptr(self.norm_partials), n, stream), 'sumsq')
-        opt.step_count += 1
-        g = opt.param_groups[0]
-        _lib.check(L.pfa_adam_clip_step(_lib.ptr(fp.flat), _lib.ptr(grads), _lib.ptr(opt.exp_avg), _lib.ptr(opt.exp_avg_sq),
-                                        fp.count, float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']),
-                                        opt.step_count, float(max_grad_norm), 1.0, C.c_void_p(grads.data_ptr() + 4 * fp.count),
-                                        _lib.ptr(loss_acc), loss_scale, _lib.ptr(self.norm_partials), n, stream), 'adam')
+        opt.step(grads, max_grad_norm, loss_acc, loss_scale, self.norm_partials)

@@ -17,12 +17,9 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-from .cnn import (EPI_BIAS, EPI_MASK, EPI_NONE, LinearLayer, _operand)
-from . import cnn
-
-MODE_IM2COL_PAD, MODE_IM2COL_U8P = 5, 6
-EPI_BIAS_ADD, EPI_BIAS_ADD_RELU, EPI_MASK_ADD = 4, 5, 6
+from . import _lib, cnn
+from ._lib import EPI_BIAS, EPI_BIAS_ADD, EPI_BIAS_ADD_RELU, EPI_MASK, EPI_MASK_ADD, EPI_NONE, MODE_IM2COL_PAD, MODE_IM2COL_U8P, operand
+from .cnn import LinearLayer
 
 
 class SameConv:
@@ -46,16 +43,14 @@ class SameConv:
         self.w_dx = None if self.u8 else torch.empty(ic, self.KT, device=device)
 
     def pack(self):
-        _lib.check(_lib.lib().pfa_cnn_pack_conv_same(_lib.ptr(self.w), C.byref(_operand(0, self.w, 0, self.geom)), 1 if self.u8 else 0,
+        _lib.check(_lib.lib().pfa_cnn_pack_conv_same(_lib.ptr(self.w), C.byref(operand(0, self.w, 0, self.geom)), 1 if self.u8 else 0,
                                                      _lib.ptr(self.w_fwd), self.KR, _lib.ptr(self.w_dx), _lib.stream_handle()), 'pack_conv_same')
 
     def rows(self, n):
         return n * self.H * self.W
 
     def _in(self, x):
-        a = _operand(self.mode, x, 0, self.geom, self.strides)
-        a.reserved = self.relu_in
-        return a
+        return operand(self.mode, x, 0, self.geom, self.strides, self.relu_in)
 
     def forward(self, x, n, out, epi=EPI_BIAS, addend=None):
         """out [n*H*W][OC] = conv(x) + bias (epi 1), + addend (epi 4), relu of that (epi 5)."""
@@ -64,7 +59,7 @@ class SameConv:
 
     def backward_dx(self, dout, n, dx, mask=None, addend=None):
         """dx [n*H*W][IC] = conv_transpose(dout), zeroed where mask <= 0 (the ReLU this layer read through), + addend (the skip gradient)."""
-        a = _operand(MODE_IM2COL_PAD, dout, 0, self.geom_t)
+        a = operand(MODE_IM2COL_PAD, dout, 0, self.geom_t)
         epi = EPI_NONE if mask is None else (EPI_MASK if addend is None else EPI_MASK_ADD)
         _lib.check(_lib.lib().pfa_igemm_rows_add(C.byref(a), self.rows(n), self.KT, _lib.ptr(self.w_dx), self.KT, self.IC, _lib.ptr(dx), self.IC, epi, None,
                                                  _lib.ptr(mask), self.IC, _lib.ptr(addend), self.IC, _lib.stream_handle()), 'same_conv_dx')

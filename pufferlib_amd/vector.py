@@ -124,10 +124,6 @@ class SquaredSpec:
         pass
 
 
-def _round_up(x, m):
-    return (x + m - 1) // m * m
-
-
 def _squared_kwargs(creator, args, kwargs):
     """Resolve (distance_to_target, num_targets) the way make_squared's signature would."""
     import inspect
@@ -206,6 +202,10 @@ class _DeviceVecEnv:
     step = step
     obs_stride = 16
     ROLLOUT_LSTM = None     # name of the family's fused recurrent rollout entry point (lstm.Engine.rollout), None: it has none
+    # fused_rollout_mlp(fp, experience, noise, key, stream): clean_pufferl.evaluate's T-step loop for the fused-kernel MLP policy as one
+    # persistent kernel; None: the family has none (policy step + store + send per step)
+    fused_rollout_mlp = None
+    PREFETCH = False        # whether the trainer draws the next rollout's reset tape (and action noise) on its side stream under a fused rollout
     FAMILY = ''
     NAMES = ()
     DEFAULTS = ()
@@ -406,12 +406,14 @@ class Squared(_ResetTape, _DeviceVecEnv):
         self._obs_stride_arg = obs_stride
         super().__init__(env_creators, env_args, env_kwargs, num_envs, **kwargs)
 
+    PREFETCH = True
+
     def _creator_spec(self, creator, args, kwargs):
         return _squared_kwargs(creator, args, kwargs)
 
     def _spec(self, d, nt):
         spec = SquaredSpec(d, nt)
-        self.obs_stride = int(self._obs_stride_arg) if self._obs_stride_arg is not None else max(16, _round_up(spec.grid_size ** 2, 16))
+        self.obs_stride = int(self._obs_stride_arg) if self._obs_stride_arg is not None else max(16, _lib.round_up(spec.grid_size ** 2, 16))
         return spec
 
     def _alloc_state(self):
@@ -458,6 +460,18 @@ class Squared(_ResetTape, _DeviceVecEnv):
     def _k_infos(self):
         _lib.check(self.L.pfa_squared_last_infos(_lib.ptr(self.state), C.byref(self.cfg), *self._fin_ptrs(), _lib.stream_handle()),
                    'last_infos')
+
+    def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
+        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/rollout.hip) over the flat 128-wide parameters `fp`,
+        or over `view`: the pfa_mlp_view of a Default of another width (general.tile_view).  The caller has drawn the tape rounds."""
+        if view is not None:
+            _lib.check(self.L.pfa_rollout_mlp_view_squared(_lib.ptr(self.state), C.byref(self.cfg), C.byref(view), C.byref(experience.c),
+                                                           _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(), stream), 'rollout')
+        else:
+            _lib.check(self.L.pfa_rollout_mlp_squared(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
+                                                      C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
+                                                      stream), 'rollout')
+        self.sends += experience.horizon
 
     # -- test introspection -------------------------------------------------------------------------------
     def debug_targets(self):

@@ -149,7 +149,7 @@ def test_heads_sample_and_loss_match_the_oracle():
     lp, ent, val = (torch.empty(n, device='cuda') for _ in range(3))
     key = _lib.NoiseKey(1, 0)
     hc, nz = h.cuda(), noise.cuda()
-    _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(hc), n, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']),
+    _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(hc), 512, n, _lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']),
                                       _lib.ptr(v['value_fn.bias']), A, _lib.ptr(nz), C.byref(key), 0, _lib.ptr(acts), _lib.ptr(lp), _lib.ptr(ent),
                                       _lib.ptr(val), None), 'sample')
     assert torch.equal(acts.cpu(), oa)

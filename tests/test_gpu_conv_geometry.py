@@ -167,9 +167,9 @@ def test_width_entry_point_at_512_returns_the_bits_of_the_old_one(A):
         tail = (_lib.ptr(aw), _lib.ptr(ab), _lib.ptr(vw), _lib.ptr(vb), A, _lib.ptr(noise), C.byref(key), 0, _lib.ptr(acts), _lib.ptr(lp),
                 _lib.ptr(ent), _lib.ptr(val), None)
         if wide:
-            _lib.check(L.pfa_cnn_heads_sample_w(_lib.ptr(h), 512, n, *tail), 'sample_w')
+            _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(h), 512, n, *tail), 'sample_w')
         else:
-            _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(h), n, *tail), 'sample')
+            _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(h), 512, n, *tail), 'sample')
         got.append((acts, lp, ent, val))
     for x, y in zip(*got):
         assert torch.equal(x, y)
@@ -183,9 +183,9 @@ def test_width_entry_point_at_512_returns_the_bits_of_the_old_one(A):
     d = {k: v.cuda() for k, v in w.items()}
     acts = torch.empty(n, dtype=torch.int64, device='cuda')
     lp, ent, val = (torch.empty(n, device='cuda') for _ in range(3))
-    _lib.check(L.pfa_cnn_heads_sample_w(_lib.ptr(h2.cuda()), H, n, _lib.ptr(d['actor.weight']), _lib.ptr(d['actor.bias']),
-                                        _lib.ptr(d['value_fn.weight']), _lib.ptr(d['value_fn.bias']), A, _lib.ptr(noise), C.byref(key), 0,
-                                        _lib.ptr(acts), _lib.ptr(lp), _lib.ptr(ent), _lib.ptr(val), None), 'sample_w')
+    _lib.check(L.pfa_cnn_heads_sample(_lib.ptr(h2.cuda()), H, n, _lib.ptr(d['actor.weight']), _lib.ptr(d['actor.bias']),
+                                      _lib.ptr(d['value_fn.weight']), _lib.ptr(d['value_fn.bias']), A, _lib.ptr(noise), C.byref(key), 0,
+                                      _lib.ptr(acts), _lib.ptr(lp), _lib.ptr(ent), _lib.ptr(val), None), 'sample_w')
     assert np.array_equal(acts.cpu().numpy(), action.numpy())
     np.testing.assert_allclose(lp.cpu().numpy(), logprob.numpy(), **TOL)
     np.testing.assert_allclose(ent.cpu().numpy(), entropy.numpy(), **TOL)
@@ -484,7 +484,7 @@ def test_reference_run_replays_at_the_new_geometries(name, golden_dir, matrix_pr
 @pytest.mark.parametrize('H', [512, 128, 144, 272])
 @pytest.mark.parametrize('A', [4, 15])
 def test_heads_loss_entry_point_at_each_width_vs_float64(H, A):
-    """pfa_cnn_heads_loss_w on its own: the two instantiated widths and two that take the run-time loop (144: nine 16-column groups,
+    """pfa_cnn_heads_loss on its own: the two instantiated widths and two that take the run-time loop (144: nine 16-column groups,
     one partial block of eight; 272: seventeen), a minibatch walked in two chunks (accumulate), rows that end inside a 16-row tile.
     d loss / d head outputs, d loss / d pre-ReLU hidden and the loss sums against float64 autograd; at 512 the bits of the old entry
     point."""
@@ -523,9 +523,9 @@ def test_heads_loss_entry_point_at_each_width_vs_float64(H, A):
                     _lib.ptr(dw['value_fn.bias']), A, C.byref(hp), _lib.ptr(stats), mbs, _lib.ptr(dout[q0:]), _lib.ptr(dh[q0:]), _lib.ptr(tail),
                     1 if ci else 0, _lib.ptr(ws), None)
             if entry == 'w':
-                _lib.check(L.pfa_cnn_heads_loss_w(_lib.ptr(hm[q0:]), H, *args), 'loss_w')
-            else:
-                _lib.check(L.pfa_cnn_heads_loss(_lib.ptr(hm[q0:]), *args), 'loss')
+                _lib.check(L.pfa_cnn_heads_loss(_lib.ptr(hm[q0:]), H, *args), 'loss_w')
+            else:                   # (what the fixed-width entry point of earlier versions passed)
+                _lib.check(L.pfa_cnn_heads_loss(_lib.ptr(hm[q0:]), 512, *args), 'loss')
             q0 += m
         return dout, dh, tail
 

@@ -535,3 +535,97 @@ def test_rank_affinity_plan_keeps_every_rank_next_to_its_gpu_and_off_its_neighbo
     assert pdist.plan_affinity(2, 4, [-1] * 4, {}, {3, 7}) == (-1, [3, 7])
     # the GPU's node has no allowed CPU at all: fall back to the mask
     assert pdist.plan_affinity(0, 2, [1, 1], node_cpus, {0, 1, 2, 3}) == (-1, [0, 1])
+
+
+def test_rollout_form_follows_what_the_env_class_declares():
+    """clean_pufferl.rollout_form for every device vecenv class against every engine combination create() can produce (it refuses a
+    recurrent policy on Stochastic): a GEMM-path policy rolls out step by step except the tile-kernel widths on exactly Squared; the
+    fused recurrent kernel where the class names one; the fused MLP kernel where the class has one; an env class that declares
+    nothing is stepped through the protocol, whatever the policy."""
+    from pufferlib_amd import clean_pufferl as cp
+    from pufferlib_amd import vector as v
+    S, R, M = cp.STEPWISE, cp.FUSED_LSTM, cp.FUSED_MLP
+
+    class Bare(v._DeviceVecEnv):
+        pass
+
+    class SquaredChild(v.Squared):
+        pass
+    #                 general   general + mlp_view   lstm    neither (fused-kernel MLP, conv)
+    table = {v.Squared:    (S, M, R, M),
+             v.Stochastic: (S, S, None, M),
+             v.Memory:     (S, S, R, S),
+             v.Spaces:     (S, S, S, S),
+             v.Synthetic:  (S, S, R, S),
+             v.Frames:     (S, S, S, S),
+             v.Bandit:     (S, S, S, S),
+             v.Multiagent: (S, S, S, S),
+             Bare:         (S, S, S, S),
+             SquaredChild: (S, S, R, M)}       # the view rollout reads Squared's own state layout: exactly that class
+    engines = [dict(gen_engine=True, lstm_engine=False, mlp_view=False), dict(gen_engine=True, lstm_engine=False, mlp_view=True),
+               dict(gen_engine=False, lstm_engine=True, mlp_view=False), dict(gen_engine=False, lstm_engine=False, mlp_view=False)]
+    for cls, want in table.items():
+        for kw, w in zip(engines, want):
+            if w is not None:
+                assert cp.rollout_form(cls, **kw) == w, (cls.__name__, kw)
+
+
+class _RecordingLib:
+    """Stands in for the library handle: every entry point records its arguments and succeeds."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def entry(*args):
+            self.calls.append((name, args))
+            return 0
+        return entry
+
+
+@pytest.mark.parametrize('kind,partials', [('mlp', None), ('lstm', 256), ('cnn', 1024), ('general', 1024)])
+def test_hip_adam_step_hands_the_kernels_what_each_update_site_did(kind, partials, monkeypatch):
+    """HipAdam.step is the one place that spells pfa_sumsq_partials + pfa_adam_clip_step.  Its arguments for each policy kind's
+    parameter buffer are the ones the four former sites built (recorded from lstm / cnn / general Engine.clip_adam with this
+    recorder, read off train()'s per-minibatch loop for the MLP): the engines' sum(g^2) in 256 (lstm) or 1024 pieces, none in train()'s
+    loop; step_count advances by one per call and is what the kernel gets."""
+    from pufferlib_amd import _lib, cleanrl, general, models, namespace, spaces, vector
+    from pufferlib_amd.clean_pufferl import HipAdam
+    env = vector.make_squared()
+    frames = namespace(single_observation_space=spaces.Box(low=0, high=255, shape=(4, 84, 84), dtype=np.uint8),
+                       single_action_space=spaces.Discrete(6))
+    fp, count = {
+        'mlp': lambda: (models.FlatParams(_policy(False).policy, 64, 'cpu'), None),
+        'lstm': lambda: (models.FlatParams(_policy(True).policy, 64, 'cpu'), 141577),
+        'cnn': lambda: (models.ConvParams(models.Convolutional(frames), 'cpu'), 1687719),
+        'general': lambda: (general.GeneralParams(models.Default(env, hidden_size=256), 'cpu'), 15113),
+    }[kind]()
+    assert count is None or fp.count == count          # (the sizes the recorded tuples carry)
+    rec = _RecordingLib()
+    monkeypatch.setattr(_lib, 'lib', lambda: rec)
+    monkeypatch.setattr(_lib, 'stream_handle', lambda: 'stream')
+    opt = HipAdam(fp, lr=2.5e-4, eps=1e-5)
+    opt.step_count = 6
+    grads, loss_acc = torch.zeros(fp.count + 16), torch.zeros(8, dtype=torch.float64)
+    parts = None if partials is None else torch.zeros(partials, dtype=torch.float64)
+    name_of = {fp.flat.data_ptr(): 'flat', grads.data_ptr(): 'grads', opt.exp_avg.data_ptr(): 'exp_avg', opt.exp_avg_sq.data_ptr(): 'exp_avg_sq',
+               grads.data_ptr() + 4 * fp.count: 'tail', loss_acc.data_ptr(): 'loss_acc'}
+    if parts is not None:
+        name_of[parts.data_ptr()] = 'partials'
+
+    def plain(args):
+        vals = [a.value if isinstance(a, C.c_void_p) else a for a in args]
+        return [name_of.get(v, v) if isinstance(v, int) and not isinstance(v, bool) and v > 1 << 20 else v for v in vals]
+    for step in (7, 8):
+        rec.calls.clear()
+        if parts is None:
+            opt.step(grads, 0.5, loss_acc, 0.125)
+        else:
+            opt.step(grads, 0.5, loss_acc, 0.125, parts)
+        want = []
+        if parts is not None:
+            want.append(('pfa_sumsq_partials', ['grads', fp.count, 'partials', partials, 'stream']))
+        want.append(('pfa_adam_clip_step', ['flat', 'grads', 'exp_avg', 'exp_avg_sq', fp.count, 0.00025, 0.9, 0.999, 1e-05, step, 0.5, 1.0, 'tail',
+                                            'loss_acc', 0.125, 'partials' if parts is not None else None, partials or 0, 'stream']))
+        assert [(n, plain(a)) for n, a in rec.calls] == want
+        assert opt.step_count == step

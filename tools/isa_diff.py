@@ -3,8 +3,9 @@
 (host-side refactors, removed preprocessor branches).  Build both with
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fuse-cuid=none -x hip -S --cuda-device-only FILE.hip -o FILE.s
 and run   tools/isa_diff.py OLD.s NEW.s [OLD2.s NEW2.s ...].  Compared per .amdhsa_kernel symbol, not as whole files (the order of
-instantiation may differ): the instruction text, the .amdhsa_ descriptor block and the metadata entry.  Two things are normalised:
-the per-compile __hip_cuid_<hex> symbol and the function ordinal in local labels (.LBB<n>_<k>, .Lfunc_end<n>, and BB<n>_<k> in comments).  Exit status 1 when a
+instantiation may differ): the instruction text, the .amdhsa_ descriptor block and the metadata entry.  Three things are normalised:
+the per-compile __hip_cuid_<hex> symbol, the function ordinal in local labels (.LBB<n>_<k>, .Lfunc_end<n>, and BB<n>_<k> in comments)
+and the blanks in front of a comment (the column padding behind a label depends on the ordinal's digit count).  Exit status 1 when a
 kernel is missing on either side or differs."""
 import re
 import sys
@@ -14,6 +15,7 @@ def kernels(path):
     text = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid', open(path).read())
     text = re.sub(r'\.L([A-Za-z_]+?)\d+(_\d+)?\b', r'.L\1#\2', text)
     text = re.sub(r'\bBB\d+_(\d+)\b', r'BB#_\1', text)   # the same labels inside the compiler's comments ("Loop: Header=BB28_3")
+    text = re.sub(r'[ \t]+;', ' ;', text)                # comments are padded to a column: an ordinal of 9 -> 10 moves the padding behind its labels
     out = {}
     for m in re.finditer(r'^\s*\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel', text, re.M | re.S):
         name = m.group(1)
