@@ -99,18 +99,11 @@ extern "C" int pfa_bandit_send(void *state, int32_t num_envs, int32_t solution, 
 }
 
 extern "C" int pfa_bandit_episode_stats(void *state, int32_t num_envs, double *out4, int32_t reset, pfa_stream_t stream) {
-    PFA_REQUIRE(state && num_envs >= 1 && out4, "bandit.episode_stats: bad arguments");
-    hipLaunchKernelGGL(episode_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, bandit_view(state, num_envs).fin, (int)num_envs,
-                       out4, (int)reset);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_stats("bandit", state, bandit_view(state, num_envs).fin, num_envs, out4, reset, nullptr, stream);
 }
 
 extern "C" int pfa_bandit_last_infos(void *state, int32_t num_envs, uint8_t *finished, double *episode_return,
                                      int32_t *episode_length, double *score, pfa_stream_t stream) {
-    PFA_REQUIRE(state && num_envs >= 1 && finished && episode_return && episode_length && score, "bandit.last_infos: bad arguments");
-    hipLaunchKernelGGL(episode_infos_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       bandit_view(state, num_envs).fin, (int)num_envs, finished, episode_return, (int *)episode_length, score);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_infos("bandit", state, bandit_view(state, num_envs).fin, num_envs, finished, episode_return, episode_length,
+                                score, stream);
 }

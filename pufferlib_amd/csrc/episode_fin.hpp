@@ -63,4 +63,23 @@ static __global__ void __launch_bounds__(256) episode_infos_kernel(const Episode
     score[e] = f.last_score;
 }
 
+// Host side of every family's `*_episode_stats` / `*_last_infos` entry point, which has checked its own config: `family` names it in
+// the error text, `fin` is the view's accumulator array over `state`.
+static inline int launch_episode_stats(const char *family, const void *state, EpisodeFin *fin, int n, double *out4, int reset,
+                                       const int *underrun, pfa_stream_t stream) {
+    PFA_REQUIRE(state && n >= 1 && out4, "%s.episode_stats: bad arguments", family);
+    hipLaunchKernelGGL(episode_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, fin, n, out4, reset, underrun);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+static inline int launch_episode_infos(const char *family, const void *state, const EpisodeFin *fin, int n, uint8_t *finished,
+                                       double *episode_return, int32_t *episode_length, double *score, pfa_stream_t stream) {
+    PFA_REQUIRE(state && n >= 1 && finished && episode_return && episode_length && score, "%s.last_infos: bad arguments", family);
+    hipLaunchKernelGGL(episode_infos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fin, n, finished,
+                       episode_return, (int *)episode_length, score);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace pfa

@@ -16,9 +16,7 @@
 #include "mlp_tile.hpp"
 #include "philox.hpp"
 #include "sampler.hpp"
-#include "squared_env.hpp"
-#include "memory_env.hpp"
-#include "synth_env.hpp"
+#include "env_adapters.hpp"
 
 namespace pfa {
 
@@ -119,131 +117,8 @@ __global__ void __launch_bounds__(kLstmThreads) lstm_policy_step_kernel(const fl
 
 // ---------------------------------------------------------------------------------------------
 // fused persistent rollout (see the header comment); structure follows rollout_mlp_squared_kernel (rollout.hip).
-// The kernel is one skeleton over an env adapter: a plain struct that holds the env's state in registers of its owner
-// thread (lane 0 of the env's 16-lane sampling group) and supplies what differs per env family:
-//   View / view()   the device view of the vecenv state and how the entry point's config maps to it
-//   Shared          what the env keeps in LDS next to LstmLds (empty: costs nothing)
-//   load / store    owner thread: state in before the first step / out after the last one
-//   step            owner thread, after the scalars of row (e, t) are stored: reset from the tape or apply the sampled
-//                   action; writes `reward` / `terminal` of the next row and the env's LDS observation row
-//   refresh         all 16 lanes of the env, after the barrier that follows step, only where kRefresh (a second barrier
-//                   follows it)
+// The kernel is one skeleton over an env adapter (env_adapters.hpp): load / step / refresh / store.
 // ---------------------------------------------------------------------------------------------
-struct SquaredRollEnv {
-    using View = SquaredView;
-    static View view(void *state, const pfa_squared_config &c) { return squared_view(state, c); }
-    static constexpr bool kRefresh = false;
-    struct Shared {
-        uint16_t tg[16 * kMaxTargets];   // target cells per env
-    };
-    SquaredEnv s;
-
-    __device__ __forceinline__ void load(const View &v, int e, int le, Shared &sh) {
-        squared_load(v, e, s);
-        for (int t = 0; t < v.nt; ++t) sh.tg[le * kMaxTargets + t] = v.tgt[(size_t)t * v.n + e];
-    }
-    __device__ __forceinline__ void step(const View &v, int e, int le, Shared &sh, float *grid, int action, float &reward,
-                                         bool &terminal) {
-        uint16_t *tc = sh.tg + le * kMaxTargets;
-        if (s.done) {
-            if ((long long)s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
-            const uint16_t *tr = v.tape + (size_t)(s.rounds % (uint32_t)v.tape_rounds) * v.nt * v.n;
-            squared_reset(v, e, s, grid, tr, tc, reward, terminal);
-            s.rounds += 1;
-        } else {
-            bool fin;
-            double fr, fs;
-            int fl;
-            squared_step(v, s, grid, tc, action, reward, terminal, fin, fr, fl, fs);
-        }
-    }
-    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
-    __device__ __forceinline__ void store(const View &v, int e, int le, Shared &sh) {
-        squared_store(v, e, s);
-        for (int t = 0; t < v.nt; ++t) v.tgt[(size_t)t * v.n + e] = sh.tg[le * kMaxTargets + t];
-        v.fin[e] = 0;
-    }
-};
-
-// ocean Memory (memory_env.hpp; observation rows of 16 floats, one real column): the env that NEEDS the recurrent state.
-struct MemoryRollEnv {
-    using View = MemoryView;
-    static View view(void *state, const pfa_memory_config &c) { return memory_view(state, c); }
-    static constexpr bool kRefresh = false;
-    struct Shared {};
-    MemoryEnv s = {};
-    int last_fin = 0;
-
-    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
-    __device__ __forceinline__ void step(const View &v, int e, int, Shared &, float *row, int action, float &reward, bool &terminal) {
-        float o;
-        last_fin = 0;
-        if (s.done) {   // auto-reset row (vector.py:144-151): the action is ignored, the next solution comes off the tape
-            if (s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
-            const uint32_t bits = v.tape[(size_t)(s.rounds % v.tape_rounds) * v.n + e];
-            const long long rounds = s.rounds + 1;
-            memory_begin_episode(s, bits, o, reward, terminal);
-            s.rounds = rounds;
-        } else {
-            double fr, fs;
-            int fl;
-            if (memory_step(v, s, action, o, reward, terminal, fr, fl, fs)) {
-                episode_account(v.fin[e], fr, fl, fs);
-                last_fin = 1;
-            }
-        }
-        row[0] = o;
-    }
-    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
-    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
-        v.env[e] = s;
-        v.fin[e].last_fin = last_fin;
-    }
-};
-
-// The synthetic byte-row env of BASELINE configs[2] (synth_env.hpp; rows of DP = obs_stride floats).  The 16 lanes of an env's
-// sampling group regenerate its observation row after the step, 16 values per lane (one Philox call each).
-struct SynthRollEnv {
-    using View = SynthView;
-    static View view(void *state, const pfa_synth_config &c) { return synth_view(state, c); }
-    static constexpr bool kRefresh = true;
-    struct Shared {
-        int tick[16], episode[16];   // the owner's (tick, episode) after the step, for the other lanes of the env
-    };
-    SynthEnv s = {};
-    int last_fin = 0;
-
-    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
-    __device__ __forceinline__ void step(const View &v, int e, int le, Shared &sh, float *row, int action, float &reward, bool &terminal) {
-        last_fin = 0;
-        if (s.done) {
-            synth_begin_episode(s, reward, terminal);
-        } else {
-            double fr, fs;
-            int fl;
-            if (synth_step(v, s, action, (int)row[0], reward, terminal, fr, fl, fs)) {
-                episode_account(v.fin[e], fr, fl, fs);
-                last_fin = 1;
-            }
-        }
-        sh.tick[le] = s.tick;
-        sh.episode[le] = s.episode;
-    }
-    __device__ __forceinline__ void refresh(const View &v, int e, int le, int lo, Shared &sh, float *row) {
-        if (lo * 16 < v.values) {   // the next observation row of this env, 16 values per lane
-            float vals[16];
-            synth_chunk(v, e, sh.episode[le], sh.tick[le], lo, vals);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (lo * 16 + k < v.values) row[lo * 16 + k] = vals[k];
-        }
-    }
-    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
-        v.env[e] = s;
-        v.fin[e].last_fin = last_fin;
-    }
-};
-
 template <int DP, class Env>
 __global__ void __launch_bounds__(kLstmThreads) rollout_lstm_kernel(typename Env::View v, const float *params, int a,
                                                                    const float4 *wpack, float *h, float *cell, pfa_experience ex,

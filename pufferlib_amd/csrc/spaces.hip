@@ -388,20 +388,13 @@ extern "C" int pfa_spaces_send(void *state, const pfa_spaces_config *cfg, const 
 
 extern "C" int pfa_spaces_episode_stats(void *state, const pfa_spaces_config *cfg, double *out5, int32_t reset, pfa_stream_t stream) {
     if (int rc = check_spaces_config(cfg)) return rc;
-    PFA_REQUIRE(state && out5, "spaces.episode_stats: null buffer");
-    SpacesView v = spaces_view(state, *cfg);
-    hipLaunchKernelGGL(episode_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, v.fin, (int)cfg->num_envs, out5, (int)reset,
-                       (const int *)&v.hdr->underrun);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    const SpacesView v = spaces_view(state, *cfg);
+    return launch_episode_stats("spaces", state, v.fin, cfg->num_envs, out5, reset, &v.hdr->underrun, stream);
 }
 
 extern "C" int pfa_spaces_last_infos(void *state, const pfa_spaces_config *cfg, uint8_t *finished, double *episode_return,
                                      int32_t *episode_length, double *score, pfa_stream_t stream) {
     if (int rc = check_spaces_config(cfg)) return rc;
-    PFA_REQUIRE(state && finished && episode_return && episode_length && score, "spaces.last_infos: null buffer");
-    hipLaunchKernelGGL(episode_infos_kernel, dim3((unsigned)((cfg->num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       spaces_view(state, *cfg).fin, (int)cfg->num_envs, finished, episode_return, (int *)episode_length, score);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_infos("spaces", state, spaces_view(state, *cfg).fin, cfg->num_envs, finished, episode_return, episode_length,
+                                score, stream);
 }

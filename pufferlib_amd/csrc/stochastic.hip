@@ -10,6 +10,7 @@
 // the last proximity.  Kernels: async_reset, send (protocol path), episode statistics, and the fused persistent rollout
 // with the MLP policy (same tile code as every other rollout, rollout_tile.hpp; observation row stride 16).
 #include "common.hpp"
+#include "env_adapters.hpp"
 #include "episode_fin.hpp"
 #include "rollout_tile.hpp"
 
@@ -27,6 +28,10 @@ struct StochasticView {
     StochasticFin *fin;
     int n;
 };
+struct StochasticStepView : StochasticView {   // what the kernels that step the env take: the state and the env's parameters
+    int horizon;
+    double p;
+};
 __host__ __device__ inline size_t stochastic_state_bytes(int n) {
     return (size_t)n * (sizeof(StochasticEnv) + sizeof(StochasticFin));
 }
@@ -35,6 +40,13 @@ __host__ __device__ inline StochasticView stochastic_view(void *state, int n) {
     v.env = (StochasticEnv *)state;
     v.fin = (StochasticFin *)((char *)state + (size_t)n * sizeof(StochasticEnv));
     v.n = n;
+    return v;
+}
+__host__ __device__ inline StochasticStepView stochastic_view(void *state, int n, double p, int horizon) {
+    StochasticStepView v;
+    static_cast<StochasticView &>(v) = stochastic_view(state, n);
+    v.horizon = horizon;
+    v.p = p;
     return v;
 }
 
@@ -89,37 +101,42 @@ __global__ void __launch_bounds__(256) stochastic_reset_kernel(StochasticView v,
     masks[e] = 1;
 }
 
-__global__ void __launch_bounds__(256) stochastic_send_kernel(StochasticView v, double p, int horizon, const long long *actions,
-                                                             float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations,
-                                                             uint8_t *masks) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= v.n) return;
-    StochasticEnv s = v.env[e];
-    float r;
-    bool t;
-    v.fin[e].last_fin = 0;
-    if (s.done) {
-        stochastic_reset(s, r, t);
-    } else {
-        double fr, fs;
-        int fl;
-        if (stochastic_step(s, (int)actions[e], p, horizon, r, t, fr, fl, fs)) episode_account(v.fin[e], fr, fl, fs);
+// The env adapter (env_adapters.hpp): the one definition of a send, for the protocol kernel and the fused rollout below.
+struct StochasticRollEnv {
+    using View = StochasticStepView;
+    static constexpr bool kRefresh = false;
+    struct Shared {};
+    StochasticEnv s = {};
+    int last_fin = 0;
+
+    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
+    __device__ __forceinline__ void step(const View &v, int e, int, Shared &, float *row, int action, float &reward, bool &terminal) {
+        last_fin = 0;
+        if (s.done) {
+            stochastic_reset(s, reward, terminal);
+        } else {
+            double fr, fs;
+            int fl;
+            if (stochastic_step(s, action, v.p, v.horizon, reward, terminal, fr, fl, fs)) {
+                episode_account(v.fin[e], fr, fl, fs);
+                last_fin = 1;
+            }
+        }
+        row[0] = 0.0f;   // the observation never changes
     }
-    v.env[e] = s;
-    obs[(size_t)e * kStoDP] = 0.0f;
-    rewards[e] = r;
-    terminals[e] = t ? 1 : 0;
-    truncations[e] = 0;
-    masks[e] = 1;
-}
+    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
+    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
+        v.env[e] = s;
+        v.fin[e].last_fin = last_fin;
+    }
+};
 
 // Fused persistent rollout, structure of rollout_mlp_squared_kernel (rollout.hip): 16 envs per 4-wave workgroup, env state
 // in registers of the owner lanes, the 16 observation rows in LDS as the MFMA B operand, weights in registers.
-__global__ void __launch_bounds__(kRollThreads) rollout_mlp_stochastic_kernel(StochasticView v, double p, int horizon_env,
-                                                                             const float *params, int a, pfa_experience ex,
-                                                                             const float *noise, uint64_t seed, uint64_t step0,
-                                                                             long long env_offset, float *live_obs, float *live_rew,
-                                                                             uint8_t *live_term, uint8_t *live_trunc,
+__global__ void __launch_bounds__(kRollThreads) rollout_mlp_stochastic_kernel(StochasticStepView v, const float *params, int a,
+                                                                             pfa_experience ex, const float *noise, uint64_t seed,
+                                                                             uint64_t step0, long long env_offset, float *live_obs,
+                                                                             float *live_rew, uint8_t *live_term, uint8_t *live_trunc,
                                                                              uint8_t *live_mask) {
     constexpr int DP = kStoDP;
     __shared__ float xs[XTile<DP>::kFloats];
@@ -133,14 +150,14 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_stochastic_kernel(St
     SliceFrags<DP> w;
     w.load(params, a);
     stage_rows<DP>(live_obs, (long long)blockIdx.x * 16, v.n, xs, 16);
-    StochasticEnv s = {};
+    StochasticRollEnv env;
+    StochasticRollEnv::Shared sh;
     float reward = 0.0f;
     bool terminal = false;
     if (owner) {
-        s = v.env[e];
+        env.load(v, e, le, sh);
         reward = live_rew[e];
         terminal = live_term[e] != 0;
-        v.fin[e].last_fin = 0;
     }
     __syncthreads();
 
@@ -159,19 +176,12 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_stochastic_kernel(St
             ex.actions[row] = sm.action;
             ex.logprobs[row] = sm.logprob;
             ex.values[row] = sm.value;
-            if (s.done) {
-                stochastic_reset(s, reward, terminal);
-            } else {
-                double fr, fs;
-                int fl;
-                if (stochastic_step(s, sm.action, p, horizon_env, reward, terminal, fr, fl, fs)) episode_account(v.fin[e], fr, fl, fs);
-            }
-            // the observation never changes: xs row le stays [0, 0, ...]
+            env.step(v, e, le, sh, xs + le * XTile<DP>::XS, sm.action, reward, terminal);
         }
         __syncthreads();
     }
     if (owner) {
-        v.env[e] = s;
+        env.store(v, e, le, sh);
         live_rew[e] = reward;
         live_term[e] = terminal ? 1 : 0;
         live_trunc[e] = 0;
@@ -197,30 +207,19 @@ extern "C" int pfa_stochastic_async_reset(void *state, int32_t num_envs, float *
 
 extern "C" int pfa_stochastic_send(void *state, int32_t num_envs, double p, int32_t horizon, const int64_t *actions, float *obs,
                                    float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    PFA_REQUIRE(state && num_envs >= 1 && horizon >= 1 && actions && obs && rewards && terminals && truncations && masks,
-                "stochastic.send: bad arguments");
-    hipLaunchKernelGGL(stochastic_send_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       stochastic_view(state, num_envs), p, (int)horizon, (const long long *)actions, obs, rewards, terminals,
-                       truncations, masks);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    PFA_REQUIRE(num_envs >= 1 && horizon >= 1, "stochastic.send: bad arguments");
+    return launch_env_send<StochasticRollEnv>("stochastic.send", state, stochastic_view(state, num_envs, p, horizon), kStoDP, actions, obs,
+                                              rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_stochastic_episode_stats(void *state, int32_t num_envs, double *out4, int32_t reset, pfa_stream_t stream) {
-    PFA_REQUIRE(state && num_envs >= 1 && out4, "stochastic.episode_stats: bad arguments");
-    hipLaunchKernelGGL(episode_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stochastic_view(state, num_envs).fin,
-                       (int)num_envs, out4, (int)reset);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_stats("stochastic", state, stochastic_view(state, num_envs).fin, num_envs, out4, reset, nullptr, stream);
 }
 
 extern "C" int pfa_stochastic_last_infos(void *state, int32_t num_envs, uint8_t *finished, double *episode_return,
                                          int32_t *episode_length, double *score, pfa_stream_t stream) {
-    PFA_REQUIRE(state && num_envs >= 1 && finished && episode_return && episode_length && score, "stochastic.last_infos: bad arguments");
-    hipLaunchKernelGGL(episode_infos_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       stochastic_view(state, num_envs).fin, (int)num_envs, finished, episode_return, (int *)episode_length, score);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_infos("stochastic", state, stochastic_view(state, num_envs).fin, num_envs, finished, episode_return,
+                                episode_length, score, stream);
 }
 
 extern "C" int pfa_rollout_mlp_stochastic(void *state, int32_t num_envs, double p, int32_t horizon, const float *params,
@@ -239,7 +238,7 @@ extern "C" int pfa_rollout_mlp_stochastic(void *state, int32_t num_envs, double 
     const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
     ScopedKernelTimer timer("rollout_mlp_stochastic", (hipStream_t)stream);
     hipLaunchKernelGGL(rollout_mlp_stochastic_kernel, dim3((unsigned)((num_envs + 15) / 16)), dim3(kRollThreads), 0, (hipStream_t)stream,
-                       stochastic_view(state, num_envs), p, (int)horizon, params, dims->num_actions, *exp, noise, seed, step,
+                       stochastic_view(state, num_envs, p, horizon), params, dims->num_actions, *exp, noise, seed, step,
                        (long long)env_offset, obs, rewards, terminals, truncations, masks);
     PFA_LAUNCH_CHECK();
     return 0;

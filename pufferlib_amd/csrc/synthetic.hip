@@ -1,7 +1,7 @@
 // synthetic.hip — protocol kernels of the synthetic byte-row vecenv (synth_env.hpp): the device-side generator of BASELINE
 // configs[2]'s workload shape.  The fused recurrent rollout over it lives in lstm_fused.hip.
 #include "common.hpp"
-#include "synth_env.hpp"
+#include "env_adapters.hpp"
 
 namespace pfa {
 
@@ -36,68 +36,39 @@ __global__ void __launch_bounds__(256) synth_reset_kernel(SynthView v, float *ob
     masks[e] = 1;
 }
 
-__global__ void __launch_bounds__(256) synth_send_kernel(SynthView v, const long long *actions, float *obs, float *rewards,
-                                                        uint8_t *terminals, uint8_t *truncations, uint8_t *masks) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= v.n) return;
-    SynthEnv s = v.env[e];
-    v.fin[e].last_fin = 0;
-    float r;
-    bool t;
-    if (s.done) {
-        synth_begin_episode(s, r, t);
-    } else {
-        double fr, fs;
-        int fl;
-        const int shown0 = (int)obs[(size_t)e * v.stride];
-        if (synth_step(v, s, (int)actions[e], shown0, r, t, fr, fl, fs)) episode_account(v.fin[e], fr, fl, fs);
-    }
-    v.env[e] = s;
-    synth_write_row(v, e, s, obs);
-    rewards[e] = r;
-    terminals[e] = t ? 1 : 0;
-    truncations[e] = 0;
-    masks[e] = 1;
-}
-
 // Frame rows (BASELINE configs[3] / SURVEY config C4: uint8 (framestack, 84, 84) observations, uniform 0..255): the same counter
 // stream, 16 bytes per Philox call stored as they come (obs_high = 255: byte % 256 is the byte).  One workgroup per env; lane 0
 // steps the episode, everyone writes the frame.  actions == nullptr is the reset.
 __global__ void __launch_bounds__(256) frames_kernel(SynthView v, const long long *actions, uint8_t *obs, float *rewards, uint8_t *terminals,
                                                     uint8_t *truncations, uint8_t *masks) {
     const int e = blockIdx.x;
-    __shared__ int sh_episode, sh_tick;
+    __shared__ SynthRollEnv::Shared sh;   // slot 0: lane 0's (tick, episode) after the step, for everyone
     uint8_t *row = obs + (size_t)e * v.stride;
     if (threadIdx.x == 0) {
-        SynthEnv s;
         float r = 0.0f;
         bool t = false;
         if (actions == nullptr) {
-            s = SynthEnv{};
+            SynthEnv s = {};
             s.episode = -1;
             synth_begin_episode(s, r, t);
+            v.env[e] = s;
             v.fin[e] = EpisodeFin{};
+            sh.tick[0] = s.tick;
+            sh.episode[0] = s.episode;
         } else {
-            s = v.env[e];
-            v.fin[e].last_fin = 0;
-            if (s.done) {
-                synth_begin_episode(s, r, t);
-            } else {
-                double fr, fs;
-                int fl;
-                if (synth_step(v, s, (int)actions[e], (int)row[0], r, t, fr, fl, fs)) episode_account(v.fin[e], fr, fl, fs);
-            }
+            SynthRollEnv env;
+            float shown = (float)row[0];   // the adapter reads byte 0 of the shown row as a float
+            env.load(v, e, 0, sh);
+            env.step(v, e, 0, sh, &shown, (int)actions[e], r, t);
+            env.store(v, e, 0, sh);
         }
-        v.env[e] = s;
         rewards[e] = r;
         terminals[e] = t ? 1 : 0;
         truncations[e] = 0;
         masks[e] = 1;
-        sh_episode = s.episode;
-        sh_tick = s.tick;
     }
     __syncthreads();          // also orders lane 0's read of row[0] before anyone overwrites it
-    const int episode = sh_episode, tick = sh_tick;
+    const int episode = sh.episode[0], tick = sh.tick[0];
     for (int chunk = threadIdx.x; chunk * 16 < v.values; chunk += 256) {
         const u32x4 w = philox4x32_10((uint32_t)(v.env_offset + e), (uint32_t)chunk, (uint32_t)episode, (uint32_t)tick, (uint32_t)v.seed,
                                       0x5359u ^ (uint32_t)(v.seed >> 32));
@@ -149,11 +120,8 @@ extern "C" int pfa_synth_async_reset(void *state, const pfa_synth_config *cfg, f
 extern "C" int pfa_synth_send(void *state, const pfa_synth_config *cfg, const int64_t *actions, float *obs, float *rewards,
                               uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     if (int rc = check_synth_config(cfg)) return rc;
-    PFA_REQUIRE(state && actions && obs && rewards && terminals && truncations && masks, "synth.send: null buffer");
-    hipLaunchKernelGGL(synth_send_kernel, dim3((unsigned)((cfg->num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       synth_view(state, *cfg), (const long long *)actions, obs, rewards, terminals, truncations, masks);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_env_send<SynthRollEnv>("synth.send", state, synth_view(state, *cfg), cfg->obs_stride, actions, obs, rewards, terminals,
+                                         truncations, masks, stream);
 }
 
 extern "C" int pfa_frames_async_reset(void *state, const pfa_synth_config *cfg, uint8_t *obs, float *rewards, uint8_t *terminals,
@@ -178,19 +146,12 @@ extern "C" int pfa_frames_send(void *state, const pfa_synth_config *cfg, const i
 
 extern "C" int pfa_synth_episode_stats(void *state, const pfa_synth_config *cfg, double *out4, int32_t reset, pfa_stream_t stream) {
     if (int rc = check_synth_any(cfg)) return rc;
-    PFA_REQUIRE(state && out4, "synth.episode_stats: null buffer");
-    hipLaunchKernelGGL(episode_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, synth_view(state, *cfg).fin, (int)cfg->num_envs, out4,
-                       (int)reset);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_stats("synth", state, synth_view(state, *cfg).fin, cfg->num_envs, out4, reset, nullptr, stream);
 }
 
 extern "C" int pfa_synth_last_infos(void *state, const pfa_synth_config *cfg, uint8_t *finished, double *episode_return,
                                     int32_t *episode_length, double *score, pfa_stream_t stream) {
     if (int rc = check_synth_any(cfg)) return rc;
-    PFA_REQUIRE(state && finished && episode_return && episode_length && score, "synth.last_infos: null buffer");
-    hipLaunchKernelGGL(episode_infos_kernel, dim3((unsigned)((cfg->num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       synth_view(state, *cfg).fin, (int)cfg->num_envs, finished, episode_return, (int *)episode_length, score);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return launch_episode_infos("synth", state, synth_view(state, *cfg).fin, cfg->num_envs, finished, episode_return, episode_length,
+                                score, stream);
 }

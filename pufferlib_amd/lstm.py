@@ -131,10 +131,7 @@ class Engine:
                                         _lib.ptr(vec.terminals_u8), _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(value),
                                         stream), 'store_step')
             vec.ensure_tape(1)
-            _lib.check(L.pfa_squared_send(_lib.ptr(vec.state), C.byref(vec.cfg), _lib.ptr(actions), _lib.ptr(vec.obs_buf),
-                                          _lib.ptr(vec.rewards), _lib.ptr(vec.terminals_u8), _lib.ptr(vec.truncations_u8),
-                                          _lib.ptr(vec.masks_u8), stream), 'send')
-            vec.sends += 1
+            vec.device_send(actions)
         vec.sends -= T      # the caller (clean_pufferl.evaluate) accounts for the T sends of a rollout
 
     def invalidate_obs_cache(self):

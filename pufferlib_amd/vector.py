@@ -196,8 +196,8 @@ class _DeviceVecEnv:
     """Backend protocol (pufferlib/vector.py) over a device-resident env family with one observation value per env: live
     buffers as torch device tensors aliased by recv() (like Serial's numpy buffers, vector.py:158-162), RESET->RECV->SEND
     state machine, ``info_mode`` 'sync' (exact per-episode info dicts, one small D2H on the sends that finish episodes) or
-    'lazy' (recv() returns [], statistics through ``episode_stats``).  Subclasses provide the kernels:
-    ``_k_reset(seed)``, ``_k_send(actions)``, ``_k_stats(reset, out)``, ``_k_infos()`` and ``_finishing_send(sends)``."""
+    'lazy' (recv() returns [], statistics through ``episode_stats``).  Subclasses provide ``ABI``, the kernels
+    ``_k_reset(seed)`` and ``_k_send(actions)``, and ``_finishing_send(sends)``."""
     reset = reset
     step = step
     obs_stride = 16
@@ -207,6 +207,7 @@ class _DeviceVecEnv:
     fused_rollout_mlp = None
     PREFETCH = False        # whether the trainer draws the next rollout's reset tape (and action noise) on its side stream under a fused rollout
     FAMILY = ''
+    ABI = ''                # prefix of the family's entry points: ABI + '_episode_stats', ABI + '_last_infos'
     NAMES = ()
     DEFAULTS = ()
     SEEDED = False          # whether the env family reads the seeds async_reset is given
@@ -280,6 +281,18 @@ class _DeviceVecEnv:
 
     def _fin_ptrs(self):
         return _lib.ptr(self._fin), _lib.ptr(self._fin_ret), _lib.ptr(self._fin_len), _lib.ptr(self._fin_score)
+
+    def _state_args(self):
+        """How the family's entry points address the device state: (state, config) or, without a config struct, (state, env count)."""
+        cfg = getattr(self, 'cfg', None)
+        return _lib.ptr(self.state), (self.env_count if cfg is None else C.byref(cfg))
+
+    def _k_stats(self, reset, out):
+        _lib.check(getattr(self.L, self.ABI + '_episode_stats')(*self._state_args(), _lib.ptr(out), reset, _lib.stream_handle()),
+                   'episode_stats')
+
+    def _k_infos(self):
+        _lib.check(getattr(self.L, self.ABI + '_last_infos')(*self._state_args(), *self._fin_ptrs(), _lib.stream_handle()), 'last_infos')
 
     def async_reset(self, seed=42):
         self.flag = RECV
@@ -400,6 +413,7 @@ class Squared(_ResetTape, _DeviceVecEnv):
     fused rollout kernel for either policy; the trainer draws the next rollout's tape rounds on a side stream (``tape_event``)."""
     SEEDED = True
     CONFIG_NAME = 'Squared '
+    ABI = 'pfa_squared'
     ROLLOUT_LSTM = 'pfa_rollout_lstm_squared'
 
     def __init__(self, env_creators, env_args, env_kwargs, num_envs, obs_stride=None, **kwargs):
@@ -453,14 +467,6 @@ class Squared(_ResetTape, _DeviceVecEnv):
         _lib.check(self.L.pfa_squared_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                            _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_squared_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
-                                                    _lib.stream_handle()), 'episode_stats')
-
-    def _k_infos(self):
-        _lib.check(self.L.pfa_squared_last_infos(_lib.ptr(self.state), C.byref(self.cfg), *self._fin_ptrs(), _lib.stream_handle()),
-                   'last_infos')
-
     def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
         """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/rollout.hip) over the flat 128-wide parameters `fp`,
         or over `view`: the pfa_mlp_view of a Default of another width (general.tile_view).  The caller has drawn the tape rounds."""
@@ -508,6 +514,7 @@ class Stochastic(_DeviceVecEnv):
     """Device-resident vecenv of N ocean Stochastic envs (csrc/stochastic.hip).  The env draws no random numbers, so there
     is no reset tape and seeds only matter to the policy's noise rows; it has a fused rollout kernel for the MLP policy."""
     FAMILY, NAMES, DEFAULTS = 'stochastic', ('p',), (0.7,)
+    ABI = 'pfa_stochastic'
 
     def _spec(self, p):
         return StochasticSpec(p)
@@ -528,14 +535,6 @@ class Stochastic(_DeviceVecEnv):
     def _k_send(self, actions):
         _lib.check(self.L.pfa_stochastic_send(_lib.ptr(self.state), self.num_agents, self.p, self.horizon, _lib.ptr(actions),
                                               *self._live(), _lib.stream_handle()), 'send')
-
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_stochastic_episode_stats(_lib.ptr(self.state), self.num_agents, _lib.ptr(out), reset,
-                                                       _lib.stream_handle()), 'episode_stats')
-
-    def _k_infos(self):
-        _lib.check(self.L.pfa_stochastic_last_infos(_lib.ptr(self.state), self.num_agents, *self._fin_ptrs(), _lib.stream_handle()),
-                   'last_infos')
 
     def fused_rollout_mlp(self, fp, experience, noise, key, stream):
         """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/stochastic.hip)."""
@@ -566,6 +565,7 @@ class Memory(_ResetTape, _DeviceVecEnv):
     kernel (csrc/lstm_fused.hip); with the MLP policy it steps it through ``device_send`` (no host sync per step)."""
     FAMILY, NAMES, DEFAULTS = 'memory', ('mem_length', 'mem_delay'), (2, 2)
     SEEDED = True
+    ABI = 'pfa_memory'
     ROLLOUT_LSTM = 'pfa_rollout_lstm_memory'
 
     def _spec(self, mem_length, mem_delay):
@@ -598,14 +598,6 @@ class Memory(_ResetTape, _DeviceVecEnv):
         self.ensure_tape(1)
         _lib.check(self.L.pfa_memory_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                           _lib.stream_handle()), 'send')
-
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_memory_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
-                                                   _lib.stream_handle()), 'episode_stats')
-
-    def _k_infos(self):
-        _lib.check(self.L.pfa_memory_last_infos(_lib.ptr(self.state), C.byref(self.cfg), *self._fin_ptrs(), _lib.stream_handle()),
-                   'last_infos')
 
     def debug_solutions(self):
         """(solution digits per env as a bit mask, tape underrun flag) — test introspection."""
@@ -655,6 +647,7 @@ class Spaces(_ResetTape, _DeviceVecEnv):
     clean_pufferl.seed_everything does before it) followed by the initial resets.  clean_pufferl.evaluate steps it through
     ``device_send`` with packed action words (head h in bits 4h..4h+3), no host sync per step."""
     FAMILY, NAMES, DEFAULTS = 'spaces', (), ()
+    ABI = 'pfa_spaces'
     SEEDED = False
     obs_stride = 128
     ROUNDS_AT_RESET = 1     # async_reset shows round 0
@@ -692,14 +685,6 @@ class Spaces(_ResetTape, _DeviceVecEnv):
         self.ensure_tape(1)
         _lib.check(self.L.pfa_spaces_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                           _lib.stream_handle()), 'send')
-
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_spaces_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
-                                                   _lib.stream_handle()), 'episode_stats')
-
-    def _k_infos(self):
-        _lib.check(self.L.pfa_spaces_last_infos(_lib.ptr(self.state), C.byref(self.cfg), *self._fin_ptrs(), _lib.stream_handle()),
-                   'last_infos')
 
     def send(self, actions):
         """Actions [N, 2] = (flat, image) per env, as the reference's emulation hands them on (emulation.py:111-121)."""
@@ -745,6 +730,7 @@ class Synthetic(_DeviceVecEnv):
     of the reference tree, so there is nothing to be bit-exact with on the env side."""
     FAMILY, NAMES, DEFAULTS = 'synthetic', ('obs_values', 'num_actions', 'episode_length', 'obs_high'), (160, 7, 100, 10)
     SEEDED = True
+    ABI = 'pfa_synth'
     ROLLOUT_LSTM = 'pfa_rollout_lstm_synth'
 
     def _spec(self, obs_values, num_actions, episode_length, obs_high):
@@ -777,14 +763,6 @@ class Synthetic(_DeviceVecEnv):
     def _k_send(self, actions):
         _lib.check(self.L.pfa_synth_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(),
                                          _lib.stream_handle()), 'send')
-
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_synth_episode_stats(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), reset,
-                                                  _lib.stream_handle()), 'episode_stats')
-
-    def _k_infos(self):
-        _lib.check(self.L.pfa_synth_last_infos(_lib.ptr(self.state), C.byref(self.cfg), *self._fin_ptrs(), _lib.stream_handle()),
-                   'last_infos')
 
 
 def make_frames(framestack=4, num_actions=4, episode_length=100, height=84, width=84, channels_last=False, **kwargs):
@@ -863,6 +841,7 @@ class Bandit(_DeviceVecEnv):
     hard fixed seed, so the solution and the reward noise env i sees are the same in every episode: they are drawn here,
     once, with numpy's own legacy RandomState — the generator the reference calls — and the kernels keep the state machine."""
     FAMILY, NAMES, DEFAULTS = 'bandit', ('num_actions', 'reward_scale', 'reward_noise'), (10, 1, 1)
+    ABI = 'pfa_bandit'
 
     def _spec(self, num_actions, reward_scale, reward_noise):
         return BanditSpec(num_actions, reward_scale, reward_noise)
@@ -893,14 +872,6 @@ class Bandit(_DeviceVecEnv):
         _lib.check(self.L.pfa_bandit_send(_lib.ptr(self.state), self.num_agents, self.solution, self.scale, _lib.ptr(self.noise),
                                           _lib.ptr(actions), *self._live(), _lib.stream_handle()), 'send')
 
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_bandit_episode_stats(_lib.ptr(self.state), self.num_agents, _lib.ptr(out), reset,
-                                                   _lib.stream_handle()), 'episode_stats')
-
-    def _k_infos(self):
-        _lib.check(self.L.pfa_bandit_last_infos(_lib.ptr(self.state), self.num_agents, *self._fin_ptrs(), _lib.stream_handle()),
-                   'last_infos')
-
 
 def make_multiagent(**kwargs):
     """Env creator token with the signature of ocean.environment.make_multiagent (ocean/environment.py:76-79)."""
@@ -922,6 +893,7 @@ class Multiagent(_DeviceVecEnv):
     the env's own ``{1: {'score': r}, 2: {'score': r}}`` per env; ``episode_stats`` holds the per-slot sums behind the
     ``1/score`` / ``2/score`` means clean_pufferl.evaluate reports."""
     FAMILY, NAMES, DEFAULTS = 'multiagent', (), ()
+    ABI = 'pfa_multiagent'
     AGENTS_PER_ENV = 2
 
     def _spec(self):
@@ -942,10 +914,6 @@ class Multiagent(_DeviceVecEnv):
     def _k_send(self, actions):
         _lib.check(self.L.pfa_multiagent_send(_lib.ptr(self.state), self.env_count, _lib.ptr(actions), *self._live(),
                                               _lib.stream_handle()), 'send')
-
-    def _k_stats(self, reset, out):
-        _lib.check(self.L.pfa_multiagent_episode_stats(_lib.ptr(self.state), self.env_count, _lib.ptr(out), reset,
-                                                       _lib.stream_handle()), 'episode_stats')
 
     def _collect_infos(self):
         if not self._finishing_send(self.sends):

@@ -104,7 +104,7 @@ def test_fused_recurrent_rollout_equals_the_stepwise_protocol_pieces(n, L, D, T)
     from pufferlib_amd import clean_pufferl, cleanrl, models
     from test_gpu_ppo import _config
     hp = [2.5e-4, 0.99, 0.95, 0.1, 0.5, 0.1, 0.5, 0.01]
-    runs = []
+    runs, vecs = [], []
     for fused in (True, False):
         torch.manual_seed(4)
         vec = _make(n, L, D)
@@ -122,9 +122,15 @@ def test_fused_recurrent_rollout_equals_the_stepwise_protocol_pieces(n, L, D, T)
             out.append([x.clone() for x in (e.obs, e.actions, e.logprobs, e.values, e.rewards, e.dones, vec.obs_buf, vec.rewards,
                                             vec.terminals_u8, data.lstm_engine.lstm_h, data.lstm_engine.lstm_c)] + [stats])
         runs.append(out)
+        vecs.append(vec)
         assert vec.debug_solutions()[1] == 0
     for it in range(2):
         for k, (a, b) in enumerate(zip(runs[0][it][:-1], runs[1][it][:-1])):
             assert torch.equal(a, b), (it, k)
         assert runs[0][it][-1] == runs[1][it][-1]
     assert runs[0][1][-1]['episode_length'] == 2 * L + D - 1
+    if (n, L, D, T) == (50, 2, 2, 37):     # the episode finished by the last send, as last_infos reports it: one meaning on both paths
+        for vec in vecs:
+            vec._k_infos()
+        for k in ('_fin', '_fin_ret', '_fin_len', '_fin_score'):
+            assert torch.equal(getattr(vecs[0], k), getattr(vecs[1], k)), k

@@ -100,6 +100,11 @@ def test_fused_rollout_equals_stepwise_protocol_and_oracle_update():
     assert torch.equal(torch.stack(rew2, 1), e.rewards.view(n, horizon))
     assert torch.equal(torch.stack(done2, 1).float(), e.dones.view(n, horizon))
     assert torch.equal(torch.stack(lp2, 1), e.logprobs.view(n, horizon))
+    # "finished by the last send" means the same on both paths: send 128 is 27 sends past the finish, so nobody finished on it
+    vec._k_infos()
+    vec2._k_infos()
+    for k in ('_fin', '_fin_ret', '_fin_len', '_fin_score'):
+        assert torch.equal(getattr(vec, k), getattr(vec2, k)), k
     # env side vs the C oracle on the same actions
     ref = c_oracle.StochasticSerial(n, 0.7, 100)
     ref.async_reset(5)

@@ -64,7 +64,7 @@ def test_fused_recurrent_rollout_equals_the_stepwise_pieces(n, T):
     from pufferlib_amd import clean_pufferl, cleanrl, models
     from test_gpu_ppo import _config
     hp = [2.5e-4, 0.99, 0.95, 0.1, 0.5, 0.1, 0.5, 0.01]
-    runs = []
+    runs, vecs = [], []
     for fused in (True, False):
         torch.manual_seed(4)
         vec = _make(n, episode_length=7)
@@ -83,11 +83,17 @@ def test_fused_recurrent_rollout_equals_the_stepwise_pieces(n, T):
             out.append([x.clone() for x in (e.obs, e.actions, e.logprobs, e.values, e.rewards, e.dones, vec.obs_buf, vec.rewards,
                                             vec.terminals_u8, data.lstm_engine.lstm_h, data.lstm_engine.lstm_c)] + [stats])
         runs.append(out)
+        vecs.append(vec)
     for it in range(2):
         for k, (a, b) in enumerate(zip(runs[0][it][:-1], runs[1][it][:-1])):
             assert torch.equal(a, b), (it, k)
         assert runs[0][it][-1] == runs[1][it][-1]
     assert runs[0][1][-1]['episode_length'] == 7
+    if (n, T) == (50, 23):     # the episode finished by the last send, as last_infos reports it: one meaning on both paths
+        for vec in vecs:
+            vec._k_infos()
+        for k in ('_fin', '_fin_ret', '_fin_len', '_fin_score'):
+            assert torch.equal(getattr(vecs[0], k), getattr(vecs[1], k)), k
 
 
 def test_c3_shaped_update_vs_oracle_trainer_on_device_rollout():
