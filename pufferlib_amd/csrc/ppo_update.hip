@@ -100,6 +100,9 @@ struct GradShape {
     // the accumulators instead of a whole k-step of 8 MFMAs that multiplies three padding columns with it: KKM k-steps on MFMA
     static constexpr bool kFcol = COL && kPipe && KKU > 4 * KTM;
     static constexpr int kKKM = kFcol ? 4 * KTM : KKU;
+    // the producers' head biases and advantage sums are requested in front of the table build, not behind it: 8 registers live across
+    // the prologue, which the 128-float rows (all 512 registers taken) would pay for with scratch — they keep the order of use
+    static constexpr bool kEarlyScalars = DP <= 96;
     static_assert(!PERM || (kPipe && !MH), "the permuted head layout is wired into the pipelined single-head form");
     static constexpr int kThreads = grad_threads(DP);
     static constexpr size_t kLdsBytes = (size_t)Lds::kFloats * sizeof(float);
@@ -191,6 +194,25 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
     float *w2bt = w2t + L::kTabFloats;
     const MlpOffsets off = mlp_offsets(DP, a);
 
+    // The producers' head biases and the minibatch's two advantage sums are requested HERE, in front of the table loads (whose
+    // first consumer waits with a vmcnt that counts in order, so these have landed by then at no wait of their own).  Requested
+    // where they are used, behind the table build, they were a round trip of their own — vmcnt(0), then the f64 divisions and
+    // the square root — in front of the first X prefetch: three dependent trips to memory before tile 0, now two.
+    constexpr bool kEarly = GS::kEarlyScalars;
+    float bo[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    double adv_s1 = 0.0, adv_s2 = 0.0;
+    auto load_scalars = [&]() {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bo[r] = b2v_at(params, off, a, slot_output(PERM, 4 * g + r));
+        if (hp.norm_adv) {
+            adv_s1 = adv_stats[2 * map.mb];
+            adv_s2 = adv_stats[2 * map.mb + 1];
+        }
+    };
+    if constexpr (kEarly) {
+        if (producer) load_scalars();
+    }
+    PFA_STAMP(0, 6);   // entry (tools/probe_grad.py prologue: stamp 6 -> stamp 0 of tile 0)
     // Build the fragment tables.  All global loads of a thread are issued before the first LDS store so they pipeline.
     {
         constexpr int N1 = kMT * 64 * KS / kGradThreads, N2 = kMT * 64 * 4 / kGradThreads;
@@ -254,13 +276,11 @@ __global__ void __launch_bounds__(grad_threads(DP), grad_waves_per_simd(DP))
 
     if (producer) {
         // ------------------------------------------------------------------------------------------ producer
-        float bo[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bo[r] = b2v_at(params, off, a, slot_output(PERM, 4 * g + r));
+        if constexpr (!kEarly) load_scalars();
         // advantage normalisation (clean_pufferl.py:211-213): unbiased std over the GLOBAL minibatch
         float adv_mean = 0.0f, adv_den = 1.0f;
         if (hp.norm_adv) {
-            const double s1 = adv_stats[2 * map.mb], s2 = adv_stats[2 * map.mb + 1];
+            const double s1 = adv_s1, s2 = adv_s2;
             const double mean = s1 / global_rows;
             double var = (s2 - s1 * mean) / (global_rows - 1.0);
             var = var > 0.0 ? var : 0.0;
@@ -979,40 +999,50 @@ __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const floa
     // the norm in adam_clip_kernel's order: 256 strided partial sums, a butterfly per 64, then the four in order
     const int npart = (int)gridDim.x;
     double tot = 0.0;
+    // Lane ql collects the pieces of workgroups 64k + ql, k = 0 .. kPolls-1 (piece 64k + ql is term k / 4 of strided sum w = k % 4).
+    // Every poll is an agent-scope load the CU's caches cannot serve, a round trip of its own: all of a lane's polls are requested
+    // before the first is looked at, and a round re-requests only the words that do not show this launch's generation yet.
+    constexpr int kPolls = ((NL::kCount + 63) / 64 + 63) / 64;   // the launch has (kCount + 63) / 64 workgroups (GradShape::kReduceGrid)
+    unsigned long long w0[kPolls], w1[kPolls];
+    unsigned pending = 0;
+#pragma unroll
+    for (int k = 0; k < kPolls; ++k)
+        if (64 * k + ql < npart) pending |= 1u << k;
+    {
+        // The wait is bounded (advisor, round 4): the hand-off relies on every workgroup of the launch being resident at once.
+        // The host checks that once per shape (reduce_adam_coresident: occupancy x CUs >= workgroups, else the two-kernel
+        // form runs), but a device shared with other processes or masked down to fewer CUs can still starve a workgroup; then
+        // the wait runs out, the status word is raised (clean_pufferl.train raises) and the norm becomes NaN, which poisons the
+        // parameters instead of hanging the GPU.
+        long long t0 = 0;
+        int spin = 0;
+        while (true) {
+#pragma unroll
+            for (int k = 0; k < kPolls; ++k)
+                if (pending >> k & 1) {
+                    w0[k] = __hip_atomic_load(gw.words + 2 * (64 * k + ql), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    w1[k] = __hip_atomic_load(gw.words + 2 * (64 * k + ql) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+#pragma unroll
+            for (int k = 0; k < kPolls; ++k)
+                if ((pending >> k & 1) && (unsigned)(w0[k] >> 32) == gw.gen && (unsigned)(w1[k] >> 32) == gw.gen) pending &= ~(1u << k);
+            if (pending == 0) break;
+            __builtin_amdgcn_s_sleep(1);
+            if ((++spin & 255) == 0) {
+                const long long now = (long long)wall_clock64();
+                if (t0 == 0) t0 = now;
+                else if (now - t0 > gw.timeout_ticks) break;
+            }
+        }
+        if (pending != 0) __hip_atomic_store(gw.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 #pragma unroll
     for (int w = 0; w < kAdamThreads / 64; ++w) {
         double ss = 0.0;
-        for (int i = 64 * w + ql; i < npart; i += kAdamThreads) {
-            // The wait is bounded (advisor, round 4): the hand-off relies on every workgroup of the launch being resident at once.
-            // The host checks that once per shape (reduce_adam_coresident: occupancy x CUs >= workgroups, else the two-kernel
-            // form runs), but a device shared with other processes or masked down to fewer CUs can still starve a workgroup; then
-            // the wait runs out, the status word is raised (clean_pufferl.train raises) and the norm becomes NaN, which poisons the
-            // parameters instead of hanging the GPU.
-            unsigned long long w0, w1;
-            long long t0 = 0;
-            int spin = 0;
-            bool lost = false;
-            while (true) {
-                w0 = __hip_atomic_load(gw.words + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w1 = __hip_atomic_load(gw.words + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned)(w0 >> 32) == gw.gen && (unsigned)(w1 >> 32) == gw.gen) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spin & 255) == 0) {
-                    const long long now = (long long)wall_clock64();
-                    if (t0 == 0) t0 = now;
-                    else if (now - t0 > gw.timeout_ticks) {
-                        lost = true;
-                        break;
-                    }
-                }
-            }
-            if (lost) {
-                __hip_atomic_store(gw.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                ss = __builtin_nan("");
-                break;
-            }
-            ss += __longlong_as_double((long long)(((w1 & 0xffffffffull) << 32) | (w0 & 0xffffffffull)));
-        }
+#pragma unroll
+        for (int k = w; k < kPolls; k += kAdamThreads / 64)
+            if (64 * k + ql < npart) ss += __longlong_as_double((long long)(((w1[k] & 0xffffffffull) << 32) | (w0[k] & 0xffffffffull)));
+        if (pending != 0) ss = __builtin_nan("");   // the wait ran out on this lane: the butterfly carries the NaN to every lane
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
         tot += ss;

@@ -3,6 +3,11 @@
 Builds a -DPFA_PROBES variant of csrc/ppo_update.hip into tools/_probe/, then times the kernel at the bench
 shape (131 072 rows x 64 floats) with parts compiled out, to see where the time goes:
     python tools/probe_grad.py            (on the GPU box)
+
+    python tools/probe_grad.py build [name [path/to/ppo_update.hip]]   (no GPU needed) libprobe.so / libprobe_<name>.so, also from another
+                                                                       copy of the kernels (it needs the PFA_STAMP(0, 6) at entry)
+    python tools/probe_grad.py prologue [name ...]                     the prologue of workgroup 0, entry -> top of tile 0, five calls each
+    python tools/probe_grad.py trace | product                         the tile timeline of workgroup 0 | the product entry points timed
 """
 import ctypes as C
 import os
@@ -14,13 +19,18 @@ sys.path.insert(0, REPO)
 OUT = os.path.join(REPO, 'tools', '_probe')
 
 
-def build():
+def build(name=None, update_src=None):
+    """libprobe.so, or libprobe_<name>.so from another copy of ppo_update.hip (an older form of the kernel, to stamp it side by side)."""
+    from pufferlib_amd import _lib
+    _lib.build()      # the product's other objects: ppo_update.hip calls into igemm.hip (the product form switch)
     os.makedirs(OUT, exist_ok=True)
-    so = os.path.join(OUT, 'libprobe.so')
-    src = os.path.join(REPO, 'pufferlib_amd', 'csrc')
-    cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-DPFA_PROBES',
-           '-x', 'hip', os.path.join(src, 'ppo_update.hip'), os.path.join(src, 'common.cpp'), os.path.join(src, 'dist.cpp'), os.path.join(src, 'p2p.hip'), '-ldl', '-o', so]
-    subprocess.check_call(cmd)
+    so = os.path.join(OUT, f'libprobe_{name}.so' if name else 'libprobe.so')
+    obj = os.path.join(OUT, f'probe_{name or "grad"}.o')
+    subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-DPFA_PROBES', '-I', _lib.CSRC, '-x', 'hip',
+                           '-c', update_src or os.path.join(_lib.CSRC, 'ppo_update.hip'), '-o', obj])
+    objs = [os.path.join(_lib.LIB_DIR, os.path.splitext(s)[0] + '.o') for s in _lib.SOURCES if s != 'ppo_update.hip'] + [obj]
+    subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', so] + objs + ['-ldl'])
+    os.remove(obj)
     return so
 
 
@@ -211,9 +221,81 @@ def trace():
             print(f'  C wave {w} tile {j}: {r}   bwd {r[1]-r[0]} wait_alpha {r[2]-r[1]} wait_beta {r[3]-r[2]}')
 
 
+def prologue(names):
+    """The prologue of workgroup 0 (stamp 6 at entry -> stamp 0 at the top of tile 0: table build, the producers' scalars, the first X
+    prefetch issued, the barrier), per wave, over five calls, for each libprobe_<name>.so (libprobe.so without names); s_memtime ticks,
+    with the launch's event time and the span from entry to the last stamp next to them to size a tick."""
+    import numpy as np
+    import torch
+    from pufferlib_amd import _lib
+    N, T, DP, A, NMB = 4096, 128, 64, 8, 4
+    B = N * T
+    dev = 'cuda'
+    res = {}
+    for name in names or [None]:
+        L = C.CDLL(os.path.join(OUT, f'libprobe_{name}.so' if name else 'libprobe.so'))
+        g = torch.Generator(device=dev).manual_seed(0)
+        obs = torch.randn(B, DP, device=dev, generator=g)
+        obs[:, 49:] = 0
+        bufs = (torch.randint(0, A, (B,), device=dev, dtype=torch.int32, generator=g),
+                torch.full((B,), -2.0794, device=dev), torch.randn(B, device=dev, generator=g),
+                torch.randn(B, device=dev, generator=g), torch.zeros(B, device=dev),
+                torch.randn(B, device=dev, generator=g), torch.randn(B, device=dev, generator=g))
+        exp = _lib.Experience(obs.data_ptr(), *(t.data_ptr() for t in bufs), T)
+        dims = _lib.MlpDims(49, DP, 128, A)
+        hp = _lib.PpoHparams(.1, .1, .5, .01, 1, 1, NMB, 16)
+        P = 128 * DP + 128 + A * 128 + A + 128 + 1
+        params = torch.randn(P, device=dev, generator=g) * 0.05
+        grads = torch.zeros(P + 16, device=dev)
+        ws = torch.zeros(16 << 20, dtype=torch.uint8, device=dev)
+        stats = torch.tensor([[0.0, float(B // NMB)]] * NMB, dtype=torch.float64, device=dev)
+        L.pfa_probe_grad.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_void_p]
+        L.pfa_probe_set_trace.argtypes = [C.c_void_p, C.c_int]
+        J = 8
+        tr = torch.zeros(8, J, 8, dtype=torch.int64, device=dev)
+
+        def run():
+            assert L.pfa_probe_grad(C.byref(exp), B, 1, params.data_ptr(), C.byref(dims), C.byref(hp), stats.data_ptr(),
+                                    grads.data_ptr(), ws.data_ptr(), 0, None) == 0
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        launch_us = e0.elapsed_time(e1) / 20 * 1e3
+        calls = []
+        for rep in range(5):
+            tr.zero_()
+            torch.cuda.synchronize()
+            assert L.pfa_probe_set_trace(tr.data_ptr(), J) == 0
+            run()
+            torch.cuda.synchronize()
+            L.pfa_probe_set_trace(None, 0)
+            t = tr.cpu().numpy()
+            pro = t[:, 0, 0] - t[:, 0, 6]                     # per wave: 0-3 producers, 4-7 consumers
+            span = int(t[t > 0].max() - t[:, 0, 6].min())
+            calls.append(dict(producers=[int(x) for x in pro[:4]], consumers=[int(x) for x in pro[4:]], span=span))
+            print(f'{name or "probe"} call {rep}: prologue ticks producers {calls[-1]["producers"]} consumers {calls[-1]["consumers"]}'
+                  f'   entry -> last stamp {span}', flush=True)
+        per_call = [float(np.median(c['producers'])) for c in calls]
+        res[name or 'probe'] = dict(launch_us=round(launch_us, 2), calls=calls, producer_median_ticks=float(np.median(per_call)),
+                                    producer_calls_min_max=[min(per_call), max(per_call)])
+        print(f'--- {name or "probe"}: launch {launch_us:.1f} us by events; producers\' prologue, median over the waves: median of 5 calls '
+              f'{np.median(per_call):.0f} ticks, calls {min(per_call):.0f} .. {max(per_call):.0f}', flush=True)
+    import json
+    json.dump(res, open(os.path.join(OUT, 'probe_grad_prologue.json'), 'w'), indent=1)
+
+
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'build':
-        print(build())
+        print(build(*sys.argv[2:4]))
+    elif len(sys.argv) > 1 and sys.argv[1] == 'prologue':
+        prologue(sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == 'trace':
         trace()
     elif len(sys.argv) > 1 and sys.argv[1] == 'product':

@@ -123,8 +123,9 @@ def run(names):
                 print(f'{k:70s} {vals[0]}')
             else:
                 med, mx = float(np.median([a for a, _ in vals])), float(np.median([b for _, b in vals]))
-                table[k] = dict(median_us=round(med, 2), max_us=round(mx, 2))
-                print(f'{k:70s} median {med:6.2f}   max {mx:6.2f}')
+                per_call = [round(a, 3) for a, _ in vals]      # the five calls' own medians: their max - min is the phase's run-to-run spread
+                table[k] = dict(median_us=round(med, 2), max_us=round(mx, 2), calls_median_us=per_call)
+                print(f'{k:70s} median {med:6.2f}   max {mx:6.2f}   calls {min(per_call):.2f} .. {max(per_call):.2f}')
         res[name] = table
     json.dump(res, open(os.path.join(OUT, 'probe_handoff.json'), 'w'), indent=1)
 
