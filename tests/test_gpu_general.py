@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from adam_moments import assert_moments_match
+
 sys.path.insert(0, os.path.dirname(__file__))
 pytestmark = pytest.mark.gpu
 TOL = dict(rtol=1e-5, atol=1e-5)
@@ -246,6 +248,7 @@ def _check_update(data, pol, opol, tr, strip):
     sd = pol.state_dict()
     for k, arr in opol.state_arrays().items():
         np.testing.assert_allclose(sd[strip(k)].cpu().numpy(), arr, err_msg=k, **TOL)
+    assert_moments_match(data, tr)
 
 
 @pytest.mark.parametrize('hidden,d', [(64, 3), (256, 3), (512, 3), (512, 5), (256, 1), (64, 2)])

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from adam_moments import assert_moments_match
+
 pytestmark = pytest.mark.gpu
 
 TOL = dict(rtol=1e-5, atol=1e-5)    # north_star: within 1e-5 fp32
@@ -344,6 +346,7 @@ def test_recurrent_policy_trains_on_other_grid_sizes(d, nt):
     for k, w in want.items():
         full = ('policy.recurrent.' if k.endswith('_l0') else 'policy.policy.') + k
         np.testing.assert_allclose(sd[full].cpu().numpy(), w, rtol=1e-5, atol=1e-5, err_msg=k)
+    assert_moments_match(data, tr)
 
 
 def test_minigrid_shaped_160_byte_rows_vs_oracle_trainer():
@@ -393,6 +396,7 @@ def test_minigrid_shaped_160_byte_rows_vs_oracle_trainer():
         for k, arr in opol.state_arrays().items():
             key = ('policy.recurrent.' + k) if k.endswith('_l0') else ('policy.policy.' + k)
             np.testing.assert_allclose(sd[key].cpu().numpy(), arr, rtol=1e-5, atol=1e-5, err_msg=k)
+        assert_moments_match(data, tr)
     # the fused MLP kernels stop at 128 floats per row: the same rows behind a non-recurrent Default take the GEMM path (general.py)
     from pufferlib_amd import general
     d2 = clean_pufferl.create(_config(n, horizon, B // nmb, bptt, 2, B * 10, hp, seed=3), HostByteRows(n),

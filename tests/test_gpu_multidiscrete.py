@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from adam_moments import assert_moments_match
+
 sys.path.insert(0, os.path.dirname(__file__))
 pytestmark = pytest.mark.gpu
 
@@ -126,6 +128,7 @@ def test_three_heads_rollout_and_update_vs_oracle_trainer():
         sd = pol.state_dict()
         for k, arr in opol.state_arrays().items():
             np.testing.assert_allclose(sd['policy.' + k].cpu().numpy(), arr, rtol=1e-5, atol=1e-5, err_msg=k)
+        assert_moments_match(data, tr)
 
 
 def test_three_heads_with_the_recurrent_policy_vs_oracle_trainer():
@@ -170,6 +173,7 @@ def test_three_heads_with_the_recurrent_policy_vs_oracle_trainer():
         for k, arr in opol.state_arrays().items():
             key = ('policy.recurrent.' + k) if k.endswith('_l0') else ('policy.policy.' + k)
             np.testing.assert_allclose(sd[key].cpu().numpy(), arr, rtol=1e-5, atol=1e-5, err_msg=k)
+        assert_moments_match(data, tr)
 
 
 def test_unsupported_combinations_fail_loudly():

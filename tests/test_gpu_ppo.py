@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from adam_moments import assert_moments_match
+
 pytestmark = pytest.mark.gpu
 
 TOL = dict(rtol=1e-5, atol=1e-5)
@@ -148,6 +150,7 @@ def test_update_vs_torch_oracle(n, horizon, nmb, bptt, matrix_products):
     sd = pol.state_dict()
     for k, arr in opol.state_arrays().items():
         np.testing.assert_allclose(sd['policy.' + k].cpu().numpy(), arr, err_msg=k, **TOL)
+    assert_moments_match(data, tr)
 
 
 def test_fused_rollout_equals_stepwise_protocol():
@@ -339,6 +342,7 @@ def test_other_grid_sizes_rollout_and_update_vs_oracle(d, nt, n, horizon, nmb, b
     for k, arr in opol.state_arrays().items():
         np.testing.assert_allclose(sd['policy.' + k].cpu().numpy(), arr, err_msg=k, **TOL)
     np.testing.assert_allclose(L.explained_variance, Lo['explained_variance'], rtol=1e-3, atol=1e-4)
+    assert_moments_match(data, tr)
 
 
 def test_argument_errors_match_reference_messages():
@@ -506,6 +510,7 @@ def test_49_float_rows_with_other_action_counts_vs_oracle(num_actions, matrix_pr
     sd = pol.state_dict()
     for k, arr in opol.state_arrays().items():
         np.testing.assert_allclose(sd['policy.' + k].cpu().numpy(), arr, err_msg=k, **TOL)
+    assert_moments_match(data, tr)
 
 
 def test_early_gae_pass_is_the_same_update_and_yields_to_in_place_edits(monkeypatch):

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from adam_moments import assert_moments_match
+
 pytestmark = pytest.mark.gpu
 
 
@@ -139,6 +141,7 @@ def test_fused_rollout_equals_stepwise_protocol_and_oracle_update():
     sd = pol.state_dict()
     for k, arr in opol.state_arrays().items():
         np.testing.assert_allclose(sd['policy.' + k].cpu().numpy(), arr, rtol=1e-5, atol=1e-5, err_msg=k)
+    assert_moments_match(data, tr)
 
 
 def test_recurrent_policy_is_refused_and_wrong_creator_raises():

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from adam_moments import assert_moments_match
+
 sys.path.insert(0, os.path.dirname(__file__))
 pytestmark = pytest.mark.gpu
 
@@ -137,3 +139,4 @@ def test_c3_shaped_update_vs_oracle_trainer_on_device_rollout():
         for k, arr in opol.state_arrays().items():
             key = ('policy.recurrent.' + k) if k.endswith('_l0') else ('policy.policy.' + k)
             np.testing.assert_allclose(sd[key].cpu().numpy(), arr, rtol=1e-5, atol=1e-5, err_msg=k)
+        assert_moments_match(data, tr)
