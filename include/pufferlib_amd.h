@@ -769,6 +769,11 @@ int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t ba
  *                          for MultiDiscrete), log-prob, entropy (nullable), value
  *   pfa_heads_rows_eval    sample_logits with GIVEN actions (cleanrl.py:38-44): the training-mode policy(obs, action=...) of
  *                          frameworks.cleanrl.Policy / RecurrentPolicy (cleanrl.py:60-66,87-93)
+ *   pfa_heads_rows_eval_backward  its backward for arbitrary upstream gradients g_logprob / g_entropy / g_value [rows] (each nullable
+ *                          = zero): per head, p = softmax, dz_j = g_logprob (1[j = a] - p_j) - g_entropy p_j (log p_j + H), all heads
+ *                          of a row sharing its three numbers; column num_actions = g_value; dout [rows][ldd] as for
+ *                          pfa_heads_rows_loss (num_actions < j < num_out zeroed, columns >= num_out untouched).  No atomics: one
+ *                          thread owns a row, bit-reproducible
  *   pfa_heads_rows_loss    PPO loss (clean_pufferl.py:202-238) of the chunk's rows and d loss / d out into dout [rows][ldd]
  *                          (columns >= num_out untouched, num_actions < j < num_out zeroed); chunk row r is minibatch row q0 + r, or,
  *                          with time_major_rows = R > 0, row t * R + k is minibatch row q0 + k * bptt_horizon + t;
@@ -782,6 +787,9 @@ int pfa_heads_rows_sample(const float *out, int32_t ld, int64_t rows, int32_t nu
                           float *value, pfa_stream_t stream);
 int pfa_heads_rows_eval(const float *out, int32_t ld, int64_t rows, int32_t num_actions, uint32_t heads, const int64_t *actions,
                         float *logprob, float *entropy, float *value, pfa_stream_t stream);
+int pfa_heads_rows_eval_backward(const float *out, int32_t ld, int64_t rows, int32_t num_actions, uint32_t heads, const int64_t *actions,
+                                 const float *g_logprob, const float *g_entropy, const float *g_value, float *dout, int32_t ldd,
+                                 int32_t num_out, pfa_stream_t stream);
 size_t pfa_heads_rows_loss_workspace_bytes(int64_t rows);
 int pfa_heads_rows_loss(const float *out, int32_t ld, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0,
                         int64_t rows, int32_t time_major_rows, int32_t num_actions, uint32_t heads, const pfa_ppo_hparams *hp,

@@ -284,6 +284,7 @@ _SIGNATURES = {
     'pfa_ppo_mlp_grad_path': (C.c_int, [C.POINTER(MlpDims), C.c_int64]),
     'pfa_heads_rows_sample': (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
     'pfa_heads_rows_eval': (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, P, P, P, P, P]),
+    'pfa_heads_rows_eval_backward': (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, P, P, P, P, P, C.c_int32, C.c_int32, P]),
     'pfa_heads_rows_loss_workspace_bytes': (C.c_size_t, [C.c_int64]),
     'pfa_heads_rows_loss': (C.c_int, [P, C.c_int32, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                       C.c_uint32, C.POINTER(PpoHparams), P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int32, P, P]),

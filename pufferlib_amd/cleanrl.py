@@ -4,8 +4,10 @@
 multinomial draw is argmax(softmax(logits)/q) with q ~ Exp(1) from either an explicit ``noise`` tensor (parity with
 torch.multinomial given its exponential draw) or the Philox stream keyed by ``seed`` (include/pufferlib_amd.h).
 ``policy(obs, action=...)`` (training mode, cleanrl.py:60-66,87-93) returns the log-probability of the GIVEN actions, the entropy and
-the value through the GEMM path (pufferlib_amd.general.Evaluator) for every policy shape; no autograd graph is attached — the
-gradients of these quantities are computed by pufferlib_amd.clean_pufferl.train()'s kernels.
+the value through the GEMM path (pufferlib_amd.general.Evaluator) for every policy shape.  By default these are plain tensors (the
+gradients of clean_pufferl.train() are computed by its own kernels); ``Policy(policy, autograd=True)`` / ``RecurrentPolicy(policy,
+autograd=True)`` attach an autograd graph to logprob, entropy and value of that call, so that a loss built from them in torch ops trains
+the policy with ``loss.backward()``, ``clip_grad_norm_`` and any torch optimizer over ``policy.parameters()`` (general.Evaluator).
 
 Policy shapes outside the fused kernels' envelope (Default(hidden_size != 128), observation rows wider than 128 / 160 floats, more
 than 15 logits, LSTMWrapper sizes other than (128, 128), LSTMWrapper over the NatureCNN, the NatureCNN with 16 .. 63 actions) adopt a
@@ -109,12 +111,38 @@ def _evaluator(self, device, recurrent):
         # every call (so does a policy used on its own, whose tensors anybody may write).  A trainer's GEMM-path Net is told when its
         # weights change: the optimizer step (Engine.clip_adam), the checkpoint loader and load_state_dict (post hook) bump its version.
         self._evaluator.net.version += 1
+    if getattr(self, 'autograd', False):    # somebody's torch optimizer may step the nn.Parameters themselves: their version counters join the pack key
+        self._evaluator.net.watch = tuple(general.module_parameters(self._flat).values())
     return self._evaluator
 
 
+def _check_autograd(policy_module, autograd):
+    """autograd=True is built for MLP encoders; said at construction, where no GPU is needed."""
+    if autograd and (find_cnn(policy_module) is not None or find_resnet(policy_module) is not None):
+        raise NotImplementedError('autograd=True with a convolutional encoder (models.Convolutional, models.ProcgenResnet): autograd through '
+                                  'policy(obs, action=...) is built for models.Default, alone or under LSTMWrapper; the conv encoders\' backward '
+                                  'is not wired to it — train them with clean_pufferl.train()')
+    return bool(autograd)
+
+
+def _grad_params(self, action):
+    """The nn.Parameters general.Evaluator.forward attaches its graph to, or None for the plain path: opted in, actions given, grad
+    mode on.  (Called after _evaluator(), which adopted the buffer.)"""
+    if not (getattr(self, 'autograd', False) and action is not None and torch.is_grad_enabled()):
+        return None
+    from . import general
+    return general.module_parameters(self._flat)
+
+
 class Policy(torch.nn.Module):
-    def __init__(self, policy, seed=0):
+    """frameworks.cleanrl.Policy.  autograd=False (default): every call returns plain tensors.  autograd=True: ``policy(obs, action=a)``
+    with grad mode on returns the same values, bit for bit, with logprob, entropy and value carrying a grad_fn whose backward
+    accumulates into .grad of every module parameter (torch semantics: adds to an existing .grad, parameter-shaped, on the device);
+    under torch.no_grad() or with action=None (sampling) the plain path runs.  Double backward is not built."""
+
+    def __init__(self, policy, seed=0, autograd=False):
         super().__init__()
+        self.autograd = _check_autograd(policy, autograd)
         self.policy = policy
         self.noise_seed = int(seed)
         self.noise_step = 0
@@ -190,7 +218,7 @@ class Policy(torch.nn.Module):
             if action is None and noise is None:
                 key = _lib.NoiseKey(self.noise_seed, self.noise_step)
                 self.noise_step += 1
-            a, logprob, entropy, value, _ = ev.forward(x2, action=action, noise=noise, key=key)
+            a, logprob, entropy, value, _ = ev.forward(x2, action=action, noise=noise, key=key, params=_grad_params(self, action))
             return (action if action is not None else self._flat.unpack_actions(a)), logprob, entropy, value
         if find_cnn(self.policy) is not None:
             return self._forward_cnn(x2, rows, noise)
@@ -284,10 +312,16 @@ class RecurrentPolicy(torch.nn.Module):
     """frameworks.cleanrl.RecurrentPolicy (pufferlib/frameworks/cleanrl.py:69-93) over the HIP LSTM path.
 
     ``policy(obs, state)`` (rollout mode) returns (actions, logprob, entropy, value, (h, c)) with state tensors of shape
-    (1, rows, 128) like nn.LSTM.  The training-mode forward lives in pufferlib_amd.clean_pufferl.train."""
+    (1, rows, 128) like nn.LSTM.  The training-mode forward of train() lives in pufferlib_amd.clean_pufferl.train.
 
-    def __init__(self, policy, seed=0):
+    autograd=True: as for Policy — ``policy(obs, state, action=a)`` with grad mode on returns (action, logprob, entropy, value, state)
+    with a grad_fn on logprob, entropy and value.  No gradient flows into the incoming ``state`` or out of the returned one (plain
+    tensors): the reference's trainer detaches the state between minibatches the same way (clean_pufferl.py:188-191), so back-propagation
+    through time covers the TT steps of one call."""
+
+    def __init__(self, policy, seed=0, autograd=False):
         super().__init__()
+        self.autograd = _check_autograd(policy, autograd)
         self.policy = policy
         self.noise_seed = int(seed)
         self.noise_step = 0
@@ -334,7 +368,8 @@ class RecurrentPolicy(torch.nn.Module):
                 key = _lib.NoiseKey(self.noise_seed, self.noise_step)
                 self.noise_step += 1
             a, logprob, entropy, value, new_state = ev.forward(x, action=action, state=state, noise=noise, key=key,
-                                                               obs_rank=len(obs_shape) if obs_shape is not None else None)
+                                                               obs_rank=len(obs_shape) if obs_shape is not None else None,
+                                                               params=_grad_params(self, action))
             return (action if action is not None else self._flat.unpack_actions(a)), logprob, entropy, value, new_state
         rows = x.shape[0]
         x2 = x.reshape(rows, -1)

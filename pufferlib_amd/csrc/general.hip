@@ -8,6 +8,8 @@
 //                      (columns < A the logits of all heads, column A the value): action, log-prob, entropy, value
 //   heads_rows_eval    sample_logits with GIVEN actions (cleanrl.py:38-44): log-prob, entropy, value — the training-mode call
 //                      policy(obs, action=...) of frameworks.cleanrl.Policy / RecurrentPolicy (cleanrl.py:60-66,87-93)
+//   heads_rows_eval_backward  d (head outputs) of that call for arbitrary upstream gradients of (log-prob, entropy, value): the
+//                      autograd path of policy(obs, action=...) (general.Evaluator with autograd=True)
 //   heads_rows_loss    the PPO loss of clean_pufferl.py:202-238 for the rows of a chunk and d loss / d (head outputs)
 //   lstm_cell_fwd/bwd  the element-wise part of one nn.LSTM step (gate order i, f, g, o: models.py:76) and of its
 //                      back-propagation through time
@@ -114,6 +116,47 @@ __global__ void __launch_bounds__(256) heads_rows_eval_kernel(const float *out, 
     logprob[row] = lp;
     entropy[row] = ent;
     value[row] = o[hs.a];
+}
+
+// Backward of heads_rows_eval for ARBITRARY upstream gradients (the autograd path of policy(obs, action=...)): per row, with
+// p = softmax(z_h) and H_h = -sum p log p of head h,
+//   dz_j = g_logprob (1[j = a_h] - p_j) - g_entropy p_j (log p_j + H_h)        d value = g_value
+// All heads of a row share its three upstream numbers (cleanrl.py:38-47 sums log-probability and entropy over the heads).  A null
+// upstream pointer is a zero gradient.  The softmax is heads_rows_eval_kernel's, operation for operation, so both agree on p.  One
+// thread owns its row of dout: plain stores, nothing summed across threads.
+__global__ void __launch_bounds__(256) heads_rows_eval_bwd_kernel(const float *out, int ld, long long rows, HeadSpec hs, const long long *actions,
+                                                                 const float *g_logprob, const float *g_entropy, const float *g_value,
+                                                                 float *dout, int ldd, int no) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const float *o = out + row * ld;
+    float *d = dout + row * ldd;
+    const long long packed = actions[row];
+    const float g_lp = g_logprob ? g_logprob[row] : 0.0f, g_ent = g_entropy ? g_entropy[row] : 0.0f;
+    int start = 0;
+    const int nh = hs.count();
+    for (int h = 0; h < nh; ++h) {
+        const int sz = hs.size(h);
+        float mx = -INFINITY;
+        for (int j = 0; j < sz; ++j) mx = fmaxf(mx, o[start + j]);
+        float se = 0.0f;
+        for (int j = 0; j < sz; ++j) se += expf(o[start + j] - mx);
+        const float lse = mx + logf(se);
+        float he = 0.0f;
+        for (int j = 0; j < sz; ++j) {
+            const float nl = o[start + j] - lse;
+            he += -nl * (expf(o[start + j] - mx) / se);
+        }
+        int act = hs.heads == 0 ? (int)packed : (int)((packed >> (4 * h)) & 15);
+        act = act < sz && act >= 0 ? act : 0;
+        for (int j = 0; j < sz; ++j) {
+            const float nl = o[start + j] - lse, p = expf(o[start + j] - mx) / se;
+            d[start + j] = g_lp * ((j == act ? 1.0f : 0.0f) - p) - g_ent * p * (nl + he);
+        }
+        start += sz;
+    }
+    d[hs.a] = g_value ? g_value[row] : 0.0f;
+    for (int j = hs.a + 1; j < no; ++j) d[j] = 0.0f;
 }
 
 __global__ void __launch_bounds__(256) heads_rows_loss_kernel(const float *out, int ld, long long rows, RowMap map, long long q0, int R,
@@ -362,6 +405,20 @@ extern "C" int pfa_heads_rows_eval(const float *out, int32_t ld, int64_t rows, i
     if (rows == 0) return 0;
     hipLaunchKernelGGL(heads_rows_eval_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (int)ld,
                        (long long)rows, HeadSpec{(int)num_actions, heads}, (const long long *)actions, logprob, entropy, value);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pfa_heads_rows_eval_backward(const float *out, int32_t ld, int64_t rows, int32_t num_actions, uint32_t heads,
+                                            const int64_t *actions, const float *g_logprob, const float *g_entropy, const float *g_value,
+                                            float *dout, int32_t ldd, int32_t num_out, pfa_stream_t stream) {
+    PFA_REQUIRE(out && actions && dout && rows >= 0, "heads_rows_eval_backward: null buffer");
+    if (int rc = check_heads(num_actions, heads, ld)) return rc;
+    PFA_REQUIRE(num_out > num_actions && num_out <= kGenMaxOut && ldd >= num_out, "heads_rows_eval_backward: num_out must cover the value column");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(heads_rows_eval_bwd_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (int)ld,
+                       (long long)rows, HeadSpec{(int)num_actions, heads}, (const long long *)actions, g_logprob, g_entropy, g_value, dout,
+                       (int)ldd, (int)num_out);
     PFA_LAUNCH_CHECK();
     return 0;
 }

@@ -186,6 +186,7 @@ class Net:
             self.wcatT = torch.zeros(I + Hl, 4 * Hl, device=dev)
         self.packed_version = None
         self.version = 0
+        self.watch = ()
         self._probe = next(iter(views.values()))     # any parameter view: views of one flat buffer share its in-place version counter
 
     def pack(self):
@@ -193,7 +194,9 @@ class Net:
         # `version` is bumped by the trainer's own writers (optimizer step kernels, checkpoint loader: raw-pointer writes torch does
         # not see); torch-level in-place writes to any parameter view (p.copy_(), load_state_dict on an inner module, dist.broadcast,
         # a torch optimizer) bump the shared version counter of the flat buffer the views alias — both are part of the key
-        key = (self.version, self._probe._version)
+        # — and so are the version counters of the module's nn.Parameters where somebody's torch optimizer steps those directly
+        # (`watch`, set by a cleanrl policy built with autograd=True: a Parameter re-pointed with p.data = view counts its own writes)
+        key = (self.version, self._probe._version) + tuple(p._version for p in self.watch)
         if self.packed_version == key:
             return
         v, nm = self.views, self.names
@@ -291,13 +294,53 @@ def net_for_flat(fp):
     return Net('mlp', views, names, fp.obs_dim, round_up(fp.obs_dim, 16), H, fp.num_actions, fp.dims.heads, lstm_sizes, fp.flat.device)
 
 
+def module_parameters(params):
+    """name -> nn.Parameter of the policy module behind a GeneralParams / models.FlatParams buffer, keyed like the views the Net
+    over that buffer reads (GeneralParams: named_parameters() names; FlatParams: the Default's names + 'recurrent.<lstm name>')."""
+    if isinstance(params, GeneralParams):
+        return dict(params.module.named_parameters())
+    out = {name: params.mlp.get_parameter(name) for name in params.views}
+    for name in params.lstm_views:
+        out['recurrent.' + name] = getattr(params.lstm, name)
+    return out
+
+
+class _EvalGrad(torch.autograd.Function):
+    """logprob, entropy, value of Evaluator.forward as functions of the module parameters: the forward is the plain launch sequence
+    (keeping what the backward reads), the backward Evaluator.backward.  The parameters are the only tensor inputs, so autograd itself
+    accumulates into their .grad.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, ev, call, *params):
+        packed, logprob, entropy, value, new_state, ctx.tape = ev._run(keep=True, **call)
+        ctx.ev = ev
+        ctx.set_materialize_grads(False)            # an output the loss does not use arrives as None: a null pointer to the kernel
+        call['rest'] = (packed, new_state)          # not functions of the parameters as far as autograd is told: handed round it
+        return logprob, entropy, value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logprob, g_entropy, g_value):
+        grads = ctx.ev.backward(ctx.tape, g_logprob, g_entropy, g_value)
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
 class Evaluator:
     """policy(obs, action=...) — sample_logits with given actions (cleanrl.py:38-44) behind Policy.forward / RecurrentPolicy.forward
-    (cleanrl.py:60-66,87-93): (action, logprob, entropy, value[, state]).  No autograd graph is attached: the gradients of these
-    quantities live in clean_pufferl.train()'s kernels."""
+    (cleanrl.py:60-66,87-93): (action, logprob, entropy, value[, state]).
+
+    By default no autograd graph is attached (plain tensors; the gradients of clean_pufferl.train() live in its own kernels).  Called
+    with `params` (name -> nn.Parameter, module_parameters(); cleanrl.Policy(..., autograd=True) does so when grad mode is on and
+    actions are given) logprob, entropy and value carry a grad_fn: the same launches compute the same bits, the buffers the backward
+    reads are kept (the padded observation rows, xh, every step's activated gates, c, the head input and output), and backward() runs
+    pfa_heads_rows_eval_backward and then the GEMM / BPTT sequence of Engine.update on rows in (b, t) order, one chunk, into gradients
+    of the parameters' torch shapes, which autograd accumulates into .grad.  No gradient flows into the incoming `state` or out of the
+    returned one — the reference's trainer detaches it the same way (clean_pufferl.py:188-191) — nor into the observations; the
+    backward is not itself differentiable.  MLP encoders only: the conv encoder's backward is not wired to this path."""
 
     def __init__(self, net):
         self.net = net
+        self.param_order = list(net.views)          # the order the parameters enter _EvalGrad in, and backward() answers in
 
     def _rows(self, x):
         net = self.net
@@ -311,10 +354,26 @@ class Evaluator:
         src[:, :net.obs_dim] = x2.float()
         return src, rows
 
-    def forward(self, x, action=None, state=None, noise=None, key=None, row_offset=0, obs_rank=None):
+    def forward(self, x, action=None, state=None, noise=None, key=None, row_offset=0, obs_rank=None, params=None):
         """x: (B, obs...) or, for a recurrent policy, (B, TT, obs...) like LSTMWrapper.forward (models.py:84-111), told apart by
         `obs_rank` = len(single_observation_space.shape) (None: x is (B, ...) with one step); state (h, c) of shape (1, B, Hl) or
-        None.  action None -> samples (noise [rows][A] or the Philox key)."""
+        None.  action None -> samples (noise [rows][A] or the Philox key).  params (name -> nn.Parameter for every view of the net;
+        needs given actions): logprob, entropy and value come with a grad_fn (class docstring)."""
+        call = dict(x=x, action=action, state=state, noise=noise, key=key, row_offset=row_offset, obs_rank=obs_rank)
+        if params is None or x.shape[0] == 0:
+            return self._run(**call)[:5]
+        if action is None:
+            raise ValueError('Evaluator.forward(params=...): the autograd path scores GIVEN actions')
+        if self.net.kind != 'mlp':
+            raise NotImplementedError('autograd through policy(obs, action=...) is built for MLP encoders (models.Default, alone or under '
+                                      'LSTMWrapper): the backward of the conv encoder is not wired to it; use train()')
+        logprob, entropy, value = _EvalGrad.apply(self, call, *(params[name] for name in self.param_order))
+        packed, new_state = call['rest']
+        return packed, logprob, entropy, value, new_state
+
+    def _run(self, x, action=None, state=None, noise=None, key=None, row_offset=0, obs_rank=None, keep=False):
+        """The launch sequence of forward().  keep: also return what backward() reads (every LSTM step's activated gates in a buffer
+        of their own instead of one overwritten step after step; otherwise the same launches on the same operands)."""
         net = self.net
         net.pack()
         L = _lib.lib()
@@ -342,9 +401,9 @@ class Evaluator:
                 xh[0, :, I:].copy_(state[0].reshape(B, Hl))
                 c[0].copy_(state[1].reshape(B, Hl))
             hs = torch.empty(TT, B, Hl, device=dev)
-            gates = torch.empty(B, 4 * Hl, device=dev)
+            gates = torch.empty(TT if keep else 1, B, 4 * Hl, device=dev)
             for t in range(TT):
-                net.lstm_step(xh[t], gates, c[t], c[t + 1], hs[t], Hl, xh[t + 1, :, I:], I + Hl)
+                net.lstm_step(xh[t], gates[t if keep else 0], c[t], c[t + 1], hs[t], Hl, xh[t + 1, :, I:], I + Hl)
             head_in = torch.empty(rows, Hl, device=dev)
             rows_perm(hs, Hl, head_in, Hl, rows, Hl, B, TT, False)           # back to (b, t) row order, like models.py:107-108
             new_state = (hs[TT - 1].unsqueeze(0).clone(), c[TT].unsqueeze(0).clone())
@@ -383,7 +442,73 @@ class Evaluator:
             packed = packed.contiguous()
             _lib.check(L.pfa_heads_rows_eval(_lib.ptr(out), NO, rows, net.A, net.heads, _lib.ptr(packed), _lib.ptr(logprob), _lib.ptr(entropy),
                                              _lib.ptr(value), _lib.stream_handle()), 'heads_rows_eval')
-        return packed, logprob, entropy, value.unsqueeze(1), new_state
+        tape = None
+        if keep:         # (the transposed operand copies as they are NOW: a later call re-packs the net's own in place)
+            tape = dict(rows=rows, B=B, TT=TT, src=src, head_in=head_in, out=out, packed=packed, w2vT=net.w2vT.clone())
+            if net.lstm:
+                tape.update(xh=xh, gates=gates, c=c, wcatT=net.wcatT.clone())
+        return packed, logprob, entropy, value.unsqueeze(1), new_state, tape
+
+    def backward(self, tape, g_logprob, g_entropy, g_value):
+        """d (sum of g . outputs) / d parameters for one kept forward, in self.param_order and the parameters' shapes; a None
+        upstream gradient is zero.  Engine.update's sequence from dout on, with the rows in (b, t) order and all in one chunk."""
+        net, dev = self.net, self.net.dev
+        L = _lib.lib()
+        stream = _lib.stream_handle()
+        rows, B, TT = tape['rows'], tape['B'], tape['TT']
+        F, FH, NO, Kp = net.F, net.FH, net.NO, net.Kp
+        g_logprob, g_entropy, g_value = (None if g is None else g.detach().to(device=dev, dtype=torch.float32).reshape(rows).contiguous()
+                                         for g in (g_logprob, g_entropy, g_value))
+        head_in, out = tape['head_in'], tape['out']
+        sizes = [L.pfa_igemm_weights_workspace_bytes(rows, FH, NO), L.pfa_igemm_weights_workspace_bytes(rows, Kp, F)]
+        if net.lstm:
+            sizes.append(L.pfa_igemm_weights_workspace_bytes(rows, net.lstm[0] + net.lstm[1], 4 * net.lstm[1]))
+        ws = torch.empty(max(sizes), dtype=torch.uint8, device=dev)
+        dout = torch.empty(rows, NO, device=dev)
+        _lib.check(L.pfa_heads_rows_eval_backward(_lib.ptr(out), NO, rows, net.A, net.heads, _lib.ptr(tape['packed']), _lib.ptr(g_logprob),
+                                                  _lib.ptr(g_entropy), _lib.ptr(g_value), _lib.ptr(dout), NO, NO, stream), 'heads_rows_eval_backward')
+        g2v, gb2v = torch.empty(NO, FH, device=dev), torch.empty(NO, device=dev)
+        gemm_weights(head_in, FH, rows, FH, dout, NO, NO, g2v, False, gb2v, ws)
+        dpre = torch.empty(rows, F, device=dev)
+        if net.lstm:
+            I, Hl = net.lstm
+            ldx = I + Hl
+            xh, gates, c = tape['xh'], tape['gates'], tape['c']
+            dhead_bt = torch.empty(rows, Hl, device=dev)
+            gemm_rows(dout, NO, rows, NO, tape['w2vT'], NO, FH, dhead_bt, FH)
+            dhead = torch.empty(TT, B, Hl, device=dev)
+            rows_perm(dhead_bt, Hl, dhead, Hl, rows, Hl, B, TT, True)                 # (b, t) rows -> time-major, like the features
+            # ---- back-propagation through time (no gradient leaves through the incoming state) --------------------------------------
+            dG = torch.empty(TT, B, 4 * Hl, device=dev)
+            dxh = torch.empty(TT, B, ldx, device=dev)
+            dc = torch.zeros(B, Hl, device=dev)
+            for t in range(TT - 1, -1, -1):
+                dh_b = dxh[t + 1, :, I:] if t < TT - 1 else None
+                _lib.check(L.pfa_lstm_cell_backward(_lib.ptr(dhead[t]), Hl, _lib.ptr(dh_b), ldx, _lib.ptr(dc), _lib.ptr(gates[t]), _lib.ptr(c[t]),
+                                                    _lib.ptr(c[t + 1]), _lib.ptr(dG[t]), B, Hl, stream), 'lstm_cell_backward')
+                gemm_rows(dG[t], 4 * Hl, B, 4 * Hl, tape['wcatT'], 4 * Hl, ldx, dxh[t], ldx)
+            gcat, gbcat = torch.empty(4 * Hl, ldx, device=dev), torch.empty(4 * Hl, device=dev)
+            gemm_weights(xh, ldx, rows, ldx, dG, 4 * Hl, 4 * Hl, gcat, False, gbcat, ws)
+            # the x columns of dxh, masked by relu' of the features (the x columns of xh), back in the (b, t) order of the observation rows
+            rows_perm(dxh, ldx, dpre, F, rows, F, B, TT, False, act=xh, lda=ldx)
+        else:
+            gemm_rows(dout, NO, rows, NO, tape['w2vT'], NO, FH, dpre, F, EPI_MASK, None, head_in, F)
+        g1, gb1 = torch.empty(F, Kp, device=dev), torch.empty(F, device=dev)
+        gemm_weights(tape['src'], Kp, rows, Kp, dpre, F, F, g1, False, gb1, ws)
+        # ---- the packed gradients in the parameters' shapes (each its own memory: autograd may adopt them as .grad) -------------------
+        nm, g = net.names, {}
+        g[nm['enc_w']] = g1[:, :net.obs_dim].contiguous()
+        g[nm['enc_b']] = gb1
+        r = 0
+        for w, b in nm['actors']:
+            n = net.views[w].shape[0]
+            g[w], g[b] = g2v[r:r + n].clone(), gb2v[r:r + n].clone()
+            r += n
+        g[nm['value_w']], g[nm['value_b']] = g2v[r:r + 1].clone(), gb2v[r:r + 1].clone()
+        if net.lstm:
+            g[nm['w_ih']], g[nm['w_hh']] = gcat[:, :I].contiguous(), gcat[:, I:].contiguous()
+            g[nm['b_ih']], g[nm['b_hh']] = gbcat, gbcat.clone()
+        return [g[name].view(net.views[name].shape) for name in self.param_order]
 
     def _encode(self, src, rows, out, ldo):
         if self.net.kind == 'cnn':
