@@ -764,7 +764,11 @@ int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t ba
  * hidden_size / observation width, LSTMWrapper with any (input_size, hidden_size) (models.py:24,65) and the recurrent
  * NatureCNN of environments/atari/torch.py:4-6 run as sequences of pfa_igemm_rows / pfa_igemm_weights launches plus these
  * row-wise kernels on the head outputs `out` [rows][ld] (columns < num_actions: the logits of all heads side by side, column
- * num_actions: the value).  num_actions <= 63; heads: the nibble packing of pfa_mlp_dims.heads, 0 = one Discrete head (which may then use all 63).
+ * num_actions: the value).  heads: the nibble packing of pfa_mlp_dims.heads (up to 8 heads of up to 15 choices: num_actions <= 120), or
+ * 0 = one Discrete head of 1 .. 1024 logits.  Up to 63 logits and every MultiDiscrete shape run one thread per row; one Discrete head
+ * of 64 .. 1024 logits runs one wavefront per row (lane l holds logits l, l + 64, ... in registers after one coalesced read of the row;
+ * all four kernels share one softmax routine, so pfa_heads_rows_eval returns, bit for bit, the log-probability pfa_heads_rows_sample
+ * gave the action it sampled from the same row).  The entry points choose; both forms are free of atomics and bit-reproducible.
  *   pfa_heads_rows_sample  sample_logits with action=None (frameworks/cleanrl.py:25-47): actions (packed like pfa_mlp_dims.heads
  *                          for MultiDiscrete), log-prob, entropy (nullable), value
  *   pfa_heads_rows_eval    sample_logits with GIVEN actions (cleanrl.py:38-44): the training-mode policy(obs, action=...) of
@@ -773,7 +777,7 @@ int pfa_cnn_gather_frames(const uint8_t *frames, int64_t frame_bytes, int64_t ba
  *                          = zero): per head, p = softmax, dz_j = g_logprob (1[j = a] - p_j) - g_entropy p_j (log p_j + H), all heads
  *                          of a row sharing its three numbers; column num_actions = g_value; dout [rows][ldd] as for
  *                          pfa_heads_rows_loss (num_actions < j < num_out zeroed, columns >= num_out untouched).  No atomics: one
- *                          thread owns a row, bit-reproducible
+ *                          thread (wide form: one wavefront) owns a row, bit-reproducible
  *   pfa_heads_rows_loss    PPO loss (clean_pufferl.py:202-238) of the chunk's rows and d loss / d out into dout [rows][ldd]
  *                          (columns >= num_out untouched, num_actions < j < num_out zeroed); chunk row r is minibatch row q0 + r, or,
  *                          with time_major_rows = R > 0, row t * R + k is minibatch row q0 + k * bptt_horizon + t;

@@ -10,7 +10,7 @@ autograd=True)`` attach an autograd graph to logprob, entropy and value of that 
 the policy with ``loss.backward()``, ``clip_grad_norm_`` and any torch optimizer over ``policy.parameters()`` (general.Evaluator).
 
 Policy shapes outside the fused kernels' envelope (Default(hidden_size != 128), observation rows wider than 128 / 160 floats, more
-than 15 logits, LSTMWrapper sizes other than (128, 128), LSTMWrapper over the NatureCNN, the NatureCNN with 16 .. 63 actions) adopt a
+than 15 logits, LSTMWrapper sizes other than (128, 128), LSTMWrapper over the NatureCNN, the NatureCNN with 16 .. 1024 actions) adopt a
 general.GeneralParams buffer and
 run rollout and update through general.Engine."""
 import ctypes as C

@@ -13,9 +13,16 @@
 //   heads_rows_loss    the PPO loss of clean_pufferl.py:202-238 for the rows of a chunk and d loss / d (head outputs)
 //   lstm_cell_fwd/bwd  the element-wise part of one nn.LSTM step (gate order i, f, g, o: models.py:76) and of its
 //                      back-propagation through time
-// One thread per row: up to 63 logits in up to 8 MultiDiscrete heads (one Discrete head may use all 63), reductions as plain
-// loops in index order.  This path is about coverage, not the roofline: the headline workload never takes it.
+// Two forms of the four heads_rows_* kernels, chosen inside the entry points:
+//   per thread  one thread per row, reductions as plain loops in index order: one Discrete head of up to 63 logits, and MultiDiscrete
+//               (up to 8 nibble-packed heads of up to 15 choices each: up to 120 logits)
+//   wide        one Discrete head of 64 .. 1024 logits: one WAVEFRONT per row, lane l owning logits l, l + 64, l + 128, ... (at most 16
+//               per lane) in registers after ONE coalesced read of the row; max, sum of exponentials, entropy, arg-max of p / q and the
+//               gradient all work on the registers.  All four wide kernels share wide_softmax, operation for operation, so the
+//               log-probability eval gives an action is bit for bit the one sample gave it, and eval_backward / loss agree with eval on p
+// This path is about coverage, not the roofline: the headline workload never takes it.
 #include <cmath>
+#include <type_traits>
 
 #include "common.hpp"
 #include "philox.hpp"
@@ -24,9 +31,16 @@
 
 namespace pfa {
 
-constexpr int kGenMaxOut = 64;
+constexpr int kMaxLogits = 1024;            // one Discrete head
+constexpr int kMaxOut = kMaxLogits + 16;     // logits, the value, zero columns up to a multiple of 16
+// first logit count of one Discrete head that takes the wide kernels (docs/lab-notebook.md: the A/B against the per-thread loops;
+// tools/wide_heads_bench.py builds a second copy of this file with the threshold above kMaxLogits to time those loops at any width)
+#ifndef PFA_WIDE_HEADS_FROM
+#define PFA_WIDE_HEADS_FROM 64
+#endif
+constexpr int kWideFrom = PFA_WIDE_HEADS_FROM;
 
-struct HeadSpec {   // a = logits in total; nibble-packed head sizes (0: one Discrete(a) head, a <= 63)
+struct HeadSpec {   // a = logits in total; nibble-packed head sizes (0: one Discrete(a) head)
     int a;
     uint32_t heads;
     __device__ __forceinline__ int count() const {
@@ -272,6 +286,284 @@ __global__ void __launch_bounds__(256) heads_rows_loss_kernel(const float *out, 
     if (threadIdx.x < 8) stats_partial[(size_t)blockIdx.x * 8 + threadIdx.x] = (st[0][threadIdx.x] + st[1][threadIdx.x]) + (st[2][threadIdx.x] + st[3][threadIdx.x]);
 }
 
+// ------------------------------------------------------------------------------------------------------------------ wide heads
+// One Discrete head of a >= kWideFrom logits, one wavefront per row.  NP = registers per lane = ceil(a / 64) rounded up to a power
+// of two; lane l holds logit l + 64 i in z[i] (-inf past the end: never read under its j < a guard except by the order-free max).
+template <int NP>
+__device__ __forceinline__ void wide_load(const float *o, int a, int lane, float (&z)[NP]) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int j = lane + 64 * i;
+        z[i] = j < a ? o[j] : -INFINITY;
+    }
+}
+
+struct WideSoftmax {
+    float mx, se, lse, ent;   // max, sum of exp(z - max), log-sum-exp, entropy: the same in every lane
+    __device__ __forceinline__ float p(float z) const { return expf(z - mx) / se; }
+};
+
+// THE softmax of the wide kernels: lane-local sums in index order, cross-lane sums a fixed xor 32 .. 1 butterfly (a + b == b + a bit
+// for bit, so every lane ends with the same number), nothing contracted into an fma whatever code surrounds the call.
+template <int NP>
+__device__ __forceinline__ WideSoftmax wide_softmax(const float (&z)[NP], int a, int lane) {
+#pragma clang fp contract(off)
+    WideSoftmax s;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) mx = fmaxf(mx, z[i]);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+    float se = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+        if (lane + 64 * i < a) se += expf(z[i] - mx);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) se += __shfl_xor(se, d, 64);
+    const float lse = mx + logf(se);
+    float he = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+        if (lane + 64 * i < a) {
+            const float nl = z[i] - lse;
+            he += -nl * (expf(z[i] - mx) / se);
+        }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) he += __shfl_xor(he, d, 64);
+    s.mx = mx;
+    s.se = se;
+    s.lse = lse;
+    s.ent = he;
+    return s;
+}
+
+// logit `idx` (0 <= idx < a, the same in every lane) from the lane that owns it
+template <int NP>
+__device__ __forceinline__ float wide_pick(const float (&z)[NP], int idx) {
+    float v = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+        if (i == (idx >> 6)) v = z[i];
+    return __shfl(v, idx & 63, 64);
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) heads_wide_sample_kernel(const float *out, int ld, long long rows, int a, const float *noise, uint64_t seed,
+                                                               uint64_t step, long long row_offset, long long *actions, float *logprob,
+                                                               float *entropy, float *value) {
+    const int lane = lane_id();
+    const long long row = (long long)blockIdx.x * 4 + wave_id();
+    if (row >= rows) return;
+    const float *o = out + row * ld;
+    const float *nz = noise ? noise + row * a : nullptr;
+    float z[NP];
+    wide_load<NP>(o, a, lane, z);
+    const WideSoftmax sm = wide_softmax<NP>(z, a, lane);
+    // torch.multinomial == argmax(p / q), first index wins ties: within a lane the lower index (ascending, strict >), across lanes the
+    // larger score, then the lower index
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int j = lane + 64 * i;
+        if (j < a) {
+            const float q = noise_lane(nz, seed, step, (uint64_t)(row_offset + row), j, a);
+            const float score = (expf(z[i] - sm.mx) / sm.se) / q;
+            if (score > best) {
+                best = score;
+                besti = j;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const float os = __shfl_xor(best, d, 64);
+        const int oi = __shfl_xor(besti, d, 64);
+        if (os > best || (os == best && oi < besti)) {
+            best = os;
+            besti = oi;
+        }
+    }
+    if (besti >= a) besti = 0;   // (no score compared greater than -inf: the per-thread kernel answers 0 as well)
+    const float lp = wide_pick<NP>(z, besti) - sm.lse;
+    if (lane == 0) {
+        actions[row] = besti;
+        logprob[row] = lp;
+        if (entropy) entropy[row] = sm.ent;
+        value[row] = o[a];
+    }
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) heads_wide_eval_kernel(const float *out, int ld, long long rows, int a, const long long *actions,
+                                                             float *logprob, float *entropy, float *value) {
+    const int lane = lane_id();
+    const long long row = (long long)blockIdx.x * 4 + wave_id();
+    if (row >= rows) return;
+    const float *o = out + row * ld;
+    float z[NP];
+    wide_load<NP>(o, a, lane, z);
+    const WideSoftmax sm = wide_softmax<NP>(z, a, lane);
+    int act = (int)actions[row];
+    act = act < a && act >= 0 ? act : 0;
+    const float lp = wide_pick<NP>(z, act) - sm.lse;
+    if (lane == 0) {
+        logprob[row] = lp;
+        entropy[row] = sm.ent;
+        value[row] = o[a];
+    }
+}
+
+// dz_j = g_logprob (1[j = a] - p_j) - g_entropy p_j (log p_j + H), as heads_rows_eval_bwd_kernel; every lane stores its own columns
+template <int NP>
+__global__ void __launch_bounds__(256) heads_wide_eval_bwd_kernel(const float *out, int ld, long long rows, int a, const long long *actions,
+                                                                 const float *g_logprob, const float *g_entropy, const float *g_value,
+                                                                 float *dout, int ldd, int no) {
+    const int lane = lane_id();
+    const long long row = (long long)blockIdx.x * 4 + wave_id();
+    if (row >= rows) return;
+    const float *o = out + row * ld;
+    float *d = dout + row * ldd;
+    float z[NP];
+    wide_load<NP>(o, a, lane, z);
+    const WideSoftmax sm = wide_softmax<NP>(z, a, lane);
+    int act = (int)actions[row];
+    act = act < a && act >= 0 ? act : 0;
+    const float g_lp = g_logprob ? g_logprob[row] : 0.0f, g_ent = g_entropy ? g_entropy[row] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int j = lane + 64 * i;
+        if (j < a) {
+            const float nl = z[i] - sm.lse, p = sm.p(z[i]);
+            d[j] = g_lp * ((j == act ? 1.0f : 0.0f) - p) - g_ent * p * (nl + sm.ent);
+        }
+    }
+    if (lane == 0) d[a] = g_value ? g_value[row] : 0.0f;
+    for (int j = a + 1 + lane; j < no; j += 64) d[j] = 0.0f;
+}
+
+// The PPO loss of heads_rows_loss_kernel, row for row the same arithmetic.  A block covers 256 consecutive rows, wave w rows
+// 64 w .. 64 w + 63 one after the other (the next row's logits are on their way while this one is worked on); lane r of a wave
+// fetches the experience numbers of the wave's row r once.  The six sums of a wave add up in row order, the four waves in the order
+// of the per-thread kernel: ONE 8-double partial per block, what gen_stats_final_kernel reads.
+template <int NP>
+__global__ void __launch_bounds__(256) heads_wide_loss_kernel(const float *out, int ld, long long rows, RowMap map, long long q0, int R,
+                                                             pfa_experience ex, int a, pfa_ppo_hparams hp, const double *adv_stats,
+                                                             double global_rows, float *dout, int ldd, int no,
+                                                             double *stats_partial /* [gridDim.x][8] */) {
+    __shared__ double st[4][8];
+    const int lane = lane_id(), wv = wave_id();
+    const long long base = (long long)blockIdx.x * 256 + wv * 64;
+    const int nrows = rows - base >= 64 ? 64 : (rows > base ? (int)(rows - base) : 0);
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    float adv_mean = 0.0f, adv_den = 1.0f;
+    if (hp.norm_adv) {   // clean_pufferl.py:211-213: unbiased std over the GLOBAL minibatch
+        const double s1 = adv_stats[2 * map.mb], s2 = adv_stats[2 * map.mb + 1];
+        const double mean = s1 / global_rows;
+        double var = (s2 - s1 * mean) / (global_rows - 1.0);
+        var = var > 0.0 ? var : 0.0;
+        adv_mean = (float)mean;
+        adv_den = (float)sqrt(var) + 1e-8f;
+    }
+    const float inv_rows = (float)(1.0 / global_rows);
+    int packed_l = 0;
+    float old_logprob_l = 0.0f, old_value_l = 0.0f, adv_raw_l = 0.0f, ret_l = 0.0f;
+    if (lane < nrows) {
+        const long long fr = map.flat(chunk_row_to_q(base + lane, q0, R, hp.bptt_horizon));
+        packed_l = ex.actions[fr];
+        old_logprob_l = ex.logprobs[fr];
+        old_value_l = ex.values[fr];
+        adv_raw_l = ex.advantages[fr];
+        ret_l = ex.returns[fr];
+    }
+    float zn[NP], vn = 0.0f;
+    if (nrows > 0) {
+        wide_load<NP>(out + base * ld, a, lane, zn);
+        vn = out[base * ld + a];
+    }
+    for (int r = 0; r < nrows; ++r) {
+        float z[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) z[i] = zn[i];
+        const float new_value = vn;
+        if (r + 1 < nrows) {
+            const float *on = out + (base + r + 1) * ld;
+            wide_load<NP>(on, a, lane, zn);
+            vn = on[a];
+        }
+        float *d = dout + (base + r) * ldd;
+        const int packed = __shfl(packed_l, r, 64);
+        const float old_logprob = __shfl(old_logprob_l, r, 64), old_value = __shfl(old_value_l, r, 64);
+        const float adv_raw = __shfl(adv_raw_l, r, 64), ret = __shfl(ret_l, r, 64);
+        const WideSoftmax sm = wide_softmax<NP>(z, a, lane);
+        const int act = packed >= 0 && packed < a ? packed : 0;
+        const float new_logprob = wide_pick<NP>(z, act) - sm.lse;
+        const float ent = sm.ent;
+        const float logratio = new_logprob - old_logprob;
+        const float ratio = expf(logratio);
+        const float adv = hp.norm_adv ? (adv_raw - adv_mean) / adv_den : adv_raw;
+        const float lo_c = 1.0f - hp.clip_coef, hi_c = 1.0f + hp.clip_coef;
+        const float pg1 = -adv * ratio, pg2 = -adv * fminf(fmaxf(ratio, lo_c), hi_c);
+        const bool inside = ratio >= lo_c && ratio <= hi_c;
+        float dpg;   // torch.max's tie rule + clamp's pass-through, as in ppo_tile.hpp
+        if (pg1 > pg2) dpg = -adv;
+        else if (pg1 < pg2) dpg = inside ? -adv : 0.0f;
+        else dpg = inside ? -adv : -0.5f * adv;
+        const float scale = inv_rows;
+        const float g_lp = dpg * ratio * scale;
+        float v_loss, dv;
+        if (hp.clip_vloss) {
+            const float du = new_value - ret, vl_u = du * du;
+            const float delta = new_value - old_value;
+            const float vcl = old_value + fminf(fmaxf(delta, -hp.vf_clip_coef), hp.vf_clip_coef);
+            const float dc = vcl - ret, vl_c = dc * dc;
+            const bool vin = delta >= -hp.vf_clip_coef && delta <= hp.vf_clip_coef;
+            v_loss = 0.5f * fmaxf(vl_u, vl_c);
+            const float gu = 2.0f * du, gc = vin ? 2.0f * dc : 0.0f;
+            dv = 0.5f * (vl_u > vl_c ? gu : (vl_u < vl_c ? gc : 0.5f * (gu + gc)));
+        } else {
+            const float du = new_value - ret;
+            v_loss = 0.5f * du * du;
+            dv = du;
+        }
+        dv *= hp.vf_coef * scale;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int j = lane + 64 * i;
+            if (j < a) {
+                const float nl = z[i] - sm.lse, p = sm.p(z[i]);
+                // d new_logprob/d logit = [chosen] - p ; d entropy/d logit = -p (nl + H)
+                d[j] = g_lp * ((j == act ? 1.0f : 0.0f) - p) + hp.ent_coef * scale * p * (nl + ent);
+            }
+        }
+        if (lane == 0) d[a] = dv;
+        for (int j = a + 1 + lane; j < no; j += 64) d[j] = 0.0f;
+        acc[0] += (double)fmaxf(pg1, pg2);
+        acc[1] += (double)v_loss;
+        acc[2] += (double)ent;
+        acc[3] += (double)(-logratio);
+        acc[4] += (double)((ratio - 1.0f) - logratio);
+        acc[5] += (double)(fabsf(ratio - 1.0f) > hp.clip_coef ? 1.0f : 0.0f);
+    }
+    if (lane == 0)
+        for (int i = 0; i < 8; ++i) st[wv][i] = i < 6 ? acc[i] : 0.0;
+    __syncthreads();
+    if (threadIdx.x < 8) stats_partial[(size_t)blockIdx.x * 8 + threadIdx.x] = (st[0][threadIdx.x] + st[1][threadIdx.x]) + (st[2][threadIdx.x] + st[3][threadIdx.x]);
+}
+
+// f(std::integral_constant<int, NP>) for the register count of `a` logits
+template <class F>
+static void wide_registers(int a, F &&f) {
+    const int per_lane = (a + 63) / 64;
+    if (per_lane <= 1) f(std::integral_constant<int, 1>{});
+    else if (per_lane <= 2) f(std::integral_constant<int, 2>{});
+    else if (per_lane <= 4) f(std::integral_constant<int, 4>{});
+    else if (per_lane <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
+static bool wide_form(int32_t a, uint32_t heads) { return heads == 0 && a >= kWideFrom; }
+
 // loss_pairs16 (+)= the (hi, lo) float pairs of the chunk's six f64 sums, fixed summation order over the block partials
 __global__ void __launch_bounds__(256) gen_stats_final_kernel(const double *partial, int nblocks, float *loss_pairs16, int accumulate) {
     __shared__ double sh[32][8];      // 32 strided chains per statistic, combined in a fixed order
@@ -370,7 +662,9 @@ __global__ void __launch_bounds__(256) rows_perm_kernel(const float *src, int ld
 }
 
 static int check_heads(int32_t a, uint32_t heads, int32_t ld) {
-    PFA_REQUIRE(a >= 1 && a < kGenMaxOut && ld > a, "heads: 1..63 logits, and the value in column num_actions of a row of ld > num_actions floats");
+    PFA_REQUIRE(a >= 1 && ld > a, "heads: at least one logit, and the value in column num_actions of a row of ld > num_actions floats");
+    PFA_REQUIRE(heads != 0 || a <= kMaxLogits,
+                "heads: %d logits: one Discrete head takes 1..1024, MultiDiscrete up to 8 nibble-packed heads of up to 15 choices (120 logits)", a);
     if (heads != 0) {
         int n = 0, total = 0;
         for (; n < 8 && ((heads >> (4 * n)) & 15u) != 0; ++n) total += (int)((heads >> (4 * n)) & 15u);
@@ -391,6 +685,15 @@ extern "C" int pfa_heads_rows_sample(const float *out, int32_t ld, int64_t rows,
     if (int rc = check_heads(num_actions, heads, ld)) return rc;
     if (rows == 0) return 0;
     ScopedKernelTimer timer("heads_rows_sample", (hipStream_t)stream);
+    if (wide_form(num_actions, heads)) {
+        wide_registers(num_actions, [&](auto np) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_wide_sample_kernel<decltype(np)::value>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                               (hipStream_t)stream, out, (int)ld, (long long)rows, (int)num_actions, noise, key ? key->seed : 0,
+                               key ? key->step : 0, (long long)row_offset, (long long *)actions, logprob, entropy, value);
+        });
+        PFA_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(heads_rows_sample_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (int)ld,
                        (long long)rows, HeadSpec{(int)num_actions, heads}, noise, key ? key->seed : 0, key ? key->step : 0,
                        (long long)row_offset, (long long *)actions, logprob, entropy, value);
@@ -403,6 +706,15 @@ extern "C" int pfa_heads_rows_eval(const float *out, int32_t ld, int64_t rows, i
     PFA_REQUIRE(out && actions && logprob && entropy && value && rows >= 0, "heads_rows_eval: null buffer");
     if (int rc = check_heads(num_actions, heads, ld)) return rc;
     if (rows == 0) return 0;
+    if (wide_form(num_actions, heads)) {
+        wide_registers(num_actions, [&](auto np) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_wide_eval_kernel<decltype(np)::value>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                               (hipStream_t)stream, out, (int)ld, (long long)rows, (int)num_actions, (const long long *)actions, logprob, entropy,
+                               value);
+        });
+        PFA_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(heads_rows_eval_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (int)ld,
                        (long long)rows, HeadSpec{(int)num_actions, heads}, (const long long *)actions, logprob, entropy, value);
     PFA_LAUNCH_CHECK();
@@ -414,8 +726,17 @@ extern "C" int pfa_heads_rows_eval_backward(const float *out, int32_t ld, int64_
                                             float *dout, int32_t ldd, int32_t num_out, pfa_stream_t stream) {
     PFA_REQUIRE(out && actions && dout && rows >= 0, "heads_rows_eval_backward: null buffer");
     if (int rc = check_heads(num_actions, heads, ld)) return rc;
-    PFA_REQUIRE(num_out > num_actions && num_out <= kGenMaxOut && ldd >= num_out, "heads_rows_eval_backward: num_out must cover the value column");
+    PFA_REQUIRE(num_out > num_actions && num_out <= kMaxOut && ldd >= num_out, "heads_rows_eval_backward: num_out must cover the value column");
     if (rows == 0) return 0;
+    if (wide_form(num_actions, heads)) {
+        wide_registers(num_actions, [&](auto np) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_wide_eval_bwd_kernel<decltype(np)::value>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                               (hipStream_t)stream, out, (int)ld, (long long)rows, (int)num_actions, (const long long *)actions, g_logprob,
+                               g_entropy, g_value, dout, (int)ldd, (int)num_out);
+        });
+        PFA_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(heads_rows_eval_bwd_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, (int)ld,
                        (long long)rows, HeadSpec{(int)num_actions, heads}, (const long long *)actions, g_logprob, g_entropy, g_value, dout,
                        (int)ldd, (int)num_out);
@@ -432,7 +753,7 @@ extern "C" int pfa_heads_rows_loss(const float *out, int32_t ld, const pfa_exper
     PFA_REQUIRE(out && exp && hp && dout && loss_pairs16 && workspace, "heads_rows_loss: null buffer");
     PFA_REQUIRE(exp->actions && exp->logprobs && exp->values && exp->advantages && exp->returns, "heads_rows_loss: null experience buffer");
     if (int rc = check_heads(num_actions, heads, ld)) return rc;
-    PFA_REQUIRE(num_out > num_actions && num_out <= kGenMaxOut && ldd >= num_out, "heads_rows_loss: num_out must cover the value column");
+    PFA_REQUIRE(num_out > num_actions && num_out <= kMaxOut && ldd >= num_out, "heads_rows_loss: num_out must cover the value column");
     PFA_REQUIRE(hp->num_minibatches >= 1 && hp->bptt_horizon >= 1 && batch_rows % hp->num_minibatches == 0, "heads_rows_loss: bad minibatch partition");
     const int64_t mbs = batch_rows / hp->num_minibatches;
     PFA_REQUIRE(mb >= 0 && mb < hp->num_minibatches && q0 >= 0 && rows >= 1 && q0 + rows <= mbs, "heads_rows_loss: chunk outside the minibatch");
@@ -441,9 +762,17 @@ extern "C" int pfa_heads_rows_loss(const float *out, int32_t ld, const pfa_exper
     PFA_REQUIRE(!hp->norm_adv || adv_stats, "heads_rows_loss: norm_adv needs adv_stats");
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     const unsigned grid = (unsigned)((rows + 255) / 256);
-    hipLaunchKernelGGL(heads_rows_loss_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, (int)ld, (long long)rows, map, (long long)q0,
-                       (int)time_major_rows, *exp, HeadSpec{(int)num_actions, heads}, *hp, adv_stats, (double)global_mb_rows, dout, (int)ldd,
-                       (int)num_out, (double *)workspace);
+    if (wide_form(num_actions, heads)) {
+        wide_registers(num_actions, [&](auto np) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(heads_wide_loss_kernel<decltype(np)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, out,
+                               (int)ld, (long long)rows, map, (long long)q0, (int)time_major_rows, *exp, (int)num_actions, *hp, adv_stats,
+                               (double)global_mb_rows, dout, (int)ldd, (int)num_out, (double *)workspace);
+        });
+    } else {
+        hipLaunchKernelGGL(heads_rows_loss_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, (int)ld, (long long)rows, map, (long long)q0,
+                           (int)time_major_rows, *exp, HeadSpec{(int)num_actions, heads}, *hp, adv_stats, (double)global_mb_rows, dout, (int)ldd,
+                           (int)num_out, (double *)workspace);
+    }
     PFA_LAUNCH_CHECK();
     hipLaunchKernelGGL(gen_stats_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double *)workspace, (int)grid, loss_pairs16,
                        (int)accumulate);

@@ -1,7 +1,8 @@
 """Width-general policy engine: every policy shape of the reference that the fused 128-wide kernels do not cover.
 
   pufferlib.models.Default(env, hidden_size=H)                         models.py:24-39    any H that is a multiple of 16, any flat
-                                                                                          observation width, up to 63 logits
+                                                                                          observation width, one Discrete head of up
+                                                                                          to 1024 logits or MultiDiscrete up to 8 x 15
   pufferlib.models.LSTMWrapper(env, policy, input_size=I, hidden_size=Hl)  models.py:64-82  any I (= the encoder width), Hl
   environments/atari/torch.py:4-6  Recurrent = LSTMWrapper(512, 512) over the NatureCNN   (what config.yaml's atari section trains)
 
@@ -28,7 +29,9 @@ from . import _lib
 from ._lib import EPI_BIAS, EPI_BIAS_RELU, EPI_MASK, EPI_NONE, MODE_DENSE, operand, round_up
 from .models import decoder_heads, find_cnn, find_lstm, find_mlp
 
-MAX_LOGITS = 63
+MAX_LOGITS = 1024                  # one Discrete head (csrc/general.hip: the wave-per-row kernels from 64 logits on)
+MAX_PACKED_HEADS, MAX_HEAD_CHOICES = 8, 15
+MAX_MULTIDISCRETE_LOGITS = MAX_PACKED_HEADS * MAX_HEAD_CHOICES     # what the 4-bit action packing allows: 120
 
 
 def gemm_rows(a, lda, rows, K, B, ldb, N, out, ldc, epi=EPI_NONE, bias=None, mask=None, ldmask=0):
@@ -54,8 +57,9 @@ def pack_heads(nvec, multidiscrete):
     """pfa_mlp_dims.heads: nibble-packed head sizes, 0 for one Discrete head."""
     if not multidiscrete:
         return 0
-    if len(nvec) > 8 or max(nvec) > 15:
-        raise NotImplementedError(f'MultiDiscrete heads {nvec}: up to 8 heads of up to 15 choices (one Discrete head may have {MAX_LOGITS})')
+    if len(nvec) > MAX_PACKED_HEADS or max(nvec) > MAX_HEAD_CHOICES:
+        raise NotImplementedError(f'MultiDiscrete heads {nvec}: up to {MAX_PACKED_HEADS} heads of up to {MAX_HEAD_CHOICES} choices '
+                                  f'({MAX_MULTIDISCRETE_LOGITS} logits; one Discrete head may have {MAX_LOGITS})')
     return sum(n << (4 * h) for h, n in enumerate(nvec))
 
 
@@ -91,9 +95,10 @@ class GeneralParams:
             if self.features % 16 != 0:
                 raise NotImplementedError(f'hidden_size {self.features}: a multiple of 16')
         self.num_actions = sum(self.nvec)
+        self.heads = pack_heads(self.nvec, self.multidiscrete)      # (MultiDiscrete: at most 8 x 15 = 120 logits past this line)
         if self.num_actions > MAX_LOGITS:
-            raise NotImplementedError(f'{self.num_actions} logits: the head kernels take up to {MAX_LOGITS}')
-        self.heads = pack_heads(self.nvec, self.multidiscrete)
+            raise NotImplementedError(f'{self.num_actions} logits: the head kernels take up to {MAX_LOGITS} in one Discrete head '
+                                      f'(MultiDiscrete: up to {MAX_MULTIDISCRETE_LOGITS} in {MAX_PACKED_HEADS} heads of up to {MAX_HEAD_CHOICES})')
         if self.lstm is not None:
             if self.lstm.input_size != self.features:
                 raise ValueError(f'nn.LSTM input_size {self.lstm.input_size} != encoder width {self.features}')
@@ -420,6 +425,7 @@ class Evaluator:
             actions = torch.empty(rows, dtype=torch.int64, device=dev)
             if noise is not None:
                 noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+                assert tuple(noise.shape) == (rows, net.A), tuple(noise.shape)      # the kernel reads net.A draws per row, whatever it is handed
             _lib.check(L.pfa_heads_rows_sample(_lib.ptr(out), NO, rows, net.A, net.heads, _lib.ptr(noise), C.byref(key) if key is not None else None,
                                                row_offset, _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(entropy), _lib.ptr(value),
                                                _lib.stream_handle()), 'heads_rows_sample')

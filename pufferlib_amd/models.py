@@ -335,7 +335,7 @@ class ConvParams:
         self.geometry = conv_geometry_of(policy_module, obs_shape)
         self.num_actions = int(net.actor.weight.shape[0])
         if self.num_actions > 15:       # (cleanrl.needs_general sends wider action sets through general.GeneralParams)
-            raise NotImplementedError('the 16-lane head kernels take up to 15 actions; 16..63 run on the GEMM path (general.py)')
+            raise NotImplementedError('the 16-lane head kernels take up to 15 actions; 16..1024 run on the GEMM path (general.py)')
         self.nvec = [self.num_actions]
         self.names = [n for n, _ in net.named_parameters()]
         sizes = [p.numel() for _, p in net.named_parameters()]

@@ -842,6 +842,7 @@ class Bandit(_DeviceVecEnv):
     once, with numpy's own legacy RandomState — the generator the reference calls — and the kernels keep the state machine."""
     FAMILY, NAMES, DEFAULTS = 'bandit', ('num_actions', 'reward_scale', 'reward_noise'), (10, 1, 1)
     ABI = 'pfa_bandit'
+    MAX_ACTIONS = 15       # what every policy tier takes, the fused 128-wide kernels included (WideBandit: the GEMM path's limit)
 
     def _spec(self, num_actions, reward_scale, reward_noise):
         return BanditSpec(num_actions, reward_scale, reward_noise)
@@ -849,8 +850,8 @@ class Bandit(_DeviceVecEnv):
     def _alloc_state(self):
         import torch
         spec = self.driver_env
-        if not 2 <= spec.num_actions <= 15:
-            raise APIUsageError('the policy kernels take 1..15 actions')
+        if not 2 <= spec.num_actions <= self.MAX_ACTIONS:
+            raise APIUsageError(f'the policy kernels take 1..{self.MAX_ACTIONS} actions')
         self.episode_len = 2                      # one step + the auto-reset row
         rs = np.random.RandomState(spec.hard_fixed_seed)              # ocean.py:36-42: seed(42) then randint for the solution
         self.solution = int(rs.randint(0, spec.num_actions))
@@ -871,6 +872,14 @@ class Bandit(_DeviceVecEnv):
     def _k_send(self, actions):
         _lib.check(self.L.pfa_bandit_send(_lib.ptr(self.state), self.num_agents, self.solution, self.scale, _lib.ptr(self.noise),
                                           _lib.ptr(actions), *self._live(), _lib.stream_handle()), 'send')
+
+
+class WideBandit(Bandit):
+    """`Bandit` with any action count the reference's make_bandit(num_actions=...) is given, up to the 1024 logits one Discrete head
+    of the GEMM-path policy engine takes (general.MAX_LOGITS): the same kernels and state.  A class of its own because `Bandit`
+    refuses more than 15 actions at construction, and callers rely on that refusal; policies on more than 15 actions run through
+    general.Engine with stepwise rollouts."""
+    MAX_ACTIONS = 1024
 
 
 def make_multiagent(**kwargs):
