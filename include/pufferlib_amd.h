@@ -736,6 +736,15 @@ int pfa_igemm_get_products(void);
 size_t pfa_igemm_weights_workspace_bytes(int64_t M, int32_t K, int32_t N);
 int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *D, int32_t ldd, int32_t N, float *out,
                       int32_t perm, int32_t accumulate, float *bias_out, void *workspace, pfa_stream_t stream);
+/* Which kernel a launch would run (host only, nothing is launched; the launches take their choice from the same code).
+ * pfa_igemm_rows_plan: for operand `mode`, M rows and contraction length K per phase (mode 3: of one of the S*S phases) and the current
+ *                    pfa_igemm_set_products setting, out4_host = {0 fp32 / 1 six-term bf16, tile rows, tile columns, row tiles (the grid
+ *                    rounds them up to a multiple of 8)}.
+ * pfa_igemm_weights_plan: out5_host = {tile columns tn, tile height over k (64, 128, 192 or 256; the 64 form exists for modes 0 and 4,
+ *                    the others run it as 128), (k, n) tiles, row splits, rows per split}; the workspace is splits * K * N floats
+ *                    rounded up to 256 bytes + splits * N doubles + 256 bytes. */
+int pfa_igemm_rows_plan(int32_t mode, int64_t M, int32_t K, int32_t N, int32_t *out4_host);
+int pfa_igemm_weights_plan(int64_t M, int32_t K, int32_t N, int32_t *out5_host);
 int pfa_cnn_pack_conv(const float *w, const pfa_igemm_operand *geom, int32_t u8_order, float *fwd, float *dx, pfa_stream_t stream);
 int pfa_igemm_rows_add(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *B, int32_t ldb, int32_t N, float *C, int32_t ldc,
                        int32_t epilogue, const float *bias, const float *mask, int32_t ldmask, const float *addend, int32_t ldadd,

@@ -1072,6 +1072,28 @@ static IgWeightPlan ig_weight_plan(int64_t M, int K, int N) {
 }
 static size_t ig_partial_bytes(const IgWeightPlan &p, int K, int N) { return align_up((size_t)p.splits * (size_t)K * (size_t)N * sizeof(float), 256); }
 
+// Launch plan of the rows form, shared by the launch and pfa_igemm_rows_plan: product form, tile (64 mi) x (16 ni) and the number of
+// row tiles (grid.x is that rounded up to 8, one run of tiles per XCD).  Mp, Kp: rows and contraction length per phase.
+struct IgRowsPlan {
+    int split;   // 1: the six-term bf16 kernel, 0: the fp32 kernel
+    int mi, ni;
+    long long tiles;
+};
+static IgRowsPlan ig_rows_plan(int mode, long long Mp, int Kp, int N) {
+    IgRowsPlan p;
+    const int tn = N % 64 == 0 ? 64 : N % 32 == 0 ? 32 : 16;
+    // A dense product over few rows (one rollout step of the width-general policies: 4096 rows) fills the chip only with 64-row tiles.
+    const bool few = mode == kADense && ((Mp + (tn == 16 ? 255 : 127)) / (tn == 16 ? 256 : 128)) * (N / tn) < 256;
+    // opt-in: the six-term bf16 form of the same products (modes 5, 6: always the fp32 kernel)
+    p.split = g_ig_products == 1 && !few && tn >= 32 && Kp % kIgSplitBK == 0 && mode <= kAIm2colU8S;
+    p.ni = tn / 16;
+    if (p.split) p.mi = 2;
+    else if (few) p.mi = 1;
+    else p.mi = tn == 16 ? 4 : 2;   // (128 x 32 beats 256 x 32: the smaller stage keeps more workgroups per CU)
+    p.tiles = (Mp + 64 * p.mi - 1) / (64 * p.mi);
+    return p;
+}
+
 }  // namespace pfa
 
 using namespace pfa;
@@ -1130,9 +1152,11 @@ static int ig_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float
     }
     PFA_REQUIRE(Kp % kIgBK == 0 && ldb >= Kp, "igemm.rows: the contraction length (per phase) must be a multiple of 16 and ldb >= it");
     ScopedKernelTimer timer("igemm_rows", (hipStream_t)stream);
+    const IgRowsPlan plan = ig_rows_plan(A.mode, Mp, Kp, N);
+    const unsigned grid_x = (unsigned)((plan.tiles + 7) / 8 * 8);
     auto rows = [&](auto mode, auto mi, auto ni) {   // the fp32 kernel on (64 MI) x (16 NI) tiles
         constexpr int MI = decltype(mi)::value, NI = decltype(ni)::value;
-        hipLaunchKernelGGL((igemm_rows_kernel<decltype(mode)::value, MI, NI>), dim3((unsigned)(((Mp + 64 * MI - 1) / (64 * MI) + 7) / 8 * 8), N / (16 * NI), phases),
+        hipLaunchKernelGGL((igemm_rows_kernel<decltype(mode)::value, MI, NI>), dim3(grid_x, N / (16 * NI), phases),
                            dim3(kIgThreads), 0, (hipStream_t)stream, A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue,
                            bias, mask, (int)ldmask, addend, (int)ldadd);
     };
@@ -1142,32 +1166,40 @@ static int ig_rows(const pfa_igemm_operand *a, int64_t M, int32_t K, const float
     auto split = [&](auto ni) {   // the six-term bf16 form on 128 x (16 NI) tiles
         ig_with_mode<kADense, kAIm2colF32, kAIm2colU8, kAIm2colU8S, kACol2im>(A.mode, [&](auto mode) {
             hipLaunchKernelGGL((igemm_rows_split_kernel<decltype(mode)::value, 2, decltype(ni)::value>),
-                               dim3((unsigned)(((Mp + 127) / 128 + 7) / 8 * 8), N / (16 * decltype(ni)::value), phases), dim3(kIgThreads), 0, (hipStream_t)stream,
+                               dim3(grid_x, N / (16 * decltype(ni)::value), phases), dim3(kIgThreads), 0, (hipStream_t)stream,
                                A, (int)Mp, (int)Kp, B, (int)ldb, (int)N, C, (int)ldc, (int)epilogue, bias, mask, (int)ldmask);
         });
     };
     constexpr IgInt<1> i1{};
     constexpr IgInt<2> i2{};
     constexpr IgInt<4> i4{};
-    // A dense product over few rows (one rollout step of the width-general policies: 4096 rows) fills the chip only with 64-row tiles.
-    const int tn = N % 64 == 0 ? 64 : N % 32 == 0 ? 32 : 16;
-    const bool few = A.mode == kADense && ((Mp + (tn == 16 ? 255 : 127)) / (tn == 16 ? 256 : 128)) * (N / tn) < 256;
-    if (g_ig_products == 1 && !few && tn >= 32 && Kp % kIgSplitBK == 0 && A.mode <= kAIm2colU8S) {   // opt-in: the six-term bf16 form of the same products (modes 5, 6: always the fp32 kernel)
-        if (tn == 64) split(i4);
+    if (plan.split) {
+        if (plan.ni == 4) split(i4);
         else split(i2);
-    } else if (few) {
+    } else if (plan.mi == 1) {   // the 64-row tiles of a small dense product
         constexpr std::integral_constant<IgAMode, kADense> dense{};
-        if (tn == 64) rows(dense, i1, i4);
-        else if (tn == 32) rows(dense, i1, i2);
+        if (plan.ni == 4) rows(dense, i1, i4);
+        else if (plan.ni == 2) rows(dense, i1, i2);
         else rows(dense, i1, i1);
-    } else if (N % 64 == 0) {
+    } else if (plan.ni == 4) {
         rows_any(i2, i4);
-    } else if (N % 32 == 0) {
-        rows_any(i2, i2);   // (128 x 32 beats 256 x 32: the smaller stage keeps more workgroups per CU)
+    } else if (plan.ni == 2) {
+        rows_any(i2, i2);
     } else {
         rows_any(i4, i1);
     }
     PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pfa_igemm_rows_plan(int32_t mode, int64_t M, int32_t K, int32_t N, int32_t *out4_host) {
+    PFA_REQUIRE(out4_host && mode >= 0 && mode <= 6 && M >= 1 && M < (1ll << 31) && K >= kIgBK && K % kIgBK == 0 && N >= 16 && N % 16 == 0,
+                "igemm.rows_plan: mode 0..6, rows >= 1, K (per phase) and N multiples of 16");
+    const IgRowsPlan p = ig_rows_plan(mode, M, K, N);
+    out4_host[0] = p.split;
+    out4_host[1] = 64 * p.mi;
+    out4_host[2] = 16 * p.ni;
+    out4_host[3] = (int32_t)p.tiles;
     return 0;
 }
 
@@ -1182,6 +1214,18 @@ extern "C" size_t pfa_igemm_weights_workspace_bytes(int64_t M, int32_t K, int32_
     if (M < 1 || K < 4 || N < 16 || N % 16 != 0) return 0;
     const IgWeightPlan p = ig_weight_plan(M, K, N);
     return ig_partial_bytes(p, K, N) + (size_t)p.splits * (size_t)N * sizeof(double) + 256;
+}
+
+extern "C" int pfa_igemm_weights_plan(int64_t M, int32_t K, int32_t N, int32_t *out5_host) {
+    PFA_REQUIRE(out5_host && M >= 1 && M < (1ll << 31) && K >= 4 && K % 4 == 0 && N >= 16 && N % 16 == 0,
+                "igemm.weights_plan: rows >= 1, K a multiple of 4, N a multiple of 16");
+    const IgWeightPlan p = ig_weight_plan(M, K, N);
+    out5_host[0] = p.tn;
+    out5_host[1] = 64 * p.kj;
+    out5_host[2] = p.tiles;
+    out5_host[3] = p.splits;
+    out5_host[4] = p.rows_per_split;
+    return 0;
 }
 
 extern "C" int pfa_igemm_weights(const pfa_igemm_operand *a, int64_t M, int32_t K, const float *D, int32_t ldd, int32_t N, float *out,

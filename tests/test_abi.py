@@ -54,6 +54,38 @@ def test_weight_gradient_workspace_never_shrinks_with_more_rows(L):
     assert L.pfa_gemm_tn_workspace_bytes(128, 160, 131072) > 0 and L.pfa_gemm_tn_workspace_bytes(128, 24, 4096) == 0
 
 
+def test_igemm_plan_queries_answer_on_the_host_and_agree_with_the_workspace(L):
+    """pfa_igemm_rows_plan / pfa_igemm_weights_plan (csrc/igemm.hip) launch nothing: they answer without a GPU, from the functions the
+    launches choose their kernel by.  The weight plan's splits are what the workspace is sized from; the rows plan follows the products
+    switch only where the six-term kernels apply (tests/test_dense_gemm_reference_cpu.py pins every kernel to a case)."""
+    out = (C.c_int32 * 5)()
+    for K, N in [(64, 256), (256, 16), (512, 64), (3136, 512), (160, 128), (48, 64), (52, 96)]:
+        for M in (1, 255, 4096, 131072, 8192 * 49):
+            assert L.pfa_igemm_weights_plan(M, K, N, out) == 0
+            tn, tk, tiles, splits, rps = out[:5]
+            assert tn in (16, 32, 64) and N % tn == 0 and tk in (64, 128, 192, 256) and tiles == -(-K // tk) * (N // tn)
+            assert 1 <= splits <= 1024 and rps % 16 == 0 and splits * rps >= M > splits * (rps - 16), (K, N, M, tuple(out[:5]))   # (whole 16-row slabs)
+            assert L.pfa_igemm_weights_workspace_bytes(M, K, N) == (splits * K * N * 4 + 255) // 256 * 256 + splits * N * 8 + 256
+    assert L.pfa_igemm_get_products() == 0
+    assert L.pfa_igemm_rows_plan(0, 4096, 64, 128, out) == 0 and tuple(out[:4]) == (0, 64, 64, 64)        # one rollout step, hidden 128
+    assert L.pfa_igemm_rows_plan(0, 131072, 64, 128, out) == 0 and tuple(out[:4]) == (0, 128, 64, 1024)
+    assert L.pfa_igemm_rows_plan(1, 4096, 64, 128, out) == 0 and tuple(out[:4]) == (0, 128, 64, 32)       # 64-row tiles are the dense operand's
+    try:
+        assert L.pfa_igemm_set_products(1) == 0
+        assert L.pfa_igemm_rows_plan(0, 131072, 64, 128, out) == 0 and tuple(out[:4]) == (1, 128, 64, 1024)
+        assert L.pfa_igemm_rows_plan(0, 131072, 48, 128, out) == 0 and tuple(out[:4]) == (0, 128, 64, 1024)
+        assert L.pfa_igemm_rows_plan(5, 131072, 64, 128, out) == 0 and tuple(out[:4]) == (0, 128, 64, 1024)   # modes 5, 6: always fp32
+    finally:
+        assert L.pfa_igemm_set_products(0) == 0
+    # what the launches refuse, the queries refuse: K % 16 (rows) / K % 4 (weights), N % 16, no rows, an unknown mode, no output
+    assert L.pfa_igemm_rows_plan(0, 4096, 20, 128, out) != 0 and b'rows_plan' in L.pfa_last_error()
+    assert L.pfa_igemm_rows_plan(0, 4096, 64, 24, out) != 0 and L.pfa_igemm_rows_plan(0, 0, 64, 128, out) != 0
+    assert L.pfa_igemm_rows_plan(7, 4096, 64, 128, out) != 0 and L.pfa_igemm_rows_plan(0, 4096, 64, 128, None) != 0
+    assert L.pfa_igemm_weights_plan(4096, 64, 24, out) != 0 and b'weights_plan' in L.pfa_last_error()
+    assert L.pfa_igemm_weights_plan(4096, 18, 64, out) != 0 and L.pfa_igemm_weights_plan(0, 64, 64, out) != 0
+    assert L.pfa_igemm_weights_plan(4096, 64, 64, None) != 0
+
+
 # recorded from the library built at commit 39f66d4, before the host dispatch of csrc/ppo_update.hip went through one shape table
 _MFMA_PER_TILE_39F66D4 = {   # (obs_dim, obs_stride): values for num_actions 1, 8, 11, 12, 15
     (16, 16): [160] * 5, (13, 16): [160] * 5, (32, 32): [224] * 5, (29, 32): [224] * 5,
