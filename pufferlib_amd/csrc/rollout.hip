@@ -67,8 +67,9 @@ __global__ void __launch_bounds__(kRollThreads) mlp_forward_sample_kernel(const 
 // fused persistent rollout
 //
 // One workgroup of 4 wavefronts owns 16 envs for all T steps.  Per step:
-//   all 256 threads   store the 16 observation rows (LDS -> experience, one float4 each at obs_stride 64)
 //   wave w            forward_slice: 2 x KS MFMAs against W1 fragments held in registers + its 8 head MFMAs
+//   all 256 threads   from inside the forward (RowStore): store the 16 observation rows (LDS -> experience, one float4 each at
+//                     obs_stride 64), read behind the forward's operands and stored behind the first layer's products
 //   barrier
 //   thread (e, o)     sample_lanes: softmax / Exp(1) noise / argmax(p/q) / logprob over the row's 16 lanes
 //   thread (e, 0)     Experience.store of the scalars, then send(): env step or tape reset, rewriting row e of the
@@ -86,15 +87,20 @@ __global__ void __launch_bounds__(kRollThreads) mlp_forward_sample_kernel(const 
 //     flight" at the loop header as far as the compiler could tell, so the first wait of every step was a `vmcnt(0)` — which
 //     also waits for the acknowledgement of the observation-row stores issued a few instructions earlier and of the previous
 //     step's scalar stores.  One explicit drain before the loop removes it; the two per-step barriers order LDS only
-//     (`lds_barrier`, common.hpp).
+//     (`lds_barrier`, common.hpp);
+//   * FULL (the env count is a multiple of 16, so every workgroup owns 16 real envs): no row guard around the observation-row
+//     stores, which the compiler can then count — the wait for the prefetched noise value in front of barrier 1 no longer waits
+//     for the acknowledgement of this step's row stores;
+//   * the row stores go behind the forward's operand reads (forward_slice's hook) instead of in front of them.
 // ---------------------------------------------------------------------------------------------
-template <int DP, int EPW, bool NT1, int KS, int MW = kMW>
+template <int DP, int EPW, bool NT1, int KS, int MW = kMW, bool FULL = false>
 __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(SquaredView v, MlpView pv, int a,
                                                                           pfa_experience ex, const float *noise,
                                                                           uint64_t seed, uint64_t step0, long long env_offset,
                                                                           float *live_obs, float *live_rew, uint8_t *live_term,
                                                                           uint8_t *live_trunc, uint8_t *live_mask) {
     constexpr int XS = XTile<DP>::XS;
+    static_assert(!FULL || EPW == 16, "FULL: every row of the 16-row tile is an env of this workgroup");
     __shared__ float xs[XTile<DP>::kFloats];
     __shared__ float part[kRollWaves][kPartFloats];  // partial out^T[o][row] per wave
     __shared__ uint16_t tg[NT1 ? 1 : 16 * kMaxTargets];
@@ -104,7 +110,7 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(Squar
     __shared__ RewardTable rtab;
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15;  // sampling role: local env, output index
     const int e = blockIdx.x * EPW + le;
-    const bool env_ok = le < EPW && e < v.n;
+    const bool env_ok = FULL || (le < EPW && e < v.n);
     const bool owner = lo == 0 && env_ok;  // the thread that carries env `e`
     const int T = ex.horizon_T;
 
@@ -121,6 +127,11 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(Squar
     long long filled = 0;        // NT1: tape rounds drawn when this launch started (the host guarantees they cover it)
     uint16_t next_cell = 0;      // NT1: target of this env's next reset (tape round s.rounds), fetched ahead of the reset
     uint32_t slot = 0;           // NT1: s.rounds % tape_rounds, kept incrementally
+    // NT1: this env's cell of tape round 0 / round `slot`, kept incrementally (no 64-bit multiply per step).  Both are per-thread
+    // pointers on purpose: reading v.tape inside the loop made the compiler reload kernel arguments with a scalar load in front of
+    // the loop, and with a scalar load possibly in flight every counted LDS wait of the forward turns into lgkmcnt(0).
+    const uint16_t *const tape_e = v.tape + e;
+    const uint16_t *tape_at = tape_e;
     const size_t tape_n = (size_t)v.n;
     if (owner) {
         squared_load(v, e, s);
@@ -128,7 +139,8 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(Squar
             t1.set(v.tgt[e], v.g);
             filled = v.hdr->rounds_filled;
             slot = s.rounds % (uint32_t)v.tape_rounds;
-            next_cell = v.tape[(size_t)slot * tape_n + e];
+            tape_at = tape_e + (size_t)slot * tape_n;
+            next_cell = *tape_at;
         } else {
             for (int t = 0; t < v.nt; ++t) tg[le * kMaxTargets + t] = v.tgt[(size_t)t * v.n + e];
         }
@@ -148,10 +160,11 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(Squar
 
     for (int t = 0; t < T; ++t) {
         PFA_RSTAMP(t, 0);
-        // Experience.store of the observation rows (clean_pufferl.py:443), env-major: row (e, t) at e*T + t
-        unstage_rows<DP>(xs, ex.obs + (size_t)t * DP, (long long)blockIdx.x * EPW, v.n, (size_t)T * DP, EPW);
+        // Experience.store of the observation rows (clean_pufferl.py:443), env-major: row (e, t) at e*T + t — issued from inside the
+        // forward, behind its operand reads
+        forward_slice<DP, KS, MW>(w, xs, part,
+                                  RowStore<DP, FULL>{xs, ex.obs + (size_t)t * DP, (long long)blockIdx.x * EPW, v.n, (size_t)T * DP, EPW});
         PFA_RSTAMP(t, 1);
-        forward_slice<DP, KS, MW>(w, xs, part);
         PFA_RSTAMP(t, 2);
         lds_barrier();
         PFA_RSTAMP(t, 3);
@@ -179,7 +192,9 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(Squar
                     if ((long long)s.rounds >= filled) v.hdr->underrun = 1;
                     squared_reset_nt1(v, s, grid, t1, next_cell, reward, terminal);
                     s.rounds += 1;
-                    slot = slot + 1 == (uint32_t)v.tape_rounds ? 0u : slot + 1;
+                    const bool wrap = slot + 1 == (uint32_t)v.tape_rounds;
+                    slot = wrap ? 0u : slot + 1;
+                    tape_at = wrap ? tape_e : tape_at + tape_n;
                 } else {
                     squared_step_nt1(v, s, grid, t1, rtab, sm.action, reward, terminal);
                 }
@@ -206,7 +221,7 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_squared_kernel(Squar
             ex.values[row] = sm.value;
             // the next reset's target, re-fetched every step (a conditional fetch would make next_cell a phi whose copy waits for
             // the load at once); the value a reset consumes was requested at least one whole step earlier
-            if (NT1) next_cell = v.tape[(size_t)slot * tape_n + e];
+            if (NT1) next_cell = *tape_at;
         }
         if (nz && t + 1 < T) q_next = nz[(size_t)(t + 1) * nz_step];
         PFA_RSTAMP(t, 6);
@@ -366,10 +381,11 @@ static int launch_rollout_squared(const TilePolicy &p, void *state, const pfa_sq
     // 16 envs per workgroup (an 8-env variant — two workgroups per CU at N = 4096 — and four helper waves for the stores and the
     // noise both measured no better in round 2: tools/probe_rollout.py); the single-target env form when it applies.
     const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);
-    const bool nt1 = cfg->num_targets == 1;
+    const bool nt1 = cfg->num_targets == 1, full = cfg->num_envs % 16 == 0;
     dispatch_tile(p, [&](auto tile) {
         using T = decltype(tile);
-        auto *kernel = nt1 ? rollout_mlp_squared_kernel<T::DP, 16, true, T::KS, T::MW> : rollout_mlp_squared_kernel<T::DP, 16, false, T::KS, T::MW>;
+        auto *kernel = nt1 ? (full ? rollout_mlp_squared_kernel<T::DP, 16, true, T::KS, T::MW, true> : rollout_mlp_squared_kernel<T::DP, 16, true, T::KS, T::MW, false>)
+                           : (full ? rollout_mlp_squared_kernel<T::DP, 16, false, T::KS, T::MW, true> : rollout_mlp_squared_kernel<T::DP, 16, false, T::KS, T::MW, false>);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRollThreads), 0, (hipStream_t)stream, v, p.pv, p.pv.a, *exp, noise, seed, step,
                            (long long)env_offset, obs, rewards, terminals, truncations, masks);
     });

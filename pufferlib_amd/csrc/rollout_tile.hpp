@@ -114,9 +114,58 @@ __device__ __forceinline__ void unstage_rows(const float *xs, float *dst, long l
     }
 }
 
+// unstage_rows in two halves, for a caller that wants other work between the LDS read and the global store (forward_slice's hook).
+// FULL: the caller vouches that all 16 rows of the tile exist; tile_rows and the row guard are not looked at.  Where the tile is a
+// whole number of passes of the workgroup (rows of 64 or 128 floats) the stores then stand in straight-line code, where the compiler
+// can count them: a later wait for an older load becomes vmcnt(n) instead of a vmcnt(0) that also waits for these stores.
+template <int DP, bool FULL>
+struct RowStore {
+    static constexpr int XS = XTile<DP>::XS, V = DP / 4, kPasses = (16 * V + kRollThreads - 1) / kRollThreads;
+    const float *xs;
+    float *dst;
+    long long first_row, rows;
+    size_t row_stride;
+    int tile_rows;
+    float2 lo2[kPasses], hi2[kPasses];
+    __device__ __forceinline__ bool live(int j) const {
+        if constexpr (FULL) {
+            if (16 * V >= (j + 1) * kRollThreads) return true;
+        }
+        const int idx = threadIdx.x + j * kRollThreads;
+        return idx < (FULL ? 16 : tile_rows) * V && (FULL || first_row + idx / V < rows);
+    }
+    __device__ __forceinline__ void read() {
+#pragma unroll
+        for (int j = 0; j < kPasses; ++j) {
+            const int idx = threadIdx.x + j * kRollThreads, r = idx / V, c4 = idx - r * V;
+            if (live(j)) {
+                const float2 *sp = reinterpret_cast<const float2 *>(xs + r * XS + 4 * c4);
+                lo2[j] = sp[0], hi2[j] = sp[1];
+            }
+        }
+    }
+    __device__ __forceinline__ void store() const {
+#pragma unroll
+        for (int j = 0; j < kPasses; ++j) {
+            const int idx = threadIdx.x + j * kRollThreads, r = idx / V, c4 = idx - r * V;
+            if (live(j))
+                *reinterpret_cast<float4 *>(dst + (size_t)(first_row + r) * row_stride + 4 * c4) =
+                    make_float4(lo2[j].x, lo2[j].y, hi2[j].x, hi2[j].y);
+        }
+    }
+};
+struct NoHook {
+    __device__ __forceinline__ void read() {}
+    __device__ __forceinline__ void store() const {}
+};
+
 // This wave's slice of models.Default.forward (models.py:41-62) for the 16 rows in xs -> part[wave][o * kPartStride + row].
-template <int DP, int KS = DP / 4, int MW = kMW>   // MW = 1 or even
-__device__ __forceinline__ void forward_slice(const SliceFrags<DP, KS, MW> &w, const float *xs, float (*part)[kPartFloats]) {
+// `hook` (a RowStore) rides along: its LDS read is issued behind the B operand reads and its global store behind the first layer's
+// products.  The fused rollout stores its observation rows this way; in front of the forward, the store's read and the wait for it
+// stood before the operand reads, two LDS latencies in sequence ahead of the first product.
+template <int DP, int KS = DP / 4, int MW = kMW, class Hook = NoHook>   // MW = 1 or even
+__device__ __forceinline__ void forward_slice(const SliceFrags<DP, KS, MW> &w, const float *xs, float (*part)[kPartFloats],
+                                              Hook hook = Hook{}) {
     constexpr int XS = XTile<DP>::XS;
     const int wv = wave_id(), c = lane_id() & 15, g = lane_id() >> 4;
     f32x4 h[MW];
@@ -129,19 +178,26 @@ __device__ __forceinline__ void forward_slice(const SliceFrags<DP, KS, MW> &w, c
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) bv[kk] = xs[c * XS + 4 * kk + g];
     __builtin_amdgcn_sched_barrier(0);
+    hook.read();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) {
 #pragma unroll
         for (int i = 0; i < MW; ++i) h[i] = mfma16(w.w1f[i][kk], bv[kk], h[i]);
     }
+    hook.store();
     // the heads' contraction over this wave's 16 MW hidden units: two accumulator chains (even / odd tiles)
+    // ReLU as max(bits, 0) on the integer view: one instruction where fmaxf is two (canonicalise + max), and exact — negative floats
+    // and -0 are negative integers, positive floats pass unchanged (the gradient kernel's form, ppo_update.hip).  Only a NaN without
+    // the sign bit differs: it stays a NaN where fmaxf(NaN, 0) is 0.
+    const auto relu = [](float x) { return __int_as_float(max(__float_as_int(x), 0)); };
     f32x4 o0 = f32x4{w.bo[0], w.bo[1], w.bo[2], w.bo[3]}, o1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < MW; i += 2) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            o0 = mfma16(w.w2f[i][r], fmaxf(h[i][r], 0.0f), o0);
-            if constexpr (MW >= 2) o1 = mfma16(w.w2f[i + 1][r], fmaxf(h[i + 1][r], 0.0f), o1);
+            o0 = mfma16(w.w2f[i][r], relu(h[i][r]), o0);
+            if constexpr (MW >= 2) o1 = mfma16(w.w2f[i + 1][r], relu(h[i + 1][r]), o1);
         }
     }
     const f32x4 po = o0 + o1;  // partial out^T[o = 4g + r][row = c]

@@ -20,7 +20,8 @@ __device__ __forceinline__ LaneSample sample_row16(float mine, int lo, int a, fl
     const float ex_ = is_logit ? expf(mine - mx) : 0.0f;
     const float se = row16_sum(ex_);
     const float lse = mx + logf(se);
-    // argmax of p/q with torch's first-index tie rule
+    // argmax of p/q with torch's first-index tie rule.  p >= +0 and q is an Exp(1) draw (> 0), so the ratio is >= +0, or -inf on the
+    // lanes outside the head: the domain row16_argmax's integer compares need (lane_ops.hpp)
     float best = is_logit ? (ex_ / se) / q : -INFINITY;
     int besti = lo;
     row16_argmax(best, besti);

@@ -233,7 +233,8 @@ __device__ __forceinline__ void squared_step(const SquaredView &v, SquaredEnv &s
 // launch or per episode taken out of the step: the target's (x, y) lives in registers (no `c / g` per step), the reward
 // 1 - k/d comes from a table of the 2d+1 possible Chebyshev distances built once per launch with the same f64 division
 // (`RewardTable`: bit-identical by construction), and a reset clears the two cells that can be non-zero (agent, target
-// marker) instead of the whole grid.  The fused-vs-stepwise test (which runs the general form) pins the equivalence.
+// marker) instead of the whole grid.  Cell indices use the full-rate 24-bit multiply (coordinates and g are below 2^23; v_mul_lo_u32
+// is quarter rate).  The fused-vs-stepwise test (which runs the general form) pins the equivalence.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kMaxRewardDist = 32;   // table entries; distances beyond it (never reached: k <= 2d <= 10) take the division
 
@@ -263,9 +264,9 @@ template <typename GridPtr>
 __device__ __forceinline__ void squared_reset_nt1(const SquaredView &v, SquaredEnv &s, GridPtr grid, Target1 &tg, uint16_t new_cell,
                                                   float &reward, bool &terminal) {
     const int g = v.g, d = v.d;
-    grid[s.x * g + s.y] = 0.0f;       // the only cells a finished episode leaves non-zero: the agent and the target marker
+    grid[__mul24(s.x, g) + s.y] = 0.0f;       // the only cells a finished episode leaves non-zero: the agent and the target marker
     grid[tg.cell] = 0.0f;
-    grid[d * g + d] = -1.0f;
+    grid[__mul24(d, g) + d] = -1.0f;
     s.x = d;
     s.y = d;
     s.tick = 0;
@@ -284,7 +285,7 @@ __device__ __forceinline__ void squared_step_nt1(const SquaredView &v, SquaredEn
                                                  const RewardTable &rt, int action, float &reward, bool &terminal) {
     const int g = v.g, d = v.d;
     int x = s.x, y = s.y;
-    grid[x * g + y] = 0.0f;
+    grid[__mul24(x, g) + y] = 0.0f;
     int dx, dy;
     squared_move(action & 7, dx, dy);
     x += dx;
@@ -305,7 +306,7 @@ __device__ __forceinline__ void squared_step_nt1(const SquaredView &v, SquaredEn
     if ((ox > oy ? ox : oy) >= d) { x = d; y = d; }         // teleport home on the perimeter (:500-504)
     s.x = x;
     s.y = y;
-    grid[x * g + y] = -1.0f;
+    grid[__mul24(x, g) + y] = -1.0f;
     s.tick += 1;
     const bool done = s.tick >= d;                          // max_ticks = num_targets * d
     s.ep_ret += r;

@@ -45,7 +45,9 @@ def main():
     vec.ensure_tape(128)
     torch.cuda.synchronize()
     key = _lib.NoiseKey(1, 12345)
-    args = (vec.state.data_ptr(), C.byref(vec.cfg), fp.flat.data_ptr(), C.byref(fp.dims), C.byref(ex.c), None, C.byref(key), 0,
+    # an explicit noise tensor, as clean_pufferl.evaluate passes one: the in-kernel Philox path is not what the bench runs
+    noise = torch.empty(128, 4096, fp.dims.num_actions, device='cuda').exponential_(1)
+    args = (vec.state.data_ptr(), C.byref(vec.cfg), fp.flat.data_ptr(), C.byref(fp.dims), C.byref(ex.c), noise.data_ptr(), C.byref(key), 0,
             vec.obs_buf.data_ptr(), vec.rewards.data_ptr(), vec.terminals_u8.data_ptr(), vec.truncations_u8.data_ptr(), vec.masks_u8.data_ptr(),
             None)
     assert L.pfa_probe_set_rollout_trace(tr.data_ptr(), T0, STEPS) == 0
@@ -56,7 +58,7 @@ def main():
     torch.cuda.synchronize()
     print(f'kernel {e0.elapsed_time(e1) * 1e3:.1f} us for 128 steps (default stream, probe build)')
     t = tr.cpu().numpy()
-    names = ['store obs', 'forward', 'barrier 1', 'noise', 'sample', 'env step + scalars', 'barrier 2']
+    names = ['forward + obs store', '-', 'barrier 1', 'noise', 'sample', 'env step + scalars', 'barrier 2']
     print('ticks per phase (wave: mean over steps %d..%d)' % (T0, T0 + STEPS - 1))
     for w in range(4):
         d = np.diff(t[w, :, :8], axis=1).astype(float)                    # [steps][7]
