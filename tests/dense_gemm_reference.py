@@ -127,15 +127,19 @@ def _split3(x):
 
 TERMS = (('lo', 'hi'), ('hi', 'lo'), ('mid', 'mid'), ('mid', 'hi'), ('hi', 'mid'), ('hi', 'hi'))     # (piece of A, piece of B), small first
 DROPPABLE = TERMS[:3]                                                                              # the three terms at 2^-16 relative
+INT_TERMS = (('hi', 'lo'), ('hi', 'mid'), ('hi', 'hi'))      # A holds integers 0 .. 255 (one exact bf16 piece): the kernel issues three terms
+INT_DROPPABLE = INT_TERMS[:1]
 
 
-def bf16x6_rows(A, B, drop=None):
+def bf16x6_rows(A, B, drop=None, a_int=False):
     """A B^T as igemm_rows_split_kernel forms it: per 32-deep slab the six partial products in the kernel's order, each added to the fp32
-    accumulator (a bf16 x bf16 product is exact in fp32; the 32 of a slab are summed in fp32).  drop: one of TERMS to leave out."""
+    accumulator (a bf16 x bf16 product is exact in fp32; the 32 of a slab are summed in fp32).  drop: one of TERMS to leave out.
+    a_int: A is integer bytes as floats (the uint8 conv operands) — the three terms of INT_TERMS."""
     a, b = _split3(torch.from_numpy(A)), _split3(torch.from_numpy(B))
+    assert not a_int or bool((a['hi'] == torch.from_numpy(A)).all())
     acc = torch.zeros(A.shape[0], B.shape[0])
     for s in range(0, A.shape[1], 32):
-        for pa, pb in TERMS:
+        for pa, pb in (INT_TERMS if a_int else TERMS):
             if (pa, pb) != drop:
                 acc = acc + a[pa][:, s:s + 32] @ b[pb][:, s:s + 32].T
     return acc.numpy()
