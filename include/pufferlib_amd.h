@@ -760,6 +760,17 @@ int pfa_cnn_pack_fc(const float *w, int32_t N, int32_t channels, int32_t hw, flo
 int pfa_cnn_heads_sample(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
                          const float *value_b, int32_t num_actions, const float *noise, const pfa_noise_key *key, int64_t row_offset,
                          int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream);
+/* policy(frames, action=...) on the same heads: log-probability of the GIVEN actions (int64 [rows], each in 0 .. num_actions - 1: the
+ * caller checks), entropy (nullable) and value — for the action pfa_cnn_heads_sample drew from the same h, its log-probability and value
+ * bit for bit — and the backward for upstream gradients g_logprob / g_entropy / g_value [rows] (each nullable = zero), recomputed from h:
+ * dout [rows][16] (column j < num_actions: g_logprob (1[j = action] - p_j) - g_entropy p_j (log p_j + entropy), column num_actions:
+ * g_value, the rest 0) and dh [rows][hidden] = d / d (pre-ReLU hidden), masked and summed as in pfa_cnn_heads_loss. */
+int pfa_cnn_heads_eval(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+                       const float *value_b, int32_t num_actions, const int64_t *actions, float *logprob, float *entropy, float *value,
+                       pfa_stream_t stream);
+int pfa_cnn_heads_eval_backward(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+                                const float *value_b, int32_t num_actions, const int64_t *actions, const float *g_logprob,
+                                const float *g_entropy, const float *g_value, float *dout, float *dh, pfa_stream_t stream);
 size_t pfa_cnn_heads_loss_workspace_bytes(void);
 int pfa_cnn_heads_loss(const float *h, int32_t hidden, const pfa_experience *exp, int64_t batch_rows, int32_t mb, int64_t q0, int64_t rows,
                        const float *actor_w, const float *actor_b, const float *value_w, const float *value_b, int32_t num_actions,

@@ -307,6 +307,8 @@ _SIGNATURES = {
     'pfa_cnn_transpose': (C.c_int, [P, C.c_int32, C.c_int32, P, P]),
     'pfa_cnn_pack_fc': (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, P, P]),
     'pfa_cnn_heads_sample': (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, P, C.c_int32, P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P]),
+    'pfa_cnn_heads_eval': (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, P, C.c_int32, P, P, P, P, P]),
+    'pfa_cnn_heads_eval_backward': (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, P, C.c_int32, P, P, P, P, P, P, P]),
     'pfa_cnn_heads_loss': (C.c_int, [P, C.c_int32, C.POINTER(Experience), C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P, P, C.c_int32,
                                      C.POINTER(PpoHparams), P, C.c_int64, P, P, P, C.c_int32, P, P]),
     'pfa_cnn_heads_loss_workspace_bytes': (C.c_size_t, []),

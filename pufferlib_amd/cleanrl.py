@@ -4,10 +4,13 @@
 multinomial draw is argmax(softmax(logits)/q) with q ~ Exp(1) from either an explicit ``noise`` tensor (parity with
 torch.multinomial given its exponential draw) or the Philox stream keyed by ``seed`` (include/pufferlib_amd.h).
 ``policy(obs, action=...)`` (training mode, cleanrl.py:60-66,87-93) returns the log-probability of the GIVEN actions, the entropy and
-the value through the GEMM path (pufferlib_amd.general.Evaluator) for every policy shape.  By default these are plain tensors (the
+the value through the GEMM path (pufferlib_amd.general.Evaluator) — the feed-forward NatureCNN with up to 15 actions through its own
+engine's head kernels (cnn.Engine.policy_eval: the bits of the rollout for the action it drew).  By default these are plain tensors (the
 gradients of clean_pufferl.train() are computed by its own kernels); ``Policy(policy, autograd=True)`` / ``RecurrentPolicy(policy,
 autograd=True)`` attach an autograd graph to logprob, entropy and value of that call, so that a loss built from them in torch ops trains
-the policy with ``loss.backward()``, ``clip_grad_norm_`` and any torch optimizer over ``policy.parameters()`` (general.Evaluator).
+the policy with ``loss.backward()``, ``clip_grad_norm_`` and any torch optimizer over ``policy.parameters()`` (general.Evaluator for
+models.Default, alone or under LSTMWrapper; cnn.Engine.eval_backward for the feed-forward models.Convolutional with up to 15 actions,
+one chunk of frames per call).
 
 Policy shapes outside the fused kernels' envelope (Default(hidden_size != 128), observation rows wider than 128 / 160 floats, more
 than 15 logits, LSTMWrapper sizes other than (128, 128), LSTMWrapper over the NatureCNN, the NatureCNN with 16 .. 1024 actions) adopt a
@@ -18,7 +21,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .models import ConvParams, FlatParams, ResnetParams, find_cnn, find_resnet
+from .models import ConvParams, FlatParams, ResnetParams, find_cnn, find_lstm, find_resnet
 
 KERNEL_STRIDES = (16, 32, 64, 96, 128)     # observation row strides (floats) every policy kernel is built for
 RECURRENT_STRIDES = KERNEL_STRIDES + (160,)  # the recurrent path also takes MiniGrid-shaped 160-byte rows (SURVEY config C3)
@@ -100,8 +103,6 @@ def _evaluator(self, device, recurrent):
             net = eng.net if eng is not None else general._net_for_general(self._flat)
         elif isinstance(self._flat, ResnetParams):
             raise NotImplementedError('policy(frames, action=...) for models.ProcgenResnet: use train()')
-        elif isinstance(self._flat, ConvParams):
-            raise NotImplementedError('policy(obs, action=...) for the non-recurrent models.Convolutional: wrap it in LSTMWrapper or use train()')
         else:
             net = general.net_for_flat(self._flat)
         self._evaluator = general.Evaluator(net)
@@ -116,12 +117,17 @@ def _evaluator(self, device, recurrent):
     return self._evaluator
 
 
-def _check_autograd(policy_module, autograd):
-    """autograd=True is built for MLP encoders; said at construction, where no GPU is needed."""
-    if autograd and (find_cnn(policy_module) is not None or find_resnet(policy_module) is not None):
+def _check_autograd(policy_module, autograd, recurrent=False):
+    """autograd=True is built for MLP encoders and for the NatureCNN in the conv engine (feed-forward, up to 15 actions); said at
+    construction, where no GPU is needed."""
+    cnn = find_cnn(policy_module)
+    fused_cnn = (cnn is not None and find_resnet(policy_module) is None and not recurrent and find_lstm(policy_module) is None
+                 and int(cnn.actor.weight.shape[0]) <= 15)
+    if autograd and not fused_cnn and (cnn is not None or find_resnet(policy_module) is not None):
         raise NotImplementedError('autograd=True with a convolutional encoder (models.Convolutional, models.ProcgenResnet): autograd through '
-                                  'policy(obs, action=...) is built for models.Default, alone or under LSTMWrapper; the conv encoders\' backward '
-                                  'is not wired to it — train them with clean_pufferl.train()')
+                                  'policy(obs, action=...) is built for models.Default, alone or under LSTMWrapper, and for the feed-forward '
+                                  'models.Convolutional with up to 15 actions; the other conv encoders\' backward is not wired to it — train '
+                                  'them with clean_pufferl.train()')
     return bool(autograd)
 
 
@@ -208,7 +214,7 @@ class Policy(torch.nn.Module):
             # given actions (cleanrl.py:60-66 with action=...): log-prob / entropy / value of THOSE actions; or a policy shape that
             # runs in the GEMM path altogether
             if find_cnn(self.policy) is not None and not general_shape:
-                raise NotImplementedError('policy(frames, action=...) for the non-recurrent models.Convolutional')
+                return self._forward_cnn(x2, rows, noise, action)      # the conv engine's own heads on given actions (csrc/cnn_heads.hip)
             if action is None and find_cnn(self.policy) is None:
                 out = self._forward_tile(x2, rows, D, noise)     # Default(64 / 256 / 512): the tile code the fused rollout runs
                 if out is not None:
@@ -281,13 +287,69 @@ def _forward_tile(self, x2, rows, D, noise):
 
 
 
-def _forward_cnn(self, x2, rows, noise):
-    """policy(frames) for models.Convolutional: uint8 (rows, frame bytes in the env's order) -> (actions, logprob, entropy, value)."""
+class _ConvEvalGrad(torch.autograd.Function):
+    """logprob, entropy, value of cnn.Engine.policy_eval as functions of the module parameters (the only tensor inputs, in
+    named_parameters() order, so autograd itself accumulates into their .grad): the forward is the plain launch sequence on one chunk,
+    the backward cnn.Engine.eval_backward — which runs the forward again where another call has overwritten the engine's activations
+    since, and reads the parameters as they are when it runs.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, eng, frames, rows, actions, *params):
+        dev = frames.device
+        logprob, entropy, value = (torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(3))
+        eng._alloc(rows)
+        eng.policy_eval(frames, rows, actions, logprob, entropy, value)
+        ctx.eng, ctx.frames, ctx.rows, ctx.actions, ctx.generation = eng, frames, rows, actions, eng.generation
+        ctx.set_materialize_grads(False)            # an output the loss does not use arrives as None: a null pointer to the kernel
+        return logprob, entropy, value.unsqueeze(1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logprob, g_entropy, g_value):
+        eng, rows = ctx.eng, ctx.rows
+        g = [None if x is None else x.detach().to(device=ctx.frames.device, dtype=torch.float32).reshape(rows).contiguous()
+             for x in (g_logprob, g_entropy, g_value)]
+        gv = eng.cp.split(eng.eval_backward(ctx.frames, rows, ctx.actions, *g, generation=ctx.generation))
+        return (None,) * 4 + tuple(gv[name] if need else None for name, need in zip(eng.cp.names, ctx.needs_input_grad[4:]))
+
+
+def _score_cnn(self, cp, frames, rows, action, aliased):
+    """policy(frames, action=...) for models.Convolutional in the conv engine: (action, logprob, entropy, value) of the GIVEN actions."""
+    eng, dev, A = self.cnn_engine, frames.device, cp.num_actions
+    a = action.to(dev).reshape(-1).to(torch.int64).contiguous()
+    if a.numel() != rows:
+        raise ValueError(f'{a.numel()} actions for {rows} frames')
+    # the kernel compares the action with its lane index: one outside the head would score as log-probability 0 (one host round trip,
+    # as on the GEMM path: not the rollout)
+    if rows and bool(((a < 0) | (a >= A)).any()):
+        raise IndexError(f'action out of range for Discrete({A})')
+    if self.autograd and torch.is_grad_enabled() and rows:
+        eng.check_one_chunk(rows)
+        if aliased:                                  # the backward reads the frames again: keep them from the caller's later writes
+            frames = frames.clone()
+        logprob, entropy, value = _ConvEvalGrad.apply(eng, frames, rows, a, *(p for _, p in cp.net.named_parameters()))
+        return action, logprob, entropy, value
+    eng._alloc(min(rows, 8192))
+    logprob, entropy, value = (torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(3))
+    eng.policy_eval(frames, rows, a, logprob, entropy, value)
+    return action, logprob, entropy, value.unsqueeze(1)
+
+
+def _forward_cnn(self, x2, rows, noise, action=None):
+    """policy(frames) for models.Convolutional: uint8 (rows, frame bytes in the env's order) -> (actions, logprob, entropy, value);
+    with `action` (models.Convolutional only) the given actions are scored instead of sampled."""
     cp = self.adopt(0, x2.device)
     if x2.shape[1] != cp.obs_dim:
         raise ValueError(f'expected frames of {cp.obs_dim} bytes, got rows of {x2.shape[1]}')
     frames = x2.to(torch.uint8).contiguous()       # the reference divides whatever it is given by 255 (models.py:152); frames are bytes
     eng = self.cnn_engine
+    if self.autograd:     # somebody's torch optimizer may step the nn.Parameters themselves: the packed conv operands follow their
+        seen = tuple(p._version for p in cp.net.parameters())      # version counters (the `watch` of general.Net.pack)
+        if seen != getattr(eng, 'watched', seen):
+            eng.version += 1
+        eng.watched = seen
+    if action is not None:
+        return _score_cnn(self, cp, frames, rows, action, frames.data_ptr() == x2.data_ptr())
     eng._alloc(min(rows, 8192 if isinstance(cp, ConvParams) else 4096))
     dev = x2.device
     actions = torch.empty(rows, dtype=torch.int64, device=dev)
@@ -321,7 +383,7 @@ class RecurrentPolicy(torch.nn.Module):
 
     def __init__(self, policy, seed=0, autograd=False):
         super().__init__()
-        self.autograd = _check_autograd(policy, autograd)
+        self.autograd = _check_autograd(policy, autograd, recurrent=True)
         self.policy = policy
         self.noise_seed = int(seed)
         self.noise_step = 0

@@ -6,6 +6,8 @@ channel-last, downsampled, odd widths — through the strided loader (mode 4); h
   Layer.forward / backward_dx / backward_dw      one conv or linear layer = one kernel launch each
   Engine.forward(frames)                         the rollout / training forward of a batch of uint8 frames -> hidden [n][hidden width]
   Engine.policy_step(frames, ...)                policy(obs) in rollout mode: + heads + sample_logits (csrc/cnn_heads.hip)
+  Engine.policy_eval(frames, ..., actions, ...)  policy(obs, action=...): the heads on given actions
+  Engine.eval_backward(frames, ..., g_*)         its backward for upstream gradients of (logprob, entropy, value) -> flat gradient
   Engine.update(mb, ...)                         forward + PPO loss + backward of one minibatch (in chunks of `chunk` rows) ->
                                                  flat gradient in named_parameters() order + the 16-float loss tail
 
@@ -141,6 +143,7 @@ class Engine:
         self.chunk = 0
         self.packed_version = -1
         self.version = 0          # bumped by whoever changes the weights (optimizer step, checkpoint load)
+        self.generation = 0       # bumped by every forward(): whose activations a1/a2/a3/h hold (eval_backward re-runs a forward not its own)
         self._alloc(chunk)
 
     def _build_layers(self, geo):
@@ -161,6 +164,7 @@ class Engine:
             return
         dev, n, H = self.dev, chunk, self.hidden
         self.chunk = n
+        self.generation += 1      # fresh buffers hold nobody's activations
         self._alloc_maps(n)
         self.h = torch.empty(n, H, device=dev)
         self.dh = torch.empty_like(self.h)
@@ -194,6 +198,7 @@ class Engine:
         """frames uint8 [n][frame_bytes] (the env's own byte order) -> self.h[:n] (hidden, post-ReLU); keeps a1/a2/a3 for a backward."""
         assert n <= self.chunk
         self.pack()
+        self.generation += 1
         self.conv1.forward(frames, n, self.a1)
         self.conv2.forward(self.a1, n, self.a2)
         self.conv3.forward(self.a2, n, self.a3)
@@ -213,6 +218,53 @@ class Engine:
                                               _lib.ptr(actions[lo:lo + m]), _lib.ptr(logprob[lo:lo + m]),
                                               None if entropy is None else _lib.ptr(entropy[lo:lo + m]), _lib.ptr(value[lo:lo + m]),
                                               _lib.stream_handle()), 'cnn_heads_sample')
+
+    def _head_pointers(self):
+        v = self.cp.views
+        return (_lib.ptr(v['actor.weight']), _lib.ptr(v['actor.bias']), _lib.ptr(v['value_fn.weight']), _lib.ptr(v['value_fn.bias']), self.cp.num_actions)
+
+    def policy_eval(self, frames, n, actions, logprob, entropy, value):
+        """policy(obs, action=...) for n frames (any n: processed in chunks): log-probability of the given actions (int64 [n], each in
+        0 .. num_actions - 1: the caller checks), entropy, value."""
+        L = _lib.lib()
+        for lo in range(0, n, self.chunk):
+            m = min(self.chunk, n - lo)
+            h = self.forward(frames[lo:lo + m], m)
+            _lib.check(L.pfa_cnn_heads_eval(_lib.ptr(h), self.hidden, m, *self._head_pointers(), _lib.ptr(actions[lo:lo + m]),
+                                            _lib.ptr(logprob[lo:lo + m]), None if entropy is None else _lib.ptr(entropy[lo:lo + m]),
+                                            _lib.ptr(value[lo:lo + m]), _lib.stream_handle()), 'cnn_heads_eval')
+
+    def check_one_chunk(self, n):
+        if n > self.max_chunk:
+            raise ValueError(f'{n} frames in one autograd call: this frame geometry allows at most {self.max_chunk} (Engine.max_chunk); split the batch')
+
+    def eval_backward(self, frames, n, actions, g_logprob, g_entropy, g_value, generation=None):
+        """d (sum of g . (logprob, entropy, value) of policy_eval) / d parameters for n frames of one chunk: a fresh flat buffer in
+        named_parameters() order.  A None upstream gradient is zero.  generation: self.generation as the caller's forward left it — when
+        it is still current the activations are that forward's, otherwise (None, or another forward ran since) the forward runs again."""
+        self.check_one_chunk(n)
+        L = _lib.lib()
+        cp = self.cp
+        stream = _lib.stream_handle()
+        self._alloc(n)
+        if generation is None or generation != self.generation:
+            self.forward(frames, n)
+        h = self.h[:n]
+        _lib.check(L.pfa_cnn_heads_eval_backward(_lib.ptr(h), self.hidden, n, *self._head_pointers(), _lib.ptr(actions), _lib.ptr(g_logprob),
+                                                 _lib.ptr(g_entropy), _lib.ptr(g_value), _lib.ptr(self.dout), _lib.ptr(self.dh), stream),
+                   'cnn_heads_eval_backward')
+        a = _operand(MODE_DENSE, h, self.hidden)
+        _lib.check(L.pfa_igemm_weights(C.byref(a), n, self.hidden, _lib.ptr(self.dout), 16, 16, _lib.ptr(self.g16), 1, 0, _lib.ptr(self.gb16),
+                                       _lib.ptr(self.ws), stream), 'heads_dw')
+        grads = torch.zeros(cp.count, device=self.dev)
+        gv = cp.split(grads)
+        self.backward(frames, n, self.dh, gv, False)
+        A = cp.num_actions
+        gv['actor.weight'].copy_(self.g16[:A])
+        gv['actor.bias'].copy_(self.gb16[:A])
+        gv['value_fn.weight'].copy_(self.g16[A:A + 1])
+        gv['value_fn.bias'].copy_(self.gb16[A:A + 1])
+        return grads
 
     # ------------------------------------------------------------------------------------------------------------- update
     def backward(self, frames, m, dh_pre, gv, acc):

@@ -3,6 +3,8 @@
 //   cnn_heads_sample   rollout: logits, value, sample_logits (cleanrl.py:25-47) -> action, log-prob, entropy, value
 //   cnn_heads_loss     training: the same heads, the PPO loss of clean_pufferl.py:202-238, d loss / d (head outputs) [rows][16],
 //                      d loss / d (pre-ReLU hidden) [rows][H], the six loss sums (f64, (hi, lo) float pairs)
+//   cnn_heads_eval     policy(frames, action=...): log-prob of GIVEN actions, entropy, value (the rollout's bits for the action it drew)
+//   cnn_heads_eval_backward  its backward for arbitrary upstream gradients: d / d (head outputs) [rows][16], d / d (pre-ReLU hidden)
 //   cnn_gather_frames  the uint8 frames of a chunk of minibatch rows, copied next to each other (rows of a minibatch are
 //                      bptt_horizon-long segments of the env-major experience, clean_pufferl.py:455-457)
 // 16 lanes per row (lane lo = head output lo), the row's hidden vector in LDS, head weights in LDS (padded rows: conflict-free),
@@ -72,6 +74,114 @@ __global__ void __launch_bounds__(256) cnn_heads_sample_kernel(const float *h, i
             if (entropy) entropy[row] = sm.entropy;
             value[row] = sm.value;
         }
+    }
+}
+
+// d loss / d h[u] = sum_o d_o W2v[o][u] for the row of the 16 lanes that hold d (lane lo: d of head output lo); lane lo owns
+// u = lo, lo + 16, ...  (the hidden vector is relu(Linear(...)): hand back d loss / d (pre-activation), i.e. masked by relu')
+template <int HT>
+__device__ __forceinline__ void cnn_heads_dh(float d, const float *w2v, const float *hs, int le, int lo, int a, bool ok, long long row, float *dh,
+                                             int hrt) {
+    const int H = HT ? HT : hrt;
+    if (HT) {
+        float dhv[(HT ? HT : 16) / 16];
+#pragma unroll
+        for (int j = 0; j < HT / 16; ++j) dhv[j] = 0.0f;
+        for (int o = 0; o <= a; ++o) {
+            const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
+#pragma unroll
+            for (int j = 0; j < HT / 16; ++j) dhv[j] = fmaf(d_o, w2v[o * (HT + 1) + lo + 16 * j], dhv[j]);
+        }
+        if (ok) {
+#pragma unroll
+            for (int j = 0; j < HT / 16; ++j) dh[row * HT + lo + 16 * j] = hs[le * HT + lo + 16 * j] > 0.0f ? dhv[j] : 0.0f;
+        }
+    } else {   // any width: the same fma chains over o, eight columns of the lane at a time
+        for (int j0 = 0; j0 < H / 16; j0 += 8) {
+            float dhv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dhv[j] = 0.0f;
+            for (int o = 0; o <= a; ++o) {
+                const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j0 + j < H / 16) dhv[j] = fmaf(d_o, w2v[o * (H + 1) + lo + 16 * (j0 + j)], dhv[j]);
+            }
+            if (ok) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j0 + j < H / 16) dh[row * H + lo + 16 * (j0 + j)] = hs[le * H + lo + 16 * (j0 + j)] > 0.0f ? dhv[j] : 0.0f;
+            }
+        }
+    }
+}
+
+// policy(frames, action=...): the heads on GIVEN actions.  The softmax is eval_row16_heads (sampler.hpp, what the LSTM eval runs): its
+// normalised logit is the expression sample_row16 forms, so the log-probability of an action cnn_heads_sample drew, and the value, come
+// out as the same bits; the entropy is -sum nl p (the loss kernel's form).  The action is compared against the lane index, never indexed by.
+template <int HT>
+__global__ void __launch_bounds__(256) cnn_heads_eval_kernel(const float *h, int hrt, long long rows, CnnHeads hd, const long long *actions,
+                                                            float *logprob, float *entropy, float *value) {
+    extern __shared__ float lds[];
+    const int H = HT ? HT : hrt;
+    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;   // hs [16][H]
+    cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
+    const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
+    const long long tiles = (rows + 15) / 16;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 16 * H; i += 256) {
+            const long long r = tile * 16 + i / H;
+            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
+        }
+        __syncthreads();
+        const long long row = tile * 16 + le;
+        const bool ok = row < rows;
+        const int action = ok ? (int)actions[row] : 0;
+        const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
+        const Row16Eval ev = eval_row16_heads(mine, lo, a, 0, action);
+        const float v = row16_sum(lo == a ? mine : 0.0f);
+        if (ok && lo == 0) {
+            logprob[row] = ev.logprob;
+            if (entropy) entropy[row] = ev.entropy;
+            value[row] = v;
+        }
+    }
+}
+
+// Its backward for upstream gradients g_logprob / g_entropy / g_value [rows] (null = zero): the softmax recomputed by the forward's code
+// from h alone, dout [rows][16] (columns < a: g_logprob (1[j = action] - p_j) - g_entropy p_j (nl_j + entropy), column a: g_value, the
+// rest 0) and d / d (pre-ReLU hidden) [rows][H] with the loss kernel's mask and summation order.
+template <int HT>
+__global__ void __launch_bounds__(256) cnn_heads_eval_backward_kernel(const float *h, int hrt, long long rows, CnnHeads hd, const long long *actions,
+                                                                     const float *g_logprob, const float *g_entropy, const float *g_value,
+                                                                     float *dout /* [rows][16] */, float *dh /* [rows][H] */) {
+    extern __shared__ float lds[];
+    const int H = HT ? HT : hrt;
+    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;
+    cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
+    const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
+    const long long tiles = (rows + 15) / 16;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 16 * H; i += 256) {
+            const long long r = tile * 16 + i / H;
+            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
+        }
+        __syncthreads();
+        const long long row = tile * 16 + le;
+        const bool ok = row < rows;
+        const int action = ok ? (int)actions[row] : 0;
+        const float g_lp = ok && g_logprob ? g_logprob[row] : 0.0f;
+        const float g_ent = ok && g_entropy ? g_entropy[row] : 0.0f;
+        const float g_v = ok && g_value ? g_value[row] : 0.0f;
+        const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
+        const Row16Eval ev = eval_row16_heads(mine, lo, a, 0, action);
+        float d = 0.0f;
+        if (ev.is_logit) d = g_lp * ((ev.chosen ? 1.0f : 0.0f) - ev.p) - g_ent * ev.p * (ev.nl + ev.head_entropy);
+        else if (lo == a) d = g_v;
+        if (ok) dout[row * kOut + lo] = d;
+        cnn_heads_dh<HT>(d, w2v, hs, le, lo, a, ok, row, dh, hrt);
     }
 }
 
@@ -155,39 +265,7 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, int
         if (is_logit) d = g_lp * ((chosen ? 1.0f : 0.0f) - p) + hp.ent_coef * scale * p * (nl + ent);
         else if (lo == a) d = dv;
         if (ok) dout[row * kOut + lo] = d;
-        // d loss / d h[u] = sum_o d_o W2v[o][u]; lane lo owns u = lo, lo + 16, ...
-        // (the hidden vector is relu(Linear(...)): hand back d loss / d (pre-activation), i.e. masked by relu')
-        if (HT) {
-            float dhv[(HT ? HT : 16) / 16];
-#pragma unroll
-            for (int j = 0; j < HT / 16; ++j) dhv[j] = 0.0f;
-            for (int o = 0; o <= a; ++o) {
-                const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
-#pragma unroll
-                for (int j = 0; j < HT / 16; ++j) dhv[j] = fmaf(d_o, w2v[o * (HT + 1) + lo + 16 * j], dhv[j]);
-            }
-            if (ok) {
-#pragma unroll
-                for (int j = 0; j < HT / 16; ++j) dh[row * HT + lo + 16 * j] = hs[le * HT + lo + 16 * j] > 0.0f ? dhv[j] : 0.0f;
-            }
-        } else {   // any width: the same fma chains over o, eight columns of the lane at a time
-            for (int j0 = 0; j0 < H / 16; j0 += 8) {
-                float dhv[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) dhv[j] = 0.0f;
-                for (int o = 0; o <= a; ++o) {
-                    const float d_o = __shfl(d, (lane_id() & 48) | o, 64);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (j0 + j < H / 16) dhv[j] = fmaf(d_o, w2v[o * (H + 1) + lo + 16 * (j0 + j)], dhv[j]);
-                }
-                if (ok) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (j0 + j < H / 16) dh[row * H + lo + 16 * (j0 + j)] = hs[le * H + lo + 16 * (j0 + j)] > 0.0f ? dhv[j] : 0.0f;
-                }
-            }
-        }
+        cnn_heads_dh<HT>(d, w2v, hs, le, lo, a, ok, row, dh, hrt);
         if (lo == 0) {
             acc[0] += (double)(fmaxf(pg1, pg2) * w);
             acc[1] += (double)(v_loss * w);
@@ -262,6 +340,34 @@ static int cnn_launch_sample(int H, unsigned grid, hipStream_t stream, const flo
     return 0;
 }
 template <int HT>
+static int cnn_launch_eval(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const CnnHeads &hd, const long long *actions,
+                           float *logprob, float *entropy, float *value) {
+    static int lds_set = 0;
+    const int lds = (int)cnn_heads_lds(H);
+    if (lds > lds_set) {
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_eval_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        lds_set = lds;
+    }
+    hipLaunchKernelGGL(cnn_heads_eval_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, hd, actions, logprob, entropy, value);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+template <int HT>
+static int cnn_launch_eval_backward(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const CnnHeads &hd,
+                                    const long long *actions, const float *g_logprob, const float *g_entropy, const float *g_value, float *dout,
+                                    float *dh) {
+    static int lds_set = 0;
+    const int lds = (int)cnn_heads_lds(H);
+    if (lds > lds_set) {
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_eval_backward_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        lds_set = lds;
+    }
+    hipLaunchKernelGGL(cnn_heads_eval_backward_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, hd, actions, g_logprob, g_entropy,
+                       g_value, dout, dh);
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+template <int HT>
 static int cnn_launch_loss(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const RowMap &map, long long q0,
                            const pfa_experience &ex, const CnnHeads &hd, const pfa_ppo_hparams &hp, const double *adv_stats, double global_rows,
                            float *dout, float *dh, double *partial) {
@@ -299,6 +405,45 @@ extern "C" int pfa_cnn_heads_sample(const float *h, int32_t hidden, int64_t rows
     if (hidden == 128) return PFA_CNN_SAMPLE(128);
     return PFA_CNN_SAMPLE(0);
 #undef PFA_CNN_SAMPLE
+}
+
+extern "C" int pfa_cnn_heads_eval(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
+                                  const float *value_b, int32_t num_actions, const int64_t *actions, float *logprob, float *entropy, float *value,
+                                  pfa_stream_t stream) {
+    PFA_REQUIRE(rows >= 0 && h && actor_w && actor_b && value_w && value_b && actions && logprob && value, "cnn.heads_eval: null buffer");
+    PFA_REQUIRE(hidden >= 16 && hidden % 16 == 0 && hidden <= kCnnMaxH, "cnn.heads_eval: hidden must be a multiple of 16 in 16..1024 (got %d)", hidden);
+    PFA_REQUIRE(num_actions >= 1 && num_actions <= 15, "cnn.heads_eval: num_actions must be in 1..15");
+    if (rows == 0) return 0;
+    const long long tiles = (rows + 15) / 16;
+    const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
+    CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
+    ScopedKernelTimer timer("cnn_heads_eval", (hipStream_t)stream);
+#define PFA_CNN_EVAL(HT) \
+    cnn_launch_eval<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, (const long long *)actions, logprob, entropy, value)
+    if (hidden == 512) return PFA_CNN_EVAL(512);
+    if (hidden == 128) return PFA_CNN_EVAL(128);
+    return PFA_CNN_EVAL(0);
+#undef PFA_CNN_EVAL
+}
+
+extern "C" int pfa_cnn_heads_eval_backward(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b,
+                                           const float *value_w, const float *value_b, int32_t num_actions, const int64_t *actions,
+                                           const float *g_logprob, const float *g_entropy, const float *g_value, float *dout, float *dh,
+                                           pfa_stream_t stream) {
+    PFA_REQUIRE(rows >= 0 && h && actor_w && actor_b && value_w && value_b && actions && dout && dh, "cnn.heads_eval_backward: null buffer");
+    PFA_REQUIRE(hidden >= 16 && hidden % 16 == 0 && hidden <= kCnnMaxH, "cnn.heads_eval_backward: hidden must be a multiple of 16 in 16..1024 (got %d)", hidden);
+    PFA_REQUIRE(num_actions >= 1 && num_actions <= 15, "cnn.heads_eval_backward: num_actions must be in 1..15");
+    if (rows == 0) return 0;
+    const long long tiles = (rows + 15) / 16;
+    const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
+    CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
+    ScopedKernelTimer timer("cnn_heads_eval_backward", (hipStream_t)stream);
+#define PFA_CNN_EVAL_BWD(HT) \
+    cnn_launch_eval_backward<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, (const long long *)actions, g_logprob, g_entropy, g_value, dout, dh)
+    if (hidden == 512) return PFA_CNN_EVAL_BWD(512);
+    if (hidden == 128) return PFA_CNN_EVAL_BWD(128);
+    return PFA_CNN_EVAL_BWD(0);
+#undef PFA_CNN_EVAL_BWD
 }
 
 extern "C" size_t pfa_cnn_heads_loss_workspace_bytes(void) { return (size_t)1024 * 8 * sizeof(double); }
