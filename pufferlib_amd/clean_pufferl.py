@@ -41,7 +41,7 @@ import torch
 
 from . import _lib, readback, utils
 from . import dist as pdist
-from .cleanrl import Policy, RecurrentPolicy
+from .cleanrl import Policy, RecurrentPolicy, _weights_changed, reads_frames, route
 from .models import FlatParams  # noqa: F401  (re-exported: callers of create() type-check the trainer's parameter buffer against it)
 from .namespace import namespace
 from .vector import Frames, Spaces, Squared, Stochastic, _DeviceVecEnv
@@ -303,28 +303,23 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
         else:
             policy = Policy(policy, seed=config.seed)     # e.g. the reference's cleanrl.Policy(models.Default)
     recurrent = isinstance(policy, RecurrentPolicy)
-    from .models import conv_geometry_of, find_cnn, find_resnet, set_conv_obs_shape, set_resnet_obs_shape
-    resnet = find_resnet(policy) is not None
-    conv = find_cnn(policy) is not None or resnet       # either one reads uint8 frames and drives the cnn_engine slot
-    if resnet:
+    from .models import conv_geometry_of, set_conv_obs_shape, set_resnet_obs_shape
+    kind = route(policy.policy, recurrent)              # (refuses LSTMWrapper over models.ProcgenResnet and its action sets beyond 15)
+    conv = reads_frames(policy.policy, recurrent)       # a conv encoder on any route: experience rows are uint8 frames
+    if conv:
         space = vecenv.single_observation_space
-        if recurrent:
-            raise NotImplementedError('LSTMWrapper over models.ProcgenResnet (procgen\'s Recurrent) is not built: use the feed-forward Policy')
+        name, layout = ('models.ProcgenResnet', ' (H, W, C)') if kind == 'resnet' else ('models.Convolutional', '')
         if not (host_mode or isinstance(vecenv, Frames)):
-            raise NotImplementedError('models.ProcgenResnet reads uint8 frames: a host vecenv or vector.Frames')
+            raise NotImplementedError(f'{name} reads uint8 frames: a host vecenv or vector.Frames')
         if np.dtype(space.dtype) != np.uint8 or len(space.shape) != 3:
-            raise NotImplementedError(f'models.ProcgenResnet reads 3-D uint8 frames (H, W, C), the env shows {space.dtype} {space.shape}')
-        set_resnet_obs_shape(policy, space.shape)      # the frame shape is not in the weights: ResnetParams checks it against them
-    elif conv:
-        space = vecenv.single_observation_space
-        if not (host_mode or isinstance(vecenv, Frames)):
-            raise NotImplementedError('models.Convolutional reads uint8 frames: a host vecenv or vector.Frames')
-        if np.dtype(space.dtype) != np.uint8 or len(space.shape) != 3:
-            raise NotImplementedError(f'models.Convolutional reads 3-D uint8 frames, the env shows {space.dtype} {space.shape}')
-        # the frame shape is not in the weights: hand the env's to the policy (a module built elsewhere has none recorded), then check
-        # that channel count and flat_size agree with it (ValueError with both numbers otherwise)
-        set_conv_obs_shape(policy, space.shape)
-        conv_geometry_of(policy)
+            raise NotImplementedError(f'{name} reads 3-D uint8 frames{layout}, the env shows {space.dtype} {space.shape}')
+        # the frame shape is not in the weights: hand the env's to the policy (a module built elsewhere has none recorded); the
+        # parameter buffer checks that channel count and flat_size agree with it (ValueError with both numbers otherwise)
+        if kind == 'resnet':
+            set_resnet_obs_shape(policy, space.shape)
+        else:
+            set_conv_obs_shape(policy, space.shape)
+            conv_geometry_of(policy)
     if isinstance(vecenv, Frames) and not conv:
         raise NotImplementedError('vector.Frames shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
     if recurrent and isinstance(vecenv, Stochastic):
@@ -368,8 +363,8 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
                             obs_stride, total_agents, device, obs_bytes=fp.obs_dim if conv else None)
     optimizer = HipAdam(fp, lr=config.learning_rate, eps=1e-5)
     lstm_engine = cnn_engine = gen_engine = None
-    from . import general
-    if isinstance(fp, general.GeneralParams):
+    if kind == 'general':
+        from . import general
         # a policy shape outside the fused kernels (wide Default, wide / conv LSTM): GEMM-path engine for rollout steps and updates
         gen_engine = general.Engine(fp, experience, total_agents)
         policy.gen_engine = gen_engine
@@ -379,8 +374,8 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
     elif conv:
         cnn_engine = policy.cnn_engine
         cnn_engine.experience = experience
-        cnn_engine._alloc(min(4096 if resnet else 8192, max(experience.minibatch_size, total_agents)))
-    if recurrent and gen_engine is None:
+        cnn_engine._alloc(min(cnn_engine.CHUNK_CAP, max(experience.minibatch_size, total_agents)))
+    if kind == 'lstm':
         from . import lstm as plstm
         lstm_engine = plstm.Engine(fp, experience, vecenv)
         experience.lstm_h, experience.lstm_c = lstm_engine.lstm_h, lstm_engine.lstm_c   # clean_pufferl.py:407-412
@@ -400,7 +395,7 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
         msg=msg, last_log_time=0, utilization=utilization,
         # engine state
         flat_params=fp, rank=rank, world_size=world, native_dp=native_dp, lstm_engine=lstm_engine, cnn_engine=cnn_engine, gen_engine=gen_engine,
-        env_offset=env_offset, host_bridge=host_bridge,
+        env_offset=env_offset, host_bridge=host_bridge, frame_rows=conv,   # (frame rows: uint8 observations, moved as bytes)
         workspace=torch.zeros(ws_bytes, dtype=torch.uint8, device=device),
         grads=torch.zeros(fp.count + 16, dtype=torch.float32, device=device),   # gradient + 8 loss sums as (hi, lo) float pairs
         # [adv_stats (nmb x 2) | the four explained-variance sums]: one allocation, so that data parallel they are ONE all-reduce
@@ -539,9 +534,35 @@ def _noise_buffer(data, T, N, A, device, other_than=None):
     return bufs[1] if (other_than is not None and other_than.data_ptr() == bufs[0].data_ptr()) else bufs[0]
 
 
-def _frames_policy(data):
-    """True when observations are uint8 frames (models.Convolutional, with or without an LSTM on top): rows are moved as bytes."""
-    return data.cnn_engine is not None or (data.gen_engine is not None and data.gen_engine.net.kind == 'cnn')
+def policy_step_fn(data):
+    """The rollout-mode policy call of the two loops that step a vecenv from the host (_rollout_stepwise, hostpath.evaluate), resolved
+    once per rollout from the engines create() built: step(obs, n, noise, key, row_offset, actions, logprob, entropy, value[, ids]),
+    the signature of general.Engine.policy_step.  `ids` (int64, device): the agents the n rows belong to where the policy keeps a
+    state row per agent and the rows are not agents 0 .. n-1 (a host vecenv's batches).  The fused recurrent kernels' gate matrix is
+    re-tiled here: once per rollout."""
+    gen, conv, eng, fp = data.gen_engine, data.cnn_engine, data.lstm_engine, data.flat_params
+    if gen is not None or conv is not None:
+        return (gen if gen is not None else conv).policy_step
+    L, stream = _lib.lib(), _lib.stream_handle()
+    if eng is None:
+        def step(obs, n, noise, key, row_offset, actions, logprob, entropy, value):
+            _lib.check(L.pfa_mlp_forward_sample(_lib.ptr(obs), n, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(noise), C.byref(key), row_offset,
+                                                _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(entropy), _lib.ptr(value), stream), 'forward_sample')
+        return step
+    from . import lstm as plstm
+    plstm.pack_gates(fp, eng.wpack)
+
+    def step(obs, n, noise, key, row_offset, actions, logprob, entropy, value, ids=None):
+        h, c = eng.lstm_h, eng.lstm_c
+        if ids is not None:                   # state rows of these agents (clean_pufferl.py:100-105)
+            h, c = h[0].index_select(0, ids), c[0].index_select(0, ids)
+        _lib.check(L.pfa_lstm_policy_step(_lib.ptr(obs), n, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(eng.wpack), _lib.ptr(h), _lib.ptr(c),
+                                          _lib.ptr(noise), C.byref(key), row_offset, _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(entropy),
+                                          _lib.ptr(value), stream), 'lstm_policy_step')
+        if ids is not None:
+            eng.lstm_h[0].index_copy_(0, ids, h)
+            eng.lstm_c[0].index_copy_(0, ids, c)
+    return step
 
 
 def _rollout_stepwise(data, noise, T, N):
@@ -551,10 +572,8 @@ def _rollout_stepwise(data, noise, T, N):
     vecenv, policy, fp, exp = data.vecenv, data.policy, data.flat_params, data.experience
     stream = _lib.stream_handle()
     dev = vecenv.device
-    eng = data.lstm_engine
-    if eng is not None:
-        from . import lstm as plstm
-        plstm.pack_gates(fp, eng.wpack)
+    step = policy_step_fn(data)
+    row_words = fp.obs_dim // 4 if data.frame_rows else fp.obs_stride      # (frame rows are bytes: the copy moves them as four-byte words)
     actions = torch.empty(N, dtype=torch.int64, device=dev)
     logprob = torch.empty(N, device=dev)
     value = torch.empty(N, device=dev)
@@ -568,21 +587,8 @@ def _rollout_stepwise(data, noise, T, N):
             vecenv.ensure_tape(min(tape_chunk, T - t))
         key = _lib.NoiseKey(policy.noise_seed, policy.noise_step + t)
         nz = None if noise is None else noise[t]
-        if data.gen_engine is not None:
-            data.gen_engine.policy_step(vecenv.obs_buf, N, nz, key, vecenv.env_offset, actions, logprob, None, value)
-        elif data.cnn_engine is not None:
-            data.cnn_engine.policy_step(vecenv.obs_buf, N, nz, key, vecenv.env_offset, actions, logprob, None, value)
-        elif eng is None:
-            _lib.check(L.pfa_mlp_forward_sample(_lib.ptr(vecenv.obs_buf), N, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(nz),
-                                                C.byref(key), vecenv.env_offset, _lib.ptr(actions), _lib.ptr(logprob), None,
-                                                _lib.ptr(value), stream), 'forward_sample')
-        else:
-            _lib.check(L.pfa_lstm_policy_step(_lib.ptr(vecenv.obs_buf), N, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(eng.wpack),
-                                              _lib.ptr(eng.lstm_h), _lib.ptr(eng.lstm_c), _lib.ptr(nz), C.byref(key),
-                                              vecenv.env_offset, _lib.ptr(actions), _lib.ptr(logprob), None, _lib.ptr(value),
-                                              stream), 'lstm_policy_step')
-        # (frame rows are bytes: the copy moves them as obs_dim / 4 four-byte words)
-        _lib.check(L.pfa_store_step(C.byref(exp.c), t, N, fp.obs_dim // 4 if _frames_policy(data) else fp.obs_stride, _lib.ptr(vecenv.obs_buf), _lib.ptr(vecenv.rewards),
+        step(vecenv.obs_buf, N, nz, key, vecenv.env_offset, actions, logprob, None, value)
+        _lib.check(L.pfa_store_step(C.byref(exp.c), t, N, row_words, _lib.ptr(vecenv.obs_buf), _lib.ptr(vecenv.rewards),
                                     _lib.ptr(vecenv.terminals_u8), _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(value), stream),
                    'store_step')
         vecenv.device_send(actions)
@@ -987,10 +993,7 @@ def try_load_checkpoint(data):
     with torch.no_grad():      # copy INTO the views of the flat device buffer the kernels read
         for k, v in data.uncompiled_policy.state_dict().items():
             v.copy_(sd[k])
-    if data.cnn_engine is not None:
-        data.cnn_engine.version += 1          # the packed weight forms are stale
-    if data.gen_engine is not None:
-        data.gen_engine.net.version += 1
+    _weights_changed(data.policy)             # the engines' packed weight forms are stale
     data.optimizer.load_state_dict(resume['optimizer_state_dict'])
     data.global_step = resume['global_step']
     data.epoch = resume['update']

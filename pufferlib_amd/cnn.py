@@ -121,8 +121,9 @@ class Engine:
     activation memory: ~170 KB per frame with the gradients at the Atari shape); clamped to what the geometry allows under
     32-bit element offsets (5325 frames of 280 x 480 x 3 bytes) and a quarter of the device memory for the activations
     (ConvGeometry.chunk_for)."""
+    CHUNK_CAP = 8192          # frames per kernel batch a caller asks for at the most (the constructor's default)
 
-    def __init__(self, cp, experience=None, chunk=8192):
+    def __init__(self, cp, experience=None, chunk=None):
         self.cp, self.dev = cp, cp.flat.device
         self.fp = cp
         self.experience = experience      # the trainer's buffers (uint8 obs [B][frame_bytes]) for update()
@@ -143,8 +144,9 @@ class Engine:
         self.chunk = 0
         self.packed_version = -1
         self.version = 0          # bumped by whoever changes the weights (optimizer step, checkpoint load)
+        self.watch = ()           # nn.Parameters whose own version counters join the pack key (general.Net.pack: a torch optimizer steps them)
         self.generation = 0       # bumped by every forward(): whose activations a1/a2/a3/h hold (eval_backward re-runs a forward not its own)
-        self._alloc(chunk)
+        self._alloc(chunk or self.CHUNK_CAP)
 
     def _build_layers(self, geo):
         """The layer objects over the parameter views: sets self.fc (the Linear behind Flatten) and self.layers (what pack() and the
@@ -188,10 +190,11 @@ class Engine:
         self.d3 = torch.empty_like(self.a3)
 
     def pack(self):
-        if self.packed_version != self.version:
+        key = (self.version,) + tuple(p._version for p in self.watch)
+        if self.packed_version != key:
             for layer in self.layers:
                 layer.pack()
-            self.packed_version = self.version
+            self.packed_version = key
 
     # ------------------------------------------------------------------------------------------------------------ forward
     def forward(self, frames, n):

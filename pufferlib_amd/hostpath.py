@@ -111,10 +111,10 @@ def _arrival_buffers(data, experience, bridge):
 
 def evaluate(data):
     """clean_pufferl.evaluate (clean_pufferl.py:76-154) for a host vecenv."""
+    from .clean_pufferl import policy_step_fn
     config, profile, experience, vecenv, policy = data.config, data.profile, data.experience, data.vecenv, data.policy
     L = _lib.lib()
     fp, bridge = data.flat_params, data.host_bridge
-    A = fp.num_actions
     stream = _lib.stream_handle()
     infos = defaultdict(list)
     if getattr(data, 'lstm_engine', None) is not None:
@@ -132,7 +132,13 @@ def evaluate(data):
     if exact:
         arrival = _arrival_buffers(data, experience, bridge)
         arr_ptr = 0
-    eng = data.lstm_engine
+    step = policy_step_fn(data)
+    stateful = experience.lstm_h is not None        # a recurrent policy on either route: one state row per agent
+    # (frame rows are bytes: pfa_store_rows moves them as obs_dim / 16 float4s with a stride of obs_dim / 4 floats, which wants
+    # whole 16-byte units; every other frame size is copied byte by byte)
+    odd_bytes = data.frame_rows and fp.obs_dim % 16 != 0
+    store = L.pfa_store_rows_bytes if odd_bytes else L.pfa_store_rows
+    row_units = fp.obs_dim if odd_bytes else fp.obs_dim // 4 if data.frame_rows else fp.obs_stride
     # `while not experience.full` (clean_pufferl.py:84).  "Full" = every agent has its batch_size / num_agents rows: a genuinely
     # async pool (fast workers return more often, vector.py:382-390) keeps being stepped until the slow agents have caught up;
     # surplus rows of an agent that is already complete are acted on but not stored (counted in stored_dropped[1]).
@@ -154,30 +160,11 @@ def evaluate(data):
             actions = torch.empty(n, dtype=torch.int64, device=bridge.obs.device)
             logprob = torch.empty(n, device=bridge.obs.device)
             value = torch.empty(n, device=bridge.obs.device)
-            if data.gen_engine is not None:                          # a policy shape outside the fused kernels (general.py)
-                ids = None
-                if data.gen_engine.lstm_h is not None:               # state rows of these agents (clean_pufferl.py:100-105)
-                    bridge.ids64[:n].copy_(bridge.ids[:n])
-                    ids = bridge.ids64[:n]
-                data.gen_engine.policy_step(bridge.obs, n, noise, key, row0, actions, logprob, None, value, ids=ids)
-            elif data.cnn_engine is not None:                        # models.Convolutional on the staged uint8 frames
-                data.cnn_engine.policy_step(bridge.obs, n, noise, key, row0, actions, logprob, None, value)
-            elif eng is None:
-                _lib.check(L.pfa_mlp_forward_sample(_lib.ptr(bridge.obs), n, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(noise),
-                                                    C.byref(key), row0, _lib.ptr(actions), _lib.ptr(logprob), None, _lib.ptr(value),
-                                                    stream), 'forward_sample')
-            else:                                                    # state rows of these agents (clean_pufferl.py:100-105)
-                from . import lstm as plstm
+            if stateful:                                             # state rows of these agents (clean_pufferl.py:100-105)
                 bridge.ids64[:n].copy_(bridge.ids[:n])
-                idx = bridge.ids64[:n]
-                h, c = eng.lstm_h[0].index_select(0, idx), eng.lstm_c[0].index_select(0, idx)
-                if recvs == 0:
-                    plstm.pack_gates(fp, eng.wpack)
-                _lib.check(L.pfa_lstm_policy_step(_lib.ptr(bridge.obs), n, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(eng.wpack),
-                                                  _lib.ptr(h), _lib.ptr(c), _lib.ptr(noise), C.byref(key), row0, _lib.ptr(actions),
-                                                  _lib.ptr(logprob), None, _lib.ptr(value), stream), 'lstm_policy_step')
-                eng.lstm_h[0].index_copy_(0, idx, h)
-                eng.lstm_c[0].index_copy_(0, idx, c)
+                step(bridge.obs, n, noise, key, row0, actions, logprob, None, value, bridge.ids64[:n])
+            else:
+                step(bridge.obs, n, noise, key, row0, actions, logprob, None, value)
             policy.noise_step += 1
         if exact:
             with profile.eval_misc:
@@ -208,13 +195,7 @@ def evaluate(data):
                 vecenv.send(actions_np)
             continue
         with profile.eval_misc:
-            # (frame rows are bytes: pfa_store_rows moves them as obs_dim / 16 float4s with a stride of obs_dim / 4 floats, which wants
-            # whole 16-byte units; every other frame size is copied byte by byte)
-            frame_rows = data.cnn_engine is not None or (data.gen_engine is not None and data.gen_engine.net.kind == 'cnn')
-            odd_bytes = frame_rows and fp.obs_dim % 16 != 0
-            store = L.pfa_store_rows_bytes if odd_bytes else L.pfa_store_rows
-            _lib.check(store(C.byref(experience.c), n, bridge.total_agents,
-                             fp.obs_dim if odd_bytes else fp.obs_dim // 4 if frame_rows else fp.obs_stride, _lib.ptr(bridge.obs),
+            _lib.check(store(C.byref(experience.c), n, bridge.total_agents, row_units, _lib.ptr(bridge.obs),
                                         _lib.ptr(bridge.rew), _lib.ptr(bridge.done), _lib.ptr(actions), _lib.ptr(logprob),
                                         _lib.ptr(value), _lib.ptr(bridge.ids), _lib.ptr(bridge.mask), _lib.ptr(bridge.counters),
                                         _lib.ptr(bridge.stored_dropped), stream), 'store_rows')

@@ -29,19 +29,17 @@ def pack_gates(fp, out=None):
     return out
 
 
-def policy_step(fp, obs, h, c, noise, key, row_offset, wpack=None):
+def policy_step(fp, obs, h, c, noise, key, row_offset, wpack=None, out=None):
     """One rollout step on ``rows`` observation rows [rows][obs_stride]; h, c [rows][128] are updated in place.
-    Returns (actions int64, logprob, entropy, value[:, None])."""
+    Returns (actions int64, logprob, entropy, value[:, None]), written into the four tensors `out` where the caller brings them."""
     L = _lib.lib()
     stream = _lib.stream_handle()
     rows = obs.shape[0]
     dev = obs.device
     if wpack is None:
         wpack = pack_gates(fp)
-    actions = torch.empty(rows, dtype=torch.int64, device=dev)
-    logprob = torch.empty(rows, device=dev)
-    entropy = torch.empty(rows, device=dev)
-    value = torch.empty(rows, device=dev)
+    actions, logprob, entropy, value = out or (torch.empty(rows, dtype=torch.int64, device=dev), torch.empty(rows, device=dev),
+                                               torch.empty(rows, device=dev), torch.empty(rows, device=dev))
     _lib.check(L.pfa_lstm_policy_step(_lib.ptr(obs), rows, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(wpack), _lib.ptr(h),
                                       _lib.ptr(c), _lib.ptr(noise), C.byref(key), row_offset, _lib.ptr(actions),
                                       _lib.ptr(logprob), _lib.ptr(entropy), _lib.ptr(value), stream), 'lstm_policy_step')

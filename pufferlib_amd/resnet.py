@@ -130,9 +130,7 @@ class Sequence:
 class Engine(cnn.Engine):
     """Forward / update of the ResNet policy over a models.ResnetParams buffer.  `chunk` = frames per kernel batch (about 1.5 MB of
     maps per frame at Procgen's shape), clamped to what 32-bit element offsets and a quarter of the device memory allow."""
-
-    def __init__(self, rp, experience=None, chunk=4096):
-        super().__init__(rp, experience, chunk)
+    CHUNK_CAP = 4096
 
     def _build_layers(self, geo):
         v, dev = self.cp.views, self.dev

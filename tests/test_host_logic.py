@@ -70,6 +70,83 @@ def test_which_policy_shapes_take_the_gemm_path():
     with pytest.raises(ValueError):
         models.Default(env(49, d8), hidden_size=100)
 
+    # cleanrl.route, the one decision the lines above are answers of, on the routing table of cleanrl's module docstring: route,
+    # needs_general and whether autograd=True is admitted at construction
+    def lstm(e, hidden=128):
+        return models.LSTMWrapper(e, models.Default(e, hidden_size=hidden), input_size=hidden, hidden_size=hidden)
+
+    def frames_env(actions, shape=(4, 84, 84)):
+        return namespace(single_observation_space=spaces.Box(low=0, high=255, shape=shape, dtype=np.uint8), single_action_space=spaces.Discrete(actions))
+    table = [
+        (lambda: models.Default(env(49, d8)), False, 'mlp', True),
+        (lambda: models.Default(env(49, spaces.MultiDiscrete([3, 4]))), False, 'mlp', True),
+        (lambda: models.Default(env(49, d8), hidden_size=64), False, 'general', True),
+        (lambda: models.Default(env(49, d8), hidden_size=256), False, 'general', True),
+        (lambda: models.Default(env(300, d8)), False, 'general', True),
+        (lambda: models.Default(env(49, spaces.Discrete(40))), False, 'general', True),
+        (lambda: lstm(env(49, d8)), True, 'lstm', True),
+        (lambda: lstm(env(160, d8)), True, 'lstm', True),
+        (lambda: lstm(env(161, d8)), True, 'general', True),
+        (lambda: lstm(env(49, d8), 256), True, 'general', True),
+        (lambda: models.Convolutional(frames_env(4)), False, 'cnn', True),
+        (lambda: models.Convolutional(frames_env(18)), False, 'general', False),
+        (lambda: models.LSTMWrapper(frames_env(4), models.Convolutional(frames_env(4)), input_size=512, hidden_size=512), True, 'general', False),
+        (lambda: models.ProcgenResnet(frames_env(15, (9, 7, 3))), False, 'resnet', False),
+    ]
+    for make, recurrent, want, admitted in table:
+        module, wrapper = make(), cleanrl.RecurrentPolicy if recurrent else cleanrl.Policy
+        assert cleanrl.route(module, recurrent) == want
+        assert cleanrl.needs_general(module, recurrent) is (want == 'general')
+        assert wrapper(module).autograd is False
+        if admitted:
+            assert wrapper(module, autograd=True).autograd is True
+        else:
+            with pytest.raises(NotImplementedError, match='autograd=True with a convolutional encoder'):
+                wrapper(module, autograd=True)
+
+
+def test_a_sampling_call_moves_the_noise_stream_by_one_exactly_when_it_draws_its_own_noise():
+    """cleanrl's shared sampling-call helper on CPU tensors: four outputs of `rows` entries, the Philox key of the stream position the
+    call was made at, the explicit noise as contiguous float32; noise_step advances by exactly one iff no noise is given, and noise of
+    another shape than (rows, logits) is refused before anything moves."""
+    from pufferlib_amd import cleanrl, models, namespace, spaces
+    e = namespace(single_observation_space=spaces.Box(low=-1, high=1, shape=(16,), dtype=np.float32), single_action_space=spaces.Discrete(4))
+    for pol in (cleanrl.Policy(models.Default(e), seed=7), cleanrl.RecurrentPolicy(models.LSTMWrapper(e, models.Default(e)), seed=7)):
+        actions, logprob, entropy, value, key, noise = pol._sampling_call(5, 'cpu', 4, None)
+        assert noise is None and pol.noise_step == 1 and (key.seed, key.step) == (7, 0)
+        assert actions.shape == (5,) and actions.dtype == torch.int64
+        assert all(t.shape == (5,) and t.dtype == torch.float32 for t in (logprob, entropy, value))
+        given = torch.rand(4, 5, dtype=torch.float64).t()                   # (5, 4), neither float32 nor contiguous
+        *_, key, noise = pol._sampling_call(5, 'cpu', 4, given)
+        assert pol.noise_step == 1 and (key.seed, key.step) == (7, 1)
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and torch.equal(noise, given.float())
+        for bad in (torch.rand(5, 3), torch.rand(4, 4), torch.rand(20)):
+            with pytest.raises(AssertionError):
+                pol._sampling_call(5, 'cpu', 4, bad)
+        assert pol.noise_step == 1
+        *_, key, noise = pol._sampling_call(5, 'cpu', 4, None)
+        assert pol.noise_step == 2 and (key.seed, key.step) == (7, 1)
+
+
+def test_a_policy_pickle_stores_what_it_stored_before_the_wrappers_shared_a_base():
+    """torch.save of the whole module is the checkpoint format: the stored __dict__ keys of Policy / RecurrentPolicy are torch.nn.Module's
+    own plus these four, no engine or parameter-buffer bookkeeping, and the load_state_dict post hook is stored by the name
+    cleanrl._weights_changed (older checkpoints name it)."""
+    import pickle
+    from pufferlib_amd import cleanrl, models, namespace, spaces
+    e = namespace(single_observation_space=spaces.Box(low=-1, high=1, shape=(16,), dtype=np.float32), single_action_space=spaces.Discrete(4))
+    for pol in (cleanrl.Policy(models.Default(e), seed=3), cleanrl.RecurrentPolicy(models.LSTMWrapper(e, models.Default(e)), seed=3, autograd=True)):
+        pol.noise_step = 7
+        pol.cnn_engine = pol.gen_engine = pol._evaluator = object()      # (what adopt() / create() hang on the wrapper)
+        state = pol.__getstate__()
+        assert set(state) - set(torch.nn.Module().__dict__) == {'autograd', 'noise_seed', 'noise_step', '_flat'} and state['_flat'] is None
+        assert list(state['_load_state_dict_post_hooks'].values()) == [cleanrl._weights_changed]
+        assert cleanrl._weights_changed.__qualname__ == '_weights_changed'
+        del pol.cnn_engine, pol.gen_engine, pol._evaluator
+        back = pickle.loads(pickle.dumps(pol))
+        assert type(back) is type(pol) and (back.noise_seed, back.noise_step, back.autograd) == (3, 7, pol.autograd)
+        assert all(torch.equal(v, back.state_dict()[k]) for k, v in pol.state_dict().items())
+
 
 def test_experience_shape_checks_raise_before_touching_the_gpu():
     from pufferlib_amd.clean_pufferl import Experience
