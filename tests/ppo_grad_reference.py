@@ -76,20 +76,29 @@ class Case:
         self.acts = np.stack([rs.randint(0, n, B) for n in self.sizes], axis=1).astype(np.int64)
         self.advantages = rs.standard_normal(B).astype(f32)
         noise_lp, noise_v = 0.2 * rs.standard_normal(B), 0.2 * rs.standard_normal(B)
-        idx = self.rows_index()
-        with torch.no_grad():                   # old log-probabilities and values: the f64 policy's own + noise, so ratios leave 1
+        self.more_params(rs)                    # (drawn last: the cases without any keep their numbers)
+        lp, val = self.old_policy()             # old log-probabilities and values: the f64 policy's own + noise, so ratios leave 1
+        self.logprobs = (lp + noise_lp).astype(f32)
+        self.values = (val + noise_v).astype(f32)
+        self.returns = (self.values + self.advantages).astype(f32)      # clean_pufferl.py:199
+
+    def more_params(self, rs):
+        """Parameters behind the six of NAMES (a subclass's: tests/lstm_grad_reference.py)."""
+
+    def old_policy(self):
+        """([B] log-probability of the stored actions, [B] value) of the float64 policy on every experience row."""
+        B, idx = self.B, self.rows_index()
+        with torch.no_grad():
             p = {k: torch.as_tensor(v).double() for k, v in self.params.items()}
             acts = torch.as_tensor(self.acts)
-            if heads_only:
+            if self.heads_only:
                 lp, val = np.zeros(B), np.zeros(B)
                 _, _, l, _, v = _policy_rows(p, None, acts[idx], self.sizes, hidden=torch.as_tensor(self.h).double())
                 lp[idx], val[idx] = l.numpy(), v.numpy()
             else:
                 _, _, l, _, v = _policy_rows(p, torch.as_tensor(self.obs).double(), acts, self.sizes)
                 lp, val = l.numpy(), v.numpy()
-        self.logprobs = (lp + noise_lp).astype(f32)
-        self.values = (val + noise_v).astype(f32)
-        self.returns = (self.values + self.advantages).astype(f32)      # clean_pufferl.py:199
+        return lp, val
 
     def rows_index(self, mb=None):
         """Flat experience row of every minibatch row, in the order the kernel walks them: minibatch m = segments {m + k nmb} of
@@ -206,17 +215,20 @@ class Reference:
         for name, (gap, err) in self.margins.items():
             assert gap > MARGIN * err, f'{self.case.tag}: {name}: smallest distance {gap:.3e} vs {MARGIN:g} x {err:.3e}: choose another seed'
 
+    def want(self, name):
+        """The float64 expectation of a compared tensor."""
+        return self.dh if name == 'dh' else self.grads[name]
+
     def bound(self, name):
         """max(4 e32, 1e-5 max|f64|): four fp32 chain errors, or the project's 1e-5 contract relative to the tensor's largest entry
         (the precedent of test_policy_call_matches_float64_within_four_fp32_chain_errors)."""
-        want = self.dh if name == 'dh' else self.grads[name]
-        return max(4.0 * self.e32[name], 1e-5 * float(np.abs(want).max()))
+        return max(4.0 * self.e32[name], 1e-5 * float(np.abs(self.want(name)).max()))
 
     def compare(self, got, names=NAMES):
         """name -> (max |got - f64|, e32, bound) for every tensor of `got` (W1 without its padding columns, or 'dh')."""
         out = {}
         for k in names:
-            want = self.dh if k == 'dh' else self.grads[k]
+            want = self.want(k)
             g = np.asarray(got[k], np.float64).reshape(want.shape)
             err = float(np.abs(g - want).max()) if np.isfinite(g).all() else float('inf')
             out[k] = (err, self.e32[k], self.bound(k))

@@ -233,11 +233,10 @@ def test_lstm_policy_step_matches_torch_modules():
     np.testing.assert_allclose(ent.cpu().numpy(), -(logp * logp.exp()).sum(1).cpu().numpy(), rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize('R,Th', [(40, 5), (64, 16), (7, 3), (8192, 16)])    # last: one full-size minibatch (BASELINE configs[1])
-def test_lstm_seq_forward_backward_match_torch_autograd(R, Th):
-    """pfa_lstm_seq_forward / pfa_lstm_seq_backward vs nn.Linear + nn.LSTM under torch autograd: every kept activation, the
-    state after Th steps, d loss/d gate pre-activations, d loss/d encoder pre-activations and the bias gradients.  Ragged
-    row counts (not a multiple of the 32-row workgroup), nonzero biases, nonzero carried-in state."""
+def _seq_forward_backward(R, Th):
+    """pfa_lstm_seq_forward / pfa_lstm_seq_backward (bias gradients through lstm_bias_final_kernel) on R random segments of Th steps from a
+    nonzero state, and the same steps under torch autograd in f64: a namespace of every device buffer and reference tensor."""
+    from types import SimpleNamespace
     from pufferlib_amd import _lib, lstm as plstm
     L = _lib.lib()
     torch.manual_seed(R * 100 + Th)
@@ -293,6 +292,17 @@ def test_lstm_seq_forward_backward_match_torch_autograd(R, Th):
         acts.append(torch.cat([i, f, g, o], 1)); hs.append(h); cs.append(c); pres.append(p)
     loss = sum((hs[t] * dh[t].double()).sum() for t in range(Th))
     loss.backward()
+    return SimpleNamespace(**locals())
+
+
+@pytest.mark.parametrize('R,Th', [(40, 5), (64, 16), (7, 3), (8192, 16)])    # last: one full-size minibatch (BASELINE configs[1])
+def test_lstm_seq_forward_backward_match_torch_autograd(R, Th):
+    """pfa_lstm_seq_forward / pfa_lstm_seq_backward vs nn.Linear + nn.LSTM under torch autograd: every kept activation, the
+    state after Th steps, d loss/d gate pre-activations, d loss/d encoder pre-activations and the bias gradients.  Ragged
+    row counts (not a multiple of the 32-row workgroup), nonzero biases, nonzero carried-in state."""
+    v = _seq_forward_backward(R, Th)
+    xe, gates, Hs, Cs, dG, dxe, gb, eb, h0, c0 = v.xe, v.gates, v.Hs, v.Cs, v.dG, v.dxe, v.gb, v.eb, v.h0, v.c0
+    x, acts, hs, cs, pres, pre, bih, b1 = v.x, v.acts, v.hs, v.cs, v.pres, v.pre, v.bih, v.b1
     tol = dict(rtol=1e-5, atol=2e-6)
     np.testing.assert_allclose(xe.cpu().numpy(), x.detach().cpu().numpy(), **tol)
     np.testing.assert_allclose(gates.cpu().numpy(), torch.stack(acts).detach().cpu().numpy(), **tol)
@@ -303,6 +313,32 @@ def test_lstm_seq_forward_backward_match_torch_autograd(R, Th):
     np.testing.assert_allclose(dxe.cpu().numpy(), pre.grad.cpu().numpy(), rtol=2e-5, atol=2e-6)
     np.testing.assert_allclose(gb.cpu().numpy(), bih.grad.cpu().numpy(), rtol=2e-5, atol=1e-5)
     np.testing.assert_allclose(eb.cpu().numpy(), b1.grad.cpu().numpy(), rtol=2e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize('R', [7, 40, 96])      # 1, 2 and 3 workgroups
+def test_lstm_seq_backward_bias_sums_through_reduce_multi(R):
+    """The bias path Engine.update takes: pfa_lstm_seq_backward with null bias outputs leaves its per-workgroup column sums
+    [groups][640] in the workspace, and one kind-1 job of pfa_reduce_multi sums them (columns >= 512 to the encoder bias) — against the f64
+    bias gradients of the reference above under the tolerances of the test above, and bit for bit against lstm_bias_final_kernel, whose
+    order of summation colsum_reduce_block (csrc/gemm.hip) repeats."""
+    from pufferlib_amd import _lib
+    L = _lib.lib()
+    v = _seq_forward_backward(R, 3)
+    nan = lambda *s: torch.full(s, float('nan'), device='cuda')     # noqa: E731
+    groups = (R + 31) // 32
+    assert v.ws.numel() == groups * 640 * 4
+    ws, dG, dxe = nan(groups * 640), nan(3, R, 512), nan(3, R, 128)
+    _lib.check(L.pfa_lstm_seq_backward(_lib.ptr(v.gates), _lib.ptr(v.Cs), _lib.ptr(v.xe), _lib.ptr(v.dh), R, 3, _lib.ptr(v.wb), _lib.ptr(dG),
+                                       _lib.ptr(dxe), None, None, _lib.ptr(ws), v.st), 'bwd')
+    gb, eb = nan(512 + 4), nan(128 + 4)
+    jobs = (_lib.ReduceJob * 1)(_lib.ReduceJob(1, groups, 1, 640, ws.data_ptr(), gb.data_ptr(), 0, eb.data_ptr(), 0, 512, 0))
+    _lib.check(L.pfa_reduce_multi(jobs, 1, v.st), 'reduce_multi')
+    torch.cuda.synchronize()
+    assert torch.equal(dG, v.dG) and torch.equal(dxe, v.dxe) and torch.equal(ws, v.ws.view(torch.float32))
+    np.testing.assert_allclose(gb[:512].cpu().numpy(), v.bih.grad.cpu().numpy(), rtol=2e-5, atol=1e-5)
+    np.testing.assert_allclose(eb[:128].cpu().numpy(), v.b1.grad.cpu().numpy(), rtol=2e-5, atol=1e-5)
+    assert torch.equal(gb[:512], v.gb) and torch.equal(eb[:128], v.eb)
+    assert torch.isnan(gb[512:]).all() and torch.isnan(eb[128:]).all()
 
 
 @pytest.mark.parametrize('d,nt', [(1, 1), (2, 2), (4, 3)])
