@@ -155,6 +155,26 @@ int pfa_squared_debug_targets(void *state, const pfa_squared_config *cfg, int32_
 int pfa_squared_debug_stream_pos(void *state, const pfa_squared_config *cfg, uint64_t *pos_device, pfa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PixelSquared vecenv — the Squared state machine above (same definitions, state layout, tape, statistics: pfa_squared_fill_tape /
+ * _episode_stats / _last_infos / _debug_targets serve it unchanged on the same `state`), shown as uint8 frames instead of the float
+ * grid.  The grid lives in the device state, behind the Squared block: N rows of cfg->obs_stride = round_up(g*g, 16) floats
+ * (g = 2d + 1).  Byte (c, y, x) of a frame sits at c*sc + y*sy + x*sx and shows grid cell (y*g / height, x*g / width):
+ * 0 -> 0, +1 (target marker) -> 255 in even channels / 128 in odd ones, -1 (agent) -> 128 / 255.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t height, width;  /* g <= height, width <= 1024 */
+    int32_t channels;       /* 1..4; height * width * channels a multiple of 16 */
+    int32_t sc, sy, sx;     /* byte strides of channel / row / column: (1, width*channels, channels) or (height*width, width, 1) */
+} pfa_pixel_config;
+size_t pfa_pixel_squared_state_bytes(const pfa_squared_config *cfg, const pfa_pixel_config *pix);
+/* pfa_squared_async_reset on the state grid, then the frames: obs [N][height*width*channels] u8. */
+int pfa_pixel_squared_async_reset(void *state, const pfa_squared_config *cfg, const pfa_pixel_config *pix, int64_t seed, uint8_t *obs,
+                                  float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* pfa_squared_send on the state grid and a repaint of every frame, one launch. */
+int pfa_pixel_squared_send(void *state, const pfa_squared_config *cfg, const pfa_pixel_config *pix, const int64_t *actions, uint8_t *obs,
+                           float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MLP policy — pufferlib.models.Default (models.py:24-62) wrapped by frameworks.cleanrl.Policy
  * (cleanrl.py:50-66) with sample_logits (cleanrl.py:25-47): one Discrete head, or the MultiDiscrete branch (models.py:29-35,
  * 55-58: one decoder Linear per head; cleanrl.py:31-44: one multinomial per head, log-probabilities and entropies summed).

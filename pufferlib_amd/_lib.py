@@ -16,7 +16,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, '_lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libpufferlib_amd.so')
-SOURCES = ['common.cpp', 'dist.cpp', 'p2p.hip', 'gae.hip', 'squared.hip', 'rollout.hip', 'ppo_update.hip', 'lstm.hip', 'gemm.hip', 'lstm_fused.hip', 'lstm_seq.hip', 'stochastic.hip', 'memory.hip', 'bandit.hip', 'multiagent.hip', 'spaces.hip', 'synthetic.hip', 'nativize.hip', 'igemm.hip', 'cnn_heads.hip', 'general.hip', 'ppo_wide.hip']
+SOURCES = ['common.cpp', 'dist.cpp', 'p2p.hip', 'gae.hip', 'squared.hip', 'pixel_squared.hip', 'rollout.hip', 'ppo_update.hip', 'lstm.hip', 'gemm.hip', 'lstm_fused.hip', 'lstm_seq.hip', 'stochastic.hip', 'memory.hip', 'bandit.hip', 'multiagent.hip', 'spaces.hip', 'synthetic.hip', 'nativize.hip', 'igemm.hip', 'cnn_heads.hip', 'general.hip', 'ppo_wide.hip']
 # every header under csrc/ (sorted: the order is part of source_hash) + the public C header: a header missing from a hand-kept list is a
 # library that silently is not rebuilt when only that header changes
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.hpp')) + [os.path.join('..', '..', 'include', 'pufferlib_amd.h')]
@@ -73,6 +73,10 @@ def build(force=False, verbose=False):
 class SquaredConfig(C.Structure):
     _fields_ = [('num_envs', C.c_int32), ('distance_to_target', C.c_int32), ('num_targets', C.c_int32),
                 ('obs_stride', C.c_int32), ('tape_rounds', C.c_int32)]
+
+
+class PixelConfig(C.Structure):
+    _fields_ = [('height', C.c_int32), ('width', C.c_int32), ('channels', C.c_int32), ('sc', C.c_int32), ('sy', C.c_int32), ('sx', C.c_int32)]
 
 
 NAT_MAX_FIELDS = 32
@@ -181,6 +185,9 @@ _SIGNATURES = {
     'pfa_squared_last_infos': (C.c_int, [P, C.POINTER(SquaredConfig), P, P, P, P, P]),
     'pfa_squared_debug_targets': (C.c_int, [P, C.POINTER(SquaredConfig), P, P]),
     'pfa_squared_debug_stream_pos': (C.c_int, [P, C.POINTER(SquaredConfig), P, P]),
+    'pfa_pixel_squared_state_bytes': (C.c_size_t, [C.POINTER(SquaredConfig), C.POINTER(PixelConfig)]),
+    'pfa_pixel_squared_async_reset': (C.c_int, [P, C.POINTER(SquaredConfig), C.POINTER(PixelConfig), C.c_int64, P, P, P, P, P, P]),
+    'pfa_pixel_squared_send': (C.c_int, [P, C.POINTER(SquaredConfig), C.POINTER(PixelConfig), P, P, P, P, P, P, P]),
     'pfa_mlp_param_count': (C.c_int64, [C.POINTER(MlpDims)]),
     'pfa_mlp_forward_sample': (C.c_int, [P, C.c_int64, P, C.POINTER(MlpDims), P, C.POINTER(NoiseKey), C.c_int64,
                                          P, P, P, P, P]),

@@ -44,7 +44,7 @@ from . import dist as pdist
 from .cleanrl import Policy, RecurrentPolicy, _weights_changed, reads_frames, route
 from .models import FlatParams  # noqa: F401  (re-exported: callers of create() type-check the trainer's parameter buffer against it)
 from .namespace import namespace
-from .vector import Frames, Spaces, Squared, Stochastic, _DeviceVecEnv
+from .vector import Frames, PixelSquared, Spaces, Squared, Stochastic, _DeviceVecEnv
 
 
 def seed_everything(seed, torch_deterministic=True):
@@ -309,7 +309,7 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
     if conv:
         space = vecenv.single_observation_space
         name, layout = ('models.ProcgenResnet', ' (H, W, C)') if kind == 'resnet' else ('models.Convolutional', '')
-        if not (host_mode or isinstance(vecenv, Frames)):
+        if not (host_mode or type(vecenv).OBS_U8):       # a device env whose live observations are bytes: vector.Frames, vector.PixelSquared
             raise NotImplementedError(f'{name} reads uint8 frames: a host vecenv or vector.Frames')
         if np.dtype(space.dtype) != np.uint8 or len(space.shape) != 3:
             raise NotImplementedError(f'{name} reads 3-D uint8 frames{layout}, the env shows {space.dtype} {space.shape}')
@@ -322,6 +322,8 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
             conv_geometry_of(policy)
     if isinstance(vecenv, Frames) and not conv:
         raise NotImplementedError('vector.Frames shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
+    if isinstance(vecenv, PixelSquared) and not conv:
+        raise NotImplementedError('vector.PixelSquared shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
     if recurrent and isinstance(vecenv, Stochastic):
         raise NotImplementedError('the device-resident Stochastic vecenv has a fused rollout for the MLP policy only '
                                   '(ocean.Stochastic: "do not use a policy with memory", ocean.py:534)')

@@ -426,35 +426,8 @@ __global__ void __launch_bounds__(256) squared_send_kernel(SquaredView v, const 
                                                           uint8_t *masks) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= v.n) return;
-    SquaredEnv s;
-    squared_load(v, e, s);
-    float *grid = obs + (size_t)e * v.stride;
     uint16_t tc[kMaxTargets];
-    float reward;
-    bool terminal, finished = false;
-    double fr = 0.0, fs = 0.0;
-    int fl = 0;
-    if (s.done) {
-        if ((long long)s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
-        const uint16_t *tr = v.tape + (size_t)(s.rounds % (uint32_t)v.tape_rounds) * v.nt * v.n;
-        squared_reset(v, e, s, grid, tr, tc, reward, terminal);
-        for (int t = 0; t < v.nt; ++t) v.tgt[(size_t)t * v.n + e] = tc[t];
-        s.rounds += 1;
-    } else {
-        for (int t = 0; t < v.nt; ++t) tc[t] = v.tgt[(size_t)t * v.n + e];
-        squared_step(v, s, grid, tc, (int)actions[e], reward, terminal, finished, fr, fl, fs);
-    }
-    squared_store(v, e, s);
-    v.fin[e] = finished ? 1 : 0;
-    if (finished) {
-        v.fin_ret[e] = fr;
-        v.fin_len[e] = fl;
-        v.fin_score[e] = fs;
-    }
-    rewards[e] = reward;
-    terminals[e] = terminal ? 1 : 0;
-    truncations[e] = 0;
-    masks[e] = 1;
+    squared_send_env(v, e, (int)actions[e], obs + (size_t)e * v.stride, tc, rewards, terminals, truncations, masks);
 }
 
 // deterministic fixed-order reduction of the per-env episode accumulators

@@ -227,6 +227,41 @@ __device__ __forceinline__ void squared_step(const SquaredView &v, SquaredEnv &s
     s.done = done;      // emulation.py:226
 }
 
+// Serial.send (vector.py:137-156) for env e by its owner thread, infos of the send included: what the protocol send of every family
+// over this state machine runs (squared.hip on the live float rows, pixel_squared.hip on the grid it keeps in its state).  `grid`:
+// the env's row of v.stride floats; `tc`: kMaxTargets cells of the caller's.
+template <typename GridPtr>
+__device__ __forceinline__ void squared_send_env(const SquaredView &v, int e, int action, GridPtr grid, uint16_t *tc, float *rewards,
+                                                 uint8_t *terminals, uint8_t *truncations, uint8_t *masks) {
+    SquaredEnv s;
+    squared_load(v, e, s);
+    float reward;
+    bool terminal, finished = false;
+    double fr = 0.0, fs = 0.0;
+    int fl = 0;
+    if (s.done) {
+        if ((long long)s.rounds >= v.hdr->rounds_filled) v.hdr->underrun = 1;
+        const uint16_t *tr = v.tape + (size_t)(s.rounds % (uint32_t)v.tape_rounds) * v.nt * v.n;
+        squared_reset(v, e, s, grid, tr, tc, reward, terminal);
+        for (int t = 0; t < v.nt; ++t) v.tgt[(size_t)t * v.n + e] = tc[t];
+        s.rounds += 1;
+    } else {
+        for (int t = 0; t < v.nt; ++t) tc[t] = v.tgt[(size_t)t * v.n + e];
+        squared_step(v, s, grid, tc, action, reward, terminal, finished, fr, fl, fs);
+    }
+    squared_store(v, e, s);
+    v.fin[e] = finished ? 1 : 0;
+    if (finished) {
+        v.fin_ret[e] = fr;
+        v.fin_len[e] = fl;
+        v.fin_score[e] = fs;
+    }
+    rewards[e] = reward;
+    terminals[e] = terminal ? 1 : 0;
+    truncations[e] = 0;
+    masks[e] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Single-target form (num_targets == 1, every ocean default) for the fused rollout, where the env step sits on the
 // rollout's per-step critical path.  Same statements as squared_reset / squared_step above, with what is constant per

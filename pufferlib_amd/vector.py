@@ -73,9 +73,12 @@ def make_squared(distance_to_target=3, num_targets=1, **kwargs):
 
 
 def env_creator(name='squared'):
-    """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only."""
+    """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only; plus pixel_squared, this package's frame
+    rendering of it (the reference has no such name)."""
     if name == 'squared':
         return make_squared
+    if name == 'pixel_squared':
+        return make_pixel_squared
     raise ValueError('Invalid environment name')
 
 
@@ -493,6 +496,95 @@ class Squared(_ResetTape, _DeviceVecEnv):
         _lib.check(self.L.pfa_squared_debug_stream_pos(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out),
                                                        _lib.stream_handle()), 'debug_stream_pos')
         return int(out.item())
+
+
+def make_pixel_squared(distance_to_target=3, num_targets=1, height=64, width=64, channels=3, channels_last=True, **kwargs):
+    """Env creator token of ocean Squared rendered as uint8 frames — the device env a conv policy can learn: make_squared's
+    dynamics, shown as (height, width, channels) frames (channels_last) or (channels, height, width) ones."""
+    return PixelSquaredSpec(distance_to_target, num_targets, height, width, channels, channels_last)
+
+
+class PixelSquaredSpec(SquaredSpec):
+    """SquaredSpec with the frame as observation.  Pixel (y, x) shows grid cell (y*g // height, x*g // width), g = 2d + 1; a cell
+    shows 0 when empty, (255, 128) in (even, odd) channels for a target marker and (128, 255) for the agent: the three values differ in
+    every channel.  Channels are colour planes, not a time stack."""
+    MAX_CHANNELS = 4
+
+    def __init__(self, distance_to_target=3, num_targets=1, height=64, width=64, channels=3, channels_last=True):
+        super().__init__(distance_to_target, num_targets)
+        self.height, self.width, self.channels, self.channels_last = int(height), int(width), int(channels), bool(channels_last)
+        g = self.grid_size
+        if self.height < g or self.width < g:
+            raise APIUsageError(f'frames of {self.height} x {self.width} pixels cannot show a {g} x {g} grid: height and width must be at least {g}')
+        if not 1 <= self.channels <= self.MAX_CHANNELS:
+            raise APIUsageError(f'{self.channels} channels: the frame painter writes 1..{self.MAX_CHANNELS} colour planes')
+        self.shape = (self.height, self.width, self.channels) if self.channels_last else (self.channels, self.height, self.width)
+        if (self.height * self.width * self.channels) % 16 != 0:
+            raise APIUsageError(f'frames of shape {self.shape}: the device env writes rows of a multiple of 16 bytes')
+        self.single_observation_space = spaces.Box(low=0, high=255, shape=self.shape, dtype=np.uint8)
+        self.observation_space = self.single_observation_space
+        self.emulated = namespace(observation_dtype=np.dtype(np.uint8),
+                                  emulated_observation_dtype=np.dtype((np.uint8, self.shape)))
+
+
+class PixelSquared(_ResetTape, _DeviceVecEnv):
+    """Device-resident vecenv of N ocean Squared envs shown as uint8 frames (csrc/pixel_squared.hip): `Squared`'s state machine, state
+    layout, reset-target tape and statistics — rewards, terminals, infos and targets equal Squared's bit for bit at the same settings,
+    seed and env count — with the float grid kept in the device state (``grid``) and the live observation a frame repainted from it on
+    every send.  It has no fused rollout: a conv policy's step is many launches, so the trainer steps it (policy step + store + send)."""
+    FAMILY = 'pixel_squared'
+    NAMES = ('distance_to_target', 'num_targets', 'height', 'width', 'channels', 'channels_last')
+    DEFAULTS = (3, 1, 64, 64, 3, True)
+    SEEDED = True
+    CONFIG_NAME = 'PixelSquared '
+    ABI = 'pfa_squared'         # episode statistics and infos: Squared's entry points on the Squared block of the state
+    OBS_U8 = True
+    ROLLOUT_LSTM = None
+    fused_rollout_mlp = None
+    PREFETCH = False
+
+    def _spec(self, d, nt, height, width, channels, channels_last):
+        spec = PixelSquaredSpec(d, nt, height, width, channels, channels_last)
+        self.obs_stride = spec.height * spec.width * spec.channels            # bytes per row
+        return spec
+
+    def _alloc_state(self):
+        import torch
+        sp = self.driver_env
+        g = sp.grid_size
+        self.obs_dim = self.obs_stride
+        self.observations = self.obs_buf.view(self.num_agents, *sp.shape)
+        self.episode_len = sp.num_targets * sp.distance_to_target + 1
+        self.tape_rounds = 192
+        grid_stride = _lib.round_up(g * g, 16)
+        self.cfg = _lib.SquaredConfig(self.num_agents, sp.distance_to_target, sp.num_targets, grid_stride, self.tape_rounds)
+        h, w, c = sp.height, sp.width, sp.channels
+        self.pix = _lib.PixelConfig(h, w, c, *((1, w * c, c) if sp.channels_last else (h * w, w, 1)))
+        nbytes = self.L.pfa_pixel_squared_state_bytes(C.byref(self.cfg), C.byref(self.pix))
+        if nbytes == 0:
+            raise APIUsageError(self.L.pfa_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        # the float grid Squared shows as its observation: rows of grid_stride floats behind the Squared block of the state
+        self.grid = self.state[nbytes - self.num_agents * grid_stride * 4:].view(torch.float32).view(self.num_agents, grid_stride)
+        sp._live_obs = self.grid
+        self._tape_reset()
+
+    _finishing_send = Squared._finishing_send
+    _k_fill = Squared._k_fill
+    _before_send = Squared._before_send
+    debug_targets = Squared.debug_targets
+
+    def _k_reset(self, seed):
+        self._wait_tape()
+        _lib.check(self.L.pfa_pixel_squared_async_reset(_lib.ptr(self.state), C.byref(self.cfg), C.byref(self.pix), seed, *self._live(),
+                                                        _lib.stream_handle()), 'async_reset')
+        self._tape_reset()
+
+    def _k_send(self, actions):
+        """The caller has drawn the reset rounds (send() does; the trainer's loop calls ensure_tape for many sends at once)."""
+        self._wait_tape()
+        _lib.check(self.L.pfa_pixel_squared_send(_lib.ptr(self.state), C.byref(self.cfg), C.byref(self.pix), _lib.ptr(actions), *self._live(),
+                                                 _lib.stream_handle()), 'send')
 
 
 def make_stochastic(p=0.7, horizon=100, **kwargs):

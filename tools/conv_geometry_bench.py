@@ -6,6 +6,8 @@ code; modelled on tools/igemm_bench.py).
                                                              the strided one (mode 4, everything else)
     python tools/conv_geometry_bench.py train [envs] [tags]  create / evaluate / train on vector.Frames at the geometry's frame shape with
                                                              the c4 hyper-parameters: env steps/s (env parity unpinned, synthetic frames)
+    python tools/conv_geometry_bench.py train_pixel [envs] [tags]  the same on vector.PixelSquared (Squared painted at the geometry's
+                                                             frame shape; geometries of more than four channels are skipped)
 
 Launches go through the C-ABI entry points the engine uses, timed with HIP events on their stream (median of 5 after 2 warm-ups).
 TFLOP/s = algorithmic flop (2 m n k) / time; the peak it is held against is 157.3 TFLOP/s (256 CUs x 256 flop / clock x 2.4 GHz)."""
@@ -65,7 +67,7 @@ def layers(n):
     return rows
 
 
-def train(envs, tags):
+def train(envs, tags, pixel=False):
     import torch
     import conv_geometry as cg
     from pufferlib_amd import clean_pufferl, cleanrl, models, namespace, vector
@@ -74,12 +76,19 @@ def train(envs, tags):
         geo = cg.GEOMETRIES[tag]
         last = geo['kwargs'].get('channels_last', False)
         (h, w, c) = geo['obs'] if last else (geo['obs'][1], geo['obs'][2], geo['obs'][0])
-        vec = vector.make(vector.make_frames, num_envs=envs, backend=vector.Frames,
-                          env_kwargs=dict(framestack=c, num_actions=4, episode_length=100, height=h, width=w, channels_last=last))
+        if pixel and c > vector.PixelSquaredSpec.MAX_CHANNELS:
+            print(json.dumps(dict(tag=tag, skipped=f'{c} channels')), flush=True)
+            continue
+        if pixel:
+            vec = vector.make(vector.make_pixel_squared, num_envs=envs, backend=vector.PixelSquared,
+                              env_kwargs=dict(height=h, width=w, channels=c, channels_last=last))
+        else:
+            vec = vector.make(vector.make_frames, num_envs=envs, backend=vector.Frames,
+                              env_kwargs=dict(framestack=c, num_actions=4, episode_length=100, height=h, width=w, channels_last=last))
         torch.manual_seed(0)
         pol = cleanrl.Policy(models.Convolutional(vec.driver_env, **geo['kwargs']))
         B = envs * horizon
-        cfg = namespace(env='frames', seed=1, torch_deterministic=True, device='cuda', total_timesteps=B * 1000, learning_rate=2.5e-4,
+        cfg = namespace(env='pixel_squared' if pixel else 'frames', seed=1, torch_deterministic=True, device='cuda', total_timesteps=B * 1000, learning_rate=2.5e-4,
                         anneal_lr=True, gamma=0.99, gae_lambda=0.95, update_epochs=1, norm_adv=True, clip_coef=0.1, clip_vloss=True, vf_coef=0.5,
                         vf_clip_coef=0.1, max_grad_norm=0.5, ent_coef=0.01, target_kl=None, batch_size=B, minibatch_size=B, bptt_horizon=16,
                         checkpoint_interval=0, data_dir='/tmp/pfa_bench', exp_id='geom')
@@ -94,7 +103,7 @@ def train(envs, tags):
             clean_pufferl.train(data)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps(dict(tag=tag, envs=envs, horizon=horizon, chunk=data.cnn_engine.chunk, steps_per_s=round(iters * B / dt),
+        print(json.dumps(dict(tag=tag, env=type(vec).__name__, envs=envs, horizon=horizon, chunk=data.cnn_engine.chunk, steps_per_s=round(iters * B / dt),
                               finite=bool(torch.isfinite(data.flat_params.flat).all()))), flush=True)
         del data, pol, vec
         torch.cuda.empty_cache()
@@ -106,4 +115,4 @@ if __name__ == '__main__':
         layers(int(sys.argv[2]) if len(sys.argv) > 2 else 4096)
     else:
         import conv_geometry
-        train(int(sys.argv[2]) if len(sys.argv) > 2 else 4096, sys.argv[3:] or list(conv_geometry.GEOMETRIES))
+        train(int(sys.argv[2]) if len(sys.argv) > 2 else 4096, sys.argv[3:] or list(conv_geometry.GEOMETRIES), pixel=what == 'train_pixel')
