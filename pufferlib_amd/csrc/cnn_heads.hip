@@ -2,7 +2,8 @@
 // value_fn Linear(H, 1)) on the H-wide hidden vector the conv stack + Linear(flat_size, H) of csrc/igemm.hip produce (H = 512 or 128):
 //   cnn_heads_sample   rollout: logits, value, sample_logits (cleanrl.py:25-47) -> action, log-prob, entropy, value
 //   cnn_heads_loss     training: the same heads, the PPO loss of clean_pufferl.py:202-238, d loss / d (head outputs) [rows][16],
-//                      d loss / d (pre-ReLU hidden) [rows][H], the six loss sums (f64, (hi, lo) float pairs)
+//                      d loss / d (pre-ReLU hidden) [rows][H], the six loss sums (f64, (hi, lo) float pairs); the loss itself is
+//                      ppo_row_loss.hpp's, shared with the LSTM and width-general heads kernels
 //   cnn_heads_eval     policy(frames, action=...): log-prob of GIVEN actions, entropy, value (the rollout's bits for the action it drew)
 //   cnn_heads_eval_backward  its backward for arbitrary upstream gradients: d / d (head outputs) [rows][16], d / d (pre-ReLU hidden)
 //   cnn_gather_frames  the uint8 frames of a chunk of minibatch rows, copied next to each other (rows of a minibatch are
@@ -11,9 +12,12 @@
 // the 16-lane log-softmax / arg-max pieces shared with the MLP and LSTM policies (sampler.hpp), so all three sample and score
 // with identical arithmetic.  The hidden width is a template argument (512: the Atari binding, 128: crafter / dm_lab / butterfly) or, for
 // any other multiple of 16 up to 1024, a run-time argument of the same code (the LDS carve follows the width).  More than 15 actions: the row kernels of csrc/general.hip on head outputs computed by pfa_igemm_rows.  VALU work: 2 x H x (A + 1) flop per row against ~56 MFLOP in the conv stack.
+#include <type_traits>
+
 #include "common.hpp"
 #include "lane_ops.hpp"
 #include "mlp_tile.hpp"
+#include "ppo_row_loss.hpp"
 #include "ppo_tile.hpp"
 #include "sampler.hpp"
 
@@ -46,23 +50,40 @@ __device__ __forceinline__ float cnn_head_dot(const float *hrow, const float *w2
     return acc;
 }
 
+// The dynamic LDS of the four heads kernels (cnn_heads_lds(H) bytes): head weights [16][H + 1], their biases [16], hidden rows [16][H]
+struct CnnLds {
+    float *lds;
+    int H;
+    __device__ __forceinline__ float *w2v() const { return lds; }
+    __device__ __forceinline__ float *b2v() const { return lds + kOut * (H + 1); }
+    __device__ __forceinline__ float *hs() const { return b2v() + kOut; }
+};
+// hidden rows 16 tile .. 16 tile + 15 into hs (zeros past the end), between the barriers that fence the previous tile's readers and
+// publish this one
+template <int HT>
+__device__ __forceinline__ void cnn_stage_rows(const float *h, float *hs, long long tile, long long rows, int hrt) {
+    const int H = HT ? HT : hrt;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 16 * H; i += 256) {
+        const long long r = tile * 16 + i / H;
+        hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
+    }
+    __syncthreads();
+}
+
 template <int HT>
 __global__ void __launch_bounds__(256) cnn_heads_sample_kernel(const float *h, int hrt, long long rows, CnnHeads hd, const float *noise, uint64_t seed,
                                                               uint64_t step, long long row_offset, long long *actions, float *logprob,
                                                               float *entropy, float *value) {
     extern __shared__ float lds[];
     const int H = HT ? HT : hrt;
-    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;   // hs [16][H]
+    const CnnLds m{lds, H};
+    float *w2v = m.w2v(), *b2v = m.b2v(), *hs = m.hs();
     cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
     const long long tiles = (rows + 15) / 16;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * H; i += 256) {
-            const long long r = tile * 16 + i / H;
-            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
-        }
-        __syncthreads();
+        cnn_stage_rows<HT>(h, hs, tile, rows, hrt);
         const long long row = tile * 16 + le;
         const bool ok = row < rows;
         const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
@@ -124,17 +145,13 @@ __global__ void __launch_bounds__(256) cnn_heads_eval_kernel(const float *h, int
                                                             float *logprob, float *entropy, float *value) {
     extern __shared__ float lds[];
     const int H = HT ? HT : hrt;
-    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;   // hs [16][H]
+    const CnnLds m{lds, H};
+    float *w2v = m.w2v(), *b2v = m.b2v(), *hs = m.hs();
     cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
     const long long tiles = (rows + 15) / 16;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * H; i += 256) {
-            const long long r = tile * 16 + i / H;
-            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
-        }
-        __syncthreads();
+        cnn_stage_rows<HT>(h, hs, tile, rows, hrt);
         const long long row = tile * 16 + le;
         const bool ok = row < rows;
         const int action = ok ? (int)actions[row] : 0;
@@ -158,17 +175,13 @@ __global__ void __launch_bounds__(256) cnn_heads_eval_backward_kernel(const floa
                                                                      float *dout /* [rows][16] */, float *dh /* [rows][H] */) {
     extern __shared__ float lds[];
     const int H = HT ? HT : hrt;
-    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;
+    const CnnLds m{lds, H};
+    float *w2v = m.w2v(), *b2v = m.b2v(), *hs = m.hs();
     cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
     const long long tiles = (rows + 15) / 16;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * H; i += 256) {
-            const long long r = tile * 16 + i / H;
-            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
-        }
-        __syncthreads();
+        cnn_stage_rows<HT>(h, hs, tile, rows, hrt);
         const long long row = tile * 16 + le;
         const bool ok = row < rows;
         const int action = ok ? (int)actions[row] : 0;
@@ -178,6 +191,7 @@ __global__ void __launch_bounds__(256) cnn_heads_eval_backward_kernel(const floa
         const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
         const Row16Eval ev = eval_row16_heads(mine, lo, a, 0, action);
         float d = 0.0f;
+        // (logit_grad with c_ent = -g_ent, kept as the subtraction it compiles to today: see heads_rows_eval_bwd_kernel, general.hip)
         if (ev.is_logit) d = g_lp * ((ev.chosen ? 1.0f : 0.0f) - ev.p) - g_ent * ev.p * (ev.nl + ev.head_entropy);
         else if (lo == a) d = g_v;
         if (ok) dout[row * kOut + lo] = d;
@@ -193,29 +207,17 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, int
                                                             double *stats_partial /* [gridDim.x][8] */) {
     extern __shared__ float lds[];
     const int H = HT ? HT : hrt;
-    float *w2v = lds, *b2v = w2v + kOut * (H + 1), *hs = b2v + kOut;
+    const CnnLds m{lds, H};
+    float *w2v = m.w2v(), *b2v = m.b2v(), *hs = m.hs();
     __shared__ double st[16][8];
     cnn_stage_heads<HT>(hd, w2v, b2v, hrt);
     const int le = threadIdx.x >> 4, lo = threadIdx.x & 15, a = hd.a;
-    float adv_mean = 0.0f, adv_den = 1.0f;
-    if (hp.norm_adv) {
-        const double s1 = adv_stats[2 * map.mb], s2 = adv_stats[2 * map.mb + 1];
-        const double mean = s1 / global_rows;
-        double var = (s2 - s1 * mean) / (global_rows - 1.0);
-        var = var > 0.0 ? var : 0.0;
-        adv_mean = (float)mean;
-        adv_den = (float)sqrt(var) + 1e-8f;
-    }
+    const AdvNorm norm = adv_norm(hp, adv_stats, map.mb, global_rows);
     const float inv_rows = (float)(1.0 / global_rows);
     double acc[6] = {0, 0, 0, 0, 0, 0};
     const long long tiles = (rows + 15) / 16;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * H; i += 256) {
-            const long long r = tile * 16 + i / H;
-            hs[i] = r < rows ? h[r * H + i % H] : 0.0f;
-        }
-        __syncthreads();
+        cnn_stage_rows<HT>(h, hs, tile, rows, hrt);
         const long long row = tile * 16 + le;
         const bool ok = row < rows;
         const long long fr = ok ? map.flat(q0 + row) : 0;
@@ -223,6 +225,8 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, int
         const int action = ex.actions[fr];
         const float old_logprob = ex.logprobs[fr], old_value = ex.values[fr], adv_raw = ex.advantages[fr], ret = ex.returns[fr];
         const float mine = cnn_head_dot<HT>(hs + le * H, w2v, b2v, lo, hrt);
+        // (the single-head case of eval_row16_heads(mine, lo, a, 0, action), expression for expression, spelled out: the call brings its
+        // loop over heads along — ~50 more instructions per tile and other opcodes, docs/lab-notebook.md)
         const bool is_logit = lo < a;
         const float mx = row16_max(is_logit ? mine : -INFINITY);
         const float ev = is_logit ? expf(mine - mx) : 0.0f;
@@ -233,47 +237,16 @@ __global__ void __launch_bounds__(256) cnn_heads_loss_kernel(const float *h, int
         const bool chosen = lo == action;
         const float new_logprob = row16_sum(chosen ? nl : 0.0f);
         const float new_value = row16_sum(lo == a ? mine : 0.0f);
-        const float logratio = new_logprob - old_logprob;
-        const float ratio = expf(logratio);
-        const float adv = hp.norm_adv ? (adv_raw - adv_mean) / adv_den : adv_raw;
-        const float lo_c = 1.0f - hp.clip_coef, hi_c = 1.0f + hp.clip_coef;
-        const float pg1 = -adv * ratio, pg2 = -adv * fminf(fmaxf(ratio, lo_c), hi_c);
-        const bool inside = ratio >= lo_c && ratio <= hi_c;
-        float dpg;   // torch.max's tie rule + clamp's pass-through, as in ppo_tile.hpp
-        if (pg1 > pg2) dpg = -adv;
-        else if (pg1 < pg2) dpg = inside ? -adv : 0.0f;
-        else dpg = inside ? -adv : -0.5f * adv;
         const float scale = inv_rows * w;
-        const float g_lp = dpg * ratio * scale;
-        float v_loss, dv;
-        if (hp.clip_vloss) {
-            const float du = new_value - ret, vl_u = du * du;
-            const float delta = new_value - old_value;
-            const float vcl = old_value + fminf(fmaxf(delta, -hp.vf_clip_coef), hp.vf_clip_coef);
-            const float dc = vcl - ret, vl_c = dc * dc;
-            const bool vin = delta >= -hp.vf_clip_coef && delta <= hp.vf_clip_coef;
-            v_loss = 0.5f * fmaxf(vl_u, vl_c);
-            const float gu = 2.0f * du, gc = vin ? 2.0f * dc : 0.0f;
-            dv = 0.5f * (vl_u > vl_c ? gu : (vl_u < vl_c ? gc : 0.5f * (gu + gc)));
-        } else {
-            const float du = new_value - ret;
-            v_loss = 0.5f * du * du;
-            dv = du;
-        }
-        dv *= hp.vf_coef * scale;
+        const float adv = hp.norm_adv ? (adv_raw - norm.mean) / norm.den : adv_raw;
+        const PolicyLoss pl = ppo_policy_loss(new_logprob, old_logprob, adv, hp, scale);
+        const ValueLoss vl = ppo_value_loss(new_value, old_value, ret, hp, scale);
         float d = 0.0f;
-        if (is_logit) d = g_lp * ((chosen ? 1.0f : 0.0f) - p) + hp.ent_coef * scale * p * (nl + ent);
-        else if (lo == a) d = dv;
+        if (is_logit) d = logit_grad(pl.g_lp, hp.ent_coef * scale, chosen, p, nl, ent);
+        else if (lo == a) d = vl.dv;
         if (ok) dout[row * kOut + lo] = d;
         cnn_heads_dh<HT>(d, w2v, hs, le, lo, a, ok, row, dh, hrt);
-        if (lo == 0) {
-            acc[0] += (double)(fmaxf(pg1, pg2) * w);
-            acc[1] += (double)(v_loss * w);
-            acc[2] += (double)(ent * w);
-            acc[3] += (double)(-logratio * w);
-            acc[4] += (double)(((ratio - 1.0f) - logratio) * w);
-            acc[5] += (double)((fabsf(ratio - 1.0f) > hp.clip_coef ? 1.0f : 0.0f) * w);
-        }
+        if (lo == 0) accumulate(acc, pl, vl, ent, hp, w);
     }
     __syncthreads();
     if (lo == 0)
@@ -325,62 +298,27 @@ __global__ void __launch_bounds__(256) cnn_gather_frames_bytes_kernel(const uint
 
 static size_t cnn_heads_lds(int H) { return (size_t)(kOut * (H + 1) + kOut + 16 * H) * sizeof(float); }
 
-template <int HT>
-static int cnn_launch_sample(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const CnnHeads &hd, const float *noise,
-                             const pfa_noise_key *key, long long row_offset, long long *actions, float *logprob, float *entropy, float *value) {
-    static int lds_set = 0;   // the opt-in LDS size of this instantiation (grows with the run-time width)
-    const int lds = (int)cnn_heads_lds(H);
-    if (lds > lds_set) {
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_sample_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL(cnn_heads_sample_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, hd, noise, key ? key->seed : 0,
-                       key ? key->step : 0, row_offset, actions, logprob, entropy, value);
-    PFA_LAUNCH_CHECK();
-    return 0;
-}
-template <int HT>
-static int cnn_launch_eval(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const CnnHeads &hd, const long long *actions,
-                           float *logprob, float *entropy, float *value) {
+// Launch of heads kernel K (any of the four, any width instantiation: K(h, H, args...)) with the dynamic LDS of hidden width H.
+// lds_set: the opt-in LDS size of THIS instantiation so far (it grows with the run-time width).
+template <auto K, class... Args>
+static int cnn_launch(int H, unsigned grid, hipStream_t stream, const float *h, Args... args) {
     static int lds_set = 0;
     const int lds = (int)cnn_heads_lds(H);
     if (lds > lds_set) {
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_eval_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         lds_set = lds;
     }
-    hipLaunchKernelGGL(cnn_heads_eval_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, hd, actions, logprob, entropy, value);
+    hipLaunchKernelGGL(K, dim3(grid), dim3(256), lds, stream, h, H, args...);
     PFA_LAUNCH_CHECK();
     return 0;
 }
-template <int HT>
-static int cnn_launch_eval_backward(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const CnnHeads &hd,
-                                    const long long *actions, const float *g_logprob, const float *g_entropy, const float *g_value, float *dout,
-                                    float *dh) {
-    static int lds_set = 0;
-    const int lds = (int)cnn_heads_lds(H);
-    if (lds > lds_set) {
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_eval_backward_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL(cnn_heads_eval_backward_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, hd, actions, g_logprob, g_entropy,
-                       g_value, dout, dh);
-    PFA_LAUNCH_CHECK();
-    return 0;
-}
-template <int HT>
-static int cnn_launch_loss(int H, unsigned grid, hipStream_t stream, const float *h, long long rows, const RowMap &map, long long q0,
-                           const pfa_experience &ex, const CnnHeads &hd, const pfa_ppo_hparams &hp, const double *adv_stats, double global_rows,
-                           float *dout, float *dh, double *partial) {
-    static int lds_set = 0;
-    const int lds = (int)cnn_heads_lds(H);
-    if (lds > lds_set) {
-        PFA_CHECK_HIP(hipFuncSetAttribute((const void *)cnn_heads_loss_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL(cnn_heads_loss_kernel<HT>, dim3(grid), dim3(256), lds, stream, h, H, rows, map, q0, ex, hd, hp, adv_stats, global_rows, dout,
-                       dh, partial);
-    PFA_LAUNCH_CHECK();
-    return 0;
+
+// f(std::integral_constant<int, HT>) for the instantiation that runs hidden width `hidden`: 512, 128, or 0 = the run-time-width code
+template <class F>
+static int cnn_hidden(int hidden, F &&f) {
+    if (hidden == 512) return f(std::integral_constant<int, 512>{});
+    if (hidden == 128) return f(std::integral_constant<int, 128>{});
+    return f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace pfa
@@ -399,12 +337,11 @@ extern "C" int pfa_cnn_heads_sample(const float *h, int32_t hidden, int64_t rows
     const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
     CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
     ScopedKernelTimer timer("cnn_heads_sample", (hipStream_t)stream);
-#define PFA_CNN_SAMPLE(HT) \
-    cnn_launch_sample<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, noise, key, (long long)row_offset, (long long *)actions, logprob, entropy, value)
-    if (hidden == 512) return PFA_CNN_SAMPLE(512);
-    if (hidden == 128) return PFA_CNN_SAMPLE(128);
-    return PFA_CNN_SAMPLE(0);
-#undef PFA_CNN_SAMPLE
+    return cnn_hidden(hidden, [&](auto ht) {
+        return cnn_launch<cnn_heads_sample_kernel<decltype(ht)::value>>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, noise,
+                                                                        key ? key->seed : 0, key ? key->step : 0, (long long)row_offset,
+                                                                        (long long *)actions, logprob, entropy, value);
+    });
 }
 
 extern "C" int pfa_cnn_heads_eval(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b, const float *value_w,
@@ -418,12 +355,10 @@ extern "C" int pfa_cnn_heads_eval(const float *h, int32_t hidden, int64_t rows, 
     const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
     CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
     ScopedKernelTimer timer("cnn_heads_eval", (hipStream_t)stream);
-#define PFA_CNN_EVAL(HT) \
-    cnn_launch_eval<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, (const long long *)actions, logprob, entropy, value)
-    if (hidden == 512) return PFA_CNN_EVAL(512);
-    if (hidden == 128) return PFA_CNN_EVAL(128);
-    return PFA_CNN_EVAL(0);
-#undef PFA_CNN_EVAL
+    return cnn_hidden(hidden, [&](auto ht) {
+        return cnn_launch<cnn_heads_eval_kernel<decltype(ht)::value>>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd,
+                                                                      (const long long *)actions, logprob, entropy, value);
+    });
 }
 
 extern "C" int pfa_cnn_heads_eval_backward(const float *h, int32_t hidden, int64_t rows, const float *actor_w, const float *actor_b,
@@ -438,12 +373,10 @@ extern "C" int pfa_cnn_heads_eval_backward(const float *h, int32_t hidden, int64
     const unsigned grid = (unsigned)(tiles < 1024 ? tiles : 1024);
     CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
     ScopedKernelTimer timer("cnn_heads_eval_backward", (hipStream_t)stream);
-#define PFA_CNN_EVAL_BWD(HT) \
-    cnn_launch_eval_backward<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd, (const long long *)actions, g_logprob, g_entropy, g_value, dout, dh)
-    if (hidden == 512) return PFA_CNN_EVAL_BWD(512);
-    if (hidden == 128) return PFA_CNN_EVAL_BWD(128);
-    return PFA_CNN_EVAL_BWD(0);
-#undef PFA_CNN_EVAL_BWD
+    return cnn_hidden(hidden, [&](auto ht) {
+        return cnn_launch<cnn_heads_eval_backward_kernel<decltype(ht)::value>>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, hd,
+                                                                               (const long long *)actions, g_logprob, g_entropy, g_value, dout, dh);
+    });
 }
 
 extern "C" size_t pfa_cnn_heads_loss_workspace_bytes(void) { return (size_t)1024 * 8 * sizeof(double); }
@@ -464,10 +397,11 @@ extern "C" int pfa_cnn_heads_loss(const float *h, int32_t hidden, const pfa_expe
     CnnHeads hd{actor_w, actor_b, value_w, value_b, (int)num_actions};
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     ScopedKernelTimer timer("cnn_heads_loss", (hipStream_t)stream);
-#define PFA_CNN_LOSS(HT) \
-    cnn_launch_loss<HT>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, map, (long long)q0, *exp, hd, *hp, adv_stats, (double)global_mb_rows, dout, dh, (double *)workspace)
-    if (int rc = hidden == 512 ? PFA_CNN_LOSS(512) : hidden == 128 ? PFA_CNN_LOSS(128) : PFA_CNN_LOSS(0)) return rc;
-#undef PFA_CNN_LOSS
+    const int rc = cnn_hidden(hidden, [&](auto ht) {
+        return cnn_launch<cnn_heads_loss_kernel<decltype(ht)::value>>((int)hidden, grid, (hipStream_t)stream, h, (long long)rows, map, (long long)q0, *exp,
+                                                                      hd, *hp, adv_stats, (double)global_mb_rows, dout, dh, (double *)workspace);
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(cnn_stats_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, (int)grid, loss_pairs16, (int)accumulate);
     PFA_LAUNCH_CHECK();
     return 0;

@@ -10,7 +10,8 @@
 //                      policy(obs, action=...) of frameworks.cleanrl.Policy / RecurrentPolicy (cleanrl.py:60-66,87-93)
 //   heads_rows_eval_backward  d (head outputs) of that call for arbitrary upstream gradients of (log-prob, entropy, value): the
 //                      autograd path of policy(obs, action=...) (general.Evaluator with autograd=True)
-//   heads_rows_loss    the PPO loss of clean_pufferl.py:202-238 for the rows of a chunk and d loss / d (head outputs)
+//   heads_rows_loss    the PPO loss of clean_pufferl.py:202-238 for the rows of a chunk and d loss / d (head outputs); the loss itself
+//                      is ppo_row_loss.hpp's, shared with the LSTM and NatureCNN heads kernels
 //   lstm_cell_fwd/bwd  the element-wise part of one nn.LSTM step (gate order i, f, g, o: models.py:76) and of its
 //                      back-propagation through time
 // Two forms of the four heads_rows_* kernels, chosen inside the entry points:
@@ -26,6 +27,7 @@
 
 #include "common.hpp"
 #include "philox.hpp"
+#include "ppo_row_loss.hpp"
 #include "ppo_tile.hpp"
 #include "sampler.hpp"
 
@@ -135,6 +137,8 @@ __global__ void __launch_bounds__(256) heads_rows_eval_kernel(const float *out, 
 // Backward of heads_rows_eval for ARBITRARY upstream gradients (the autograd path of policy(obs, action=...)): per row, with
 // p = softmax(z_h) and H_h = -sum p log p of head h,
 //   dz_j = g_logprob (1[j = a_h] - p_j) - g_entropy p_j (log p_j + H_h)        d value = g_value
+// (ppo_row_loss.hpp's logit_grad with c_ent = -g_entropy.  The three eval_backward kernels keep the line as a subtraction: with the call
+// their v_sub_f32 become v_add_f32 with a negated operand — the same bits, but not the instructions they had.)
 // All heads of a row share its three upstream numbers (cleanrl.py:38-47 sums log-probability and entropy over the heads).  A null
 // upstream pointer is a zero gradient.  The softmax is heads_rows_eval_kernel's, operation for operation, so both agree on p.  One
 // thread owns its row of dout: plain stores, nothing summed across threads.
@@ -181,15 +185,7 @@ __global__ void __launch_bounds__(256) heads_rows_loss_kernel(const float *out, 
     const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
     double acc[6] = {0, 0, 0, 0, 0, 0};
     if (row < rows) {
-        float adv_mean = 0.0f, adv_den = 1.0f;
-        if (hp.norm_adv) {   // clean_pufferl.py:211-213: unbiased std over the GLOBAL minibatch
-            const double s1 = adv_stats[2 * map.mb], s2 = adv_stats[2 * map.mb + 1];
-            const double mean = s1 / global_rows;
-            double var = (s2 - s1 * mean) / (global_rows - 1.0);
-            var = var > 0.0 ? var : 0.0;
-            adv_mean = (float)mean;
-            adv_den = (float)sqrt(var) + 1e-8f;
-        }
+        const AdvNorm norm = adv_norm(hp, adv_stats, map.mb, global_rows);
         const float inv_rows = (float)(1.0 / global_rows);
         const long long fr = map.flat(chunk_row_to_q(row, q0, R, hp.bptt_horizon));
         const int packed = ex.actions[fr];
@@ -223,34 +219,9 @@ __global__ void __launch_bounds__(256) heads_rows_loss_kernel(const float *out, 
             start += sz;
         }
         const float new_value = o[hs.a];
-        const float logratio = new_logprob - old_logprob;
-        const float ratio = expf(logratio);
-        const float adv = hp.norm_adv ? (adv_raw - adv_mean) / adv_den : adv_raw;
-        const float lo_c = 1.0f - hp.clip_coef, hi_c = 1.0f + hp.clip_coef;
-        const float pg1 = -adv * ratio, pg2 = -adv * fminf(fmaxf(ratio, lo_c), hi_c);
-        const bool inside = ratio >= lo_c && ratio <= hi_c;
-        float dpg;   // torch.max's tie rule + clamp's pass-through, as in ppo_tile.hpp
-        if (pg1 > pg2) dpg = -adv;
-        else if (pg1 < pg2) dpg = inside ? -adv : 0.0f;
-        else dpg = inside ? -adv : -0.5f * adv;
-        const float scale = inv_rows;
-        const float g_lp = dpg * ratio * scale;
-        float v_loss, dv;
-        if (hp.clip_vloss) {
-            const float du = new_value - ret, vl_u = du * du;
-            const float delta = new_value - old_value;
-            const float vcl = old_value + fminf(fmaxf(delta, -hp.vf_clip_coef), hp.vf_clip_coef);
-            const float dc = vcl - ret, vl_c = dc * dc;
-            const bool vin = delta >= -hp.vf_clip_coef && delta <= hp.vf_clip_coef;
-            v_loss = 0.5f * fmaxf(vl_u, vl_c);
-            const float gu = 2.0f * du, gc = vin ? 2.0f * dc : 0.0f;
-            dv = 0.5f * (vl_u > vl_c ? gu : (vl_u < vl_c ? gc : 0.5f * (gu + gc)));
-        } else {
-            const float du = new_value - ret;
-            v_loss = 0.5f * du * du;
-            dv = du;
-        }
-        dv *= hp.vf_coef * scale;
+        const float adv = hp.norm_adv ? (adv_raw - norm.mean) / norm.den : adv_raw;
+        const PolicyLoss pl = ppo_policy_loss(new_logprob, old_logprob, adv, hp, inv_rows);
+        const ValueLoss vl = ppo_value_loss(new_value, old_value, ret, hp, inv_rows);
         // pass 2: d loss / d out
         start = 0;
         for (int h = 0; h < nh; ++h) {
@@ -262,19 +233,16 @@ __global__ void __launch_bounds__(256) heads_rows_loss_kernel(const float *out, 
             for (int j = 0; j < sz; ++j) se += expf(o[start + j] - mx);
             for (int j = 0; j < sz; ++j) {
                 const float nl = o[start + j] - lse_h[h], p = expf(o[start + j] - mx) / se;
-                // d new_logprob/d logit = [chosen] - p ; d entropy/d logit = -p (nl + H_head)
-                d[start + j] = g_lp * ((start + j == act_h[h] ? 1.0f : 0.0f) - p) + hp.ent_coef * scale * p * (nl + ent_h[h]);
+                d[start + j] = logit_grad(pl.g_lp, hp.ent_coef * inv_rows, start + j == act_h[h], p, nl, ent_h[h]);
             }
             start += sz;
         }
-        d[hs.a] = dv;
+        d[hs.a] = vl.dv;
         for (int j = hs.a + 1; j < no; ++j) d[j] = 0.0f;
-        acc[0] = (double)fmaxf(pg1, pg2);
-        acc[1] = (double)v_loss;
-        acc[2] = (double)ent;
-        acc[3] = (double)(-logratio);
-        acc[4] = (double)((ratio - 1.0f) - logratio);
-        acc[5] = (double)(fabsf(ratio - 1.0f) > hp.clip_coef ? 1.0f : 0.0f);
+        float s[6];
+        row_stats(s, pl, vl, ent, hp);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[i] = (double)s[i];   // one row per thread: set (0.0 + x would be an add this kernel never had)
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i)
@@ -456,15 +424,7 @@ __global__ void __launch_bounds__(256) heads_wide_loss_kernel(const float *out, 
     const long long base = (long long)blockIdx.x * 256 + wv * 64;
     const int nrows = rows - base >= 64 ? 64 : (rows > base ? (int)(rows - base) : 0);
     double acc[6] = {0, 0, 0, 0, 0, 0};
-    float adv_mean = 0.0f, adv_den = 1.0f;
-    if (hp.norm_adv) {   // clean_pufferl.py:211-213: unbiased std over the GLOBAL minibatch
-        const double s1 = adv_stats[2 * map.mb], s2 = adv_stats[2 * map.mb + 1];
-        const double mean = s1 / global_rows;
-        double var = (s2 - s1 * mean) / (global_rows - 1.0);
-        var = var > 0.0 ? var : 0.0;
-        adv_mean = (float)mean;
-        adv_den = (float)sqrt(var) + 1e-8f;
-    }
+    const AdvNorm norm = adv_norm(hp, adv_stats, map.mb, global_rows);
     const float inv_rows = (float)(1.0 / global_rows);
     int packed_l = 0;
     float old_logprob_l = 0.0f, old_value_l = 0.0f, adv_raw_l = 0.0f, ret_l = 0.0f;
@@ -498,52 +458,17 @@ __global__ void __launch_bounds__(256) heads_wide_loss_kernel(const float *out, 
         const WideSoftmax sm = wide_softmax<NP>(z, a, lane);
         const int act = packed >= 0 && packed < a ? packed : 0;
         const float new_logprob = wide_pick<NP>(z, act) - sm.lse;
-        const float ent = sm.ent;
-        const float logratio = new_logprob - old_logprob;
-        const float ratio = expf(logratio);
-        const float adv = hp.norm_adv ? (adv_raw - adv_mean) / adv_den : adv_raw;
-        const float lo_c = 1.0f - hp.clip_coef, hi_c = 1.0f + hp.clip_coef;
-        const float pg1 = -adv * ratio, pg2 = -adv * fminf(fmaxf(ratio, lo_c), hi_c);
-        const bool inside = ratio >= lo_c && ratio <= hi_c;
-        float dpg;   // torch.max's tie rule + clamp's pass-through, as in ppo_tile.hpp
-        if (pg1 > pg2) dpg = -adv;
-        else if (pg1 < pg2) dpg = inside ? -adv : 0.0f;
-        else dpg = inside ? -adv : -0.5f * adv;
-        const float scale = inv_rows;
-        const float g_lp = dpg * ratio * scale;
-        float v_loss, dv;
-        if (hp.clip_vloss) {
-            const float du = new_value - ret, vl_u = du * du;
-            const float delta = new_value - old_value;
-            const float vcl = old_value + fminf(fmaxf(delta, -hp.vf_clip_coef), hp.vf_clip_coef);
-            const float dc = vcl - ret, vl_c = dc * dc;
-            const bool vin = delta >= -hp.vf_clip_coef && delta <= hp.vf_clip_coef;
-            v_loss = 0.5f * fmaxf(vl_u, vl_c);
-            const float gu = 2.0f * du, gc = vin ? 2.0f * dc : 0.0f;
-            dv = 0.5f * (vl_u > vl_c ? gu : (vl_u < vl_c ? gc : 0.5f * (gu + gc)));
-        } else {
-            const float du = new_value - ret;
-            v_loss = 0.5f * du * du;
-            dv = du;
-        }
-        dv *= hp.vf_coef * scale;
+        const float adv = hp.norm_adv ? (adv_raw - norm.mean) / norm.den : adv_raw;
+        const PolicyLoss pl = ppo_policy_loss(new_logprob, old_logprob, adv, hp, inv_rows);
+        const ValueLoss vl = ppo_value_loss(new_value, old_value, ret, hp, inv_rows);
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             const int j = lane + 64 * i;
-            if (j < a) {
-                const float nl = z[i] - sm.lse, p = sm.p(z[i]);
-                // d new_logprob/d logit = [chosen] - p ; d entropy/d logit = -p (nl + H)
-                d[j] = g_lp * ((j == act ? 1.0f : 0.0f) - p) + hp.ent_coef * scale * p * (nl + ent);
-            }
+            if (j < a) d[j] = logit_grad(pl.g_lp, hp.ent_coef * inv_rows, j == act, sm.p(z[i]), z[i] - sm.lse, sm.ent);
         }
-        if (lane == 0) d[a] = dv;
+        if (lane == 0) d[a] = vl.dv;
         for (int j = a + 1 + lane; j < no; j += 64) d[j] = 0.0f;
-        acc[0] += (double)fmaxf(pg1, pg2);
-        acc[1] += (double)v_loss;
-        acc[2] += (double)ent;
-        acc[3] += (double)(-logratio);
-        acc[4] += (double)((ratio - 1.0f) - logratio);
-        acc[5] += (double)(fabsf(ratio - 1.0f) > hp.clip_coef ? 1.0f : 0.0f);
+        accumulate(acc, pl, vl, sm.ent, hp, 1.0f);
     }
     if (lane == 0)
         for (int i = 0; i < 8; ++i) st[wv][i] = i < 6 ? acc[i] : 0.0;

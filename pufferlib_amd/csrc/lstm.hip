@@ -5,7 +5,8 @@
 //
 // The products of this path are the fused MFMA kernels of lstm_fused.hip (rollout), lstm_seq.hip (training forward / BPTT) and
 // gemm.hip (weight gradients).  This file holds the rest:
-//   lstm_heads_loss                     decoder + value head, PPO loss, d loss/d heads, d loss/d h, loss sums, head bias gradient
+//   lstm_heads_loss                     decoder + value head, PPO loss (ppo_row_loss.hpp, shared with the NatureCNN and width-general
+//                                       heads kernels), d loss/d heads, d loss/d h, loss sums, head bias gradient
 //   gather_obs_time_major / store_rows / store_step / finish_grads / sumsq pieces for the clip norm
 // and the step-wise pieces the fused kernels replaced, kept as protocol-level entry points and test anchors:
 //   lstm_cell_fwd / lstm_cell_bwd      gate nonlinearities + cell/hidden update and their exact derivatives (gate order i,f,g,o)
@@ -15,6 +16,7 @@
 #include "lane_ops.hpp"
 #include "lstm_tile.hpp"
 #include "mlp_tile.hpp"
+#include "ppo_row_loss.hpp"
 #include "sampler.hpp"
 
 namespace pfa {
@@ -178,17 +180,8 @@ __global__ void __launch_bounds__(256) lstm_heads_loss_kernel(const float *h, lo
     // h[row][16 j + 4 g ..]); dh: contraction index o = 4 kk + g, column tile n.
     const float *wfp = w2v + c * WS + 4 * g, *wbp = w2v + g * WS + c;
     const float bias = b2v[c];
-    float adv_mean = 0.0f, adv_den = 1.0f;
-    if (hp.norm_adv) {
-        const double s1 = adv_stats[2 * map.mb], s2 = adv_stats[2 * map.mb + 1];
-        const double mean = s1 / global_rows;
-        double var = (s2 - s1 * mean) / (global_rows - 1.0);
-        var = var > 0.0 ? var : 0.0;
-        adv_mean = (float)mean;
-        adv_den = (float)sqrt(var) + 1e-8f;
-    }
+    const AdvNorm norm = adv_norm(hp, adv_stats, map.mb, global_rows);
     const float inv_rows = (float)(1.0 / global_rows);
-    const float lo_c = 1.0f - hp.clip_coef, hi_c = 1.0f + hp.clip_coef;
     const bool is_logit = lo < a;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float dsum = 0.0f;  // this lane's column of sum_rows dout (the head bias gradient)
@@ -225,7 +218,8 @@ __global__ void __launch_bounds__(256) lstm_heads_loss_kernel(const float *h, lo
             // log-softmax over the row's logits
             bool chosen;
             float nl, p, ent, hent, new_logprob;
-            if (heads == 0) {
+            if (heads == 0) {   // (eval_row16_heads' single-head case spelled out: straight-line code for the Discrete policies, without
+                                // the call's loop over heads — one branch for both changes the kernel's opcodes, docs/lab-notebook.md)
                 const float mx = row16_max(is_logit ? mine : -INFINITY);
                 const float ev = is_logit ? expf(mine - mx) : 0.0f;
                 const float se = row16_sum(ev);
@@ -240,49 +234,19 @@ __global__ void __launch_bounds__(256) lstm_heads_loss_kernel(const float *h, lo
                 nl = ev.nl, p = ev.p, hent = ev.head_entropy, ent = ev.entropy, chosen = ev.chosen, new_logprob = ev.logprob;
             }
             const float new_value = row16_sum(lo == a ? mine : 0.0f);
-            const float logratio = new_logprob - old_logprob;
-            const float ratio = expf(logratio);
-            const float adv = hp.norm_adv ? (adv_raw - adv_mean) / adv_den : adv_raw;
-            const float pg1 = -adv * ratio, pg2 = -adv * fminf(fmaxf(ratio, lo_c), hi_c);
-            const bool inside = ratio >= lo_c && ratio <= hi_c;
-            float dpg;  // d pg / d ratio: torch.max tie rule + clamp pass-through (see csrc/ppo_update.hip)
-            if (pg1 > pg2) dpg = -adv;
-            else if (pg1 < pg2) dpg = inside ? -adv : 0.0f;
-            else dpg = inside ? -adv : -0.5f * adv;
             const float scale = inv_rows * w;
-            const float g_lp = dpg * ratio * scale;
-            float v_loss, dv;
-            if (hp.clip_vloss) {
-                const float du = new_value - ret, vl_u = du * du;
-                const float delta = new_value - old_value;
-                const float vcl = old_value + fminf(fmaxf(delta, -hp.vf_clip_coef), hp.vf_clip_coef);
-                const float dc = vcl - ret, vl_c = dc * dc;
-                const bool vin = delta >= -hp.vf_clip_coef && delta <= hp.vf_clip_coef;
-                v_loss = 0.5f * fmaxf(vl_u, vl_c);
-                const float gu = 2.0f * du, gc = vin ? 2.0f * dc : 0.0f;
-                dv = 0.5f * (vl_u > vl_c ? gu : (vl_u < vl_c ? gc : 0.5f * (gu + gc)));
-            } else {
-                const float du = new_value - ret;
-                v_loss = 0.5f * du * du;
-                dv = du;
-            }
-            dv *= hp.vf_coef * scale;
+            const float adv = hp.norm_adv ? (adv_raw - norm.mean) / norm.den : adv_raw;
+            const PolicyLoss pl = ppo_policy_loss(new_logprob, old_logprob, adv, hp, scale);
+            const ValueLoss vl = ppo_value_loss(new_value, old_value, ret, hp, scale);
             float d = 0.0f;
-            if (is_logit) d = g_lp * ((chosen ? 1.0f : 0.0f) - p) + hp.ent_coef * scale * p * (nl + hent);
-            else if (lo == a) d = dv;
+            if (is_logit) d = logit_grad(pl.g_lp, hp.ent_coef * scale, chosen, p, nl, hent);
+            else if (lo == a) d = vl.dv;
             if (ok) {
                 dout[row * kOut + lo] = d;
                 dsum += d;
             }
             dt[wv][4 * g + r][lo] = ok ? d : 0.0f;
-            if (lo == 0) {
-                acc[0] += fmaxf(pg1, pg2) * w;
-                acc[1] += v_loss * w;
-                acc[2] += ent * w;
-                acc[3] += -logratio * w;
-                acc[4] += ((ratio - 1.0f) - logratio) * w;
-                acc[5] += (fabsf(ratio - 1.0f) > hp.clip_coef ? 1.0f : 0.0f) * w;
-            }
+            if (lo == 0) accumulate(acc, pl, vl, ent, hp, w);
         }
         // d loss / d h = dout W2v: A operand lane (c, g) = dout[row c][o = 4 kk + g] from this wave's own LDS tile (a wave's LDS
         // operations complete in order: no barrier between its writes above and these reads)

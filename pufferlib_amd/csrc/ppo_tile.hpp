@@ -102,7 +102,9 @@ struct LossOut {
     float pg, v_loss, ent, neg_logratio, kl, clipped;
 };
 
-// PPO loss for the rows of one tile (clean_pufferl.py:202-238) and d(loss)/d(out^T fragment).
+// PPO loss for the rows of one tile (clean_pufferl.py:202-238) and d(loss)/d(out^T fragment).  The formula's reference form is
+// ppo_row_loss.hpp (what the multi-kernel heads kernels run); this is the same loss on loss_exp / loss_log and a reciprocal of the
+// advantages' std, with its own text: it is the headline kernel's, whose instruction order is left alone (docs/next-steps.md).
 // MH: MultiDiscrete (cleanrl.py:31-44) — `heads` packs the head sizes, rs.action the per-head choices (pfa_mlp_dims.heads); the
 // log-softmax, the chosen log-probability and the entropy are taken per head and summed.  The single-head instantiation is the
 // code the headline workload runs, unchanged.

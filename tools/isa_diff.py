@@ -6,7 +6,11 @@ and run   tools/isa_diff.py OLD.s NEW.s [OLD2.s NEW2.s ...].  Compared per .amdh
 instantiation may differ): the instruction text, the .amdhsa_ descriptor block and the metadata entry.  Three things are normalised:
 the per-compile __hip_cuid_<hex> symbol, the function ordinal in local labels (.LBB<n>_<k>, .Lfunc_end<n>, and BB<n>_<k> in comments)
 and the blanks in front of a comment (the column padding behind a label depends on the ordinal's digit count).  Exit status 1 when a
-kernel is missing on either side or differs."""
+kernel is missing on either side or differs.
+With --opcodes in front, every kernel that differs also gets a line for changes that may re-order a kernel but must keep its
+instructions (a helper function taken out of it): instructions before -> after, the opcodes whose COUNT moved (_e32 / _e64 encodings
+of one opcode counted together), VGPRs, static LDS bytes and scratch bytes before -> after."""
+import collections
 import re
 import sys
 
@@ -27,8 +31,33 @@ def kernels(path):
     return out
 
 
+def opcodes(code):
+    c = collections.Counter()
+    for line in code.split('\n'):
+        line = line.split(';')[0].strip()
+        if line and not line.startswith('.') and not line.endswith(':'):
+            c[re.sub(r'_e(32|64)$', '', line.split()[0])] += 1
+    return c
+
+
+def resources(k):
+    field = lambda text, name: int(re.search(r'%s:?\s+(\d+)' % re.escape(name), text).group(1))   # noqa: E731
+    return (field(k['descriptor'], '.amdhsa_next_free_vgpr'), field(k['metadata'], '.group_segment_fixed_size'),
+            field(k['metadata'], '.private_segment_fixed_size'))
+
+
+def opcode_line(a, b):
+    oa, ob = opcodes(a['code']), opcodes(b['code'])
+    moved = ', '.join(f'{o} {oa[o]} -> {ob[o]}' for o in sorted(set(oa) | set(ob)) if oa[o] != ob[o]) or 'none'
+    (va, la, sa), (vb, lb, sb) = resources(a), resources(b)
+    return (f'    instructions {sum(oa.values())} -> {sum(ob.values())}; opcode counts moved: {moved}; VGPRs {va} -> {vb}, LDS {la} -> {lb}, '
+            f'scratch {sa} -> {sb}')
+
+
 def main(argv):
     bad = 0
+    with_opcodes = argv[:1] == ['--opcodes']
+    argv = argv[1:] if with_opcodes else argv
     for old, new in zip(argv[0::2], argv[1::2]):
         a, b = kernels(old), kernels(new)
         differ = [(k, [p for p in a[k] if a[k][p] != b[k].get(p)]) for k in sorted(set(a) & set(b)) if a[k] != b[k]]
@@ -36,6 +65,8 @@ def main(argv):
             print(f'  only in {old if k in a else new}: {k}')
         for k, parts in differ:
             print(f'  differs ({", ".join(parts)}): {k}')
+            if with_opcodes:
+                print(opcode_line(a[k], b[k]))
         print(f'{new}: {len(a)} kernels before, {len(b)} after, {len(differ)} of {len(set(a) & set(b))} differ')
         bad += len(differ) + len(set(a) ^ set(b))
     return 1 if bad else 0
