@@ -412,6 +412,55 @@ int pfa_synth_last_infos(void *state, const pfa_synth_config *cfg, uint8_t *fini
                          int32_t *episode_length, double *score, pfa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tabular vecenv — a user-given finite MDP / POMDP as device tables (csrc/tabular_env.hpp; built and validated by
+ * pufferlib_amd.vector.TabularMDP): outcome k of action a in state s leads to next[s][a][k] with reward[s][a][k]; cum holds the
+ * outcome probabilities as uint32 thresholds (cum[k] = floor(2^32 * sum_{j<=k} prob_j) clipped to 2^32 - 1; the drawn outcome is the
+ * first k with word < cum[k], else the last one whose threshold rises above its predecessor's).  Entering a state with terminal[s]
+ * != 0, or the step that makes the episode `horizon` steps long, ends the episode (reported as terminal); the send after it is the
+ * auto-reset row, which draws a start state from (start_states, start_cum) the same way.  The word is Philox4x32-10(counter =
+ * (env_offset + env, episode, tick, domain), key = (seed lo, 0x5442 ^ seed hi)).x, domain 0 = start, 1 = transition.  Rewards are
+ * f64, cast to f32 on the buffer write and summed as f64 into the episode return; infos' score = score[final state], or the
+ * episode's return when score is NULL.  All table pointers are device memory; obs rows are obs_stride floats, zero behind obs_dim,
+ * the table 16-byte aligned.  Protocol and live buffers as the other device envs (observation rows of obs_stride floats).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t num_envs;
+    int32_t num_states;     /* S, 1..2^20 */
+    int32_t num_actions;    /* A, 1..1024 */
+    int32_t num_outcomes;   /* K, 1..8 */
+    int32_t num_starts;     /* M, 1..S */
+    int32_t obs_dim;        /* D, 1..160 */
+    int32_t obs_stride;     /* floats per row: 16 / 32 / 64 / 96 / 128 / 160, >= obs_dim */
+    int32_t horizon;        /* >= 1 */
+    uint64_t seed;
+    int64_t env_offset;     /* global index of local env 0 (sharding) */
+    const int32_t *next;          /* [S][A][K] */
+    const uint32_t *cum;          /* [S][A][K] */
+    const double *reward;         /* [S][A][K] */
+    const uint8_t *terminal;      /* [S] */
+    const double *score;          /* [S] or NULL */
+    const float *obs;             /* [S][obs_stride] */
+    const int32_t *start_states;  /* [M] */
+    const uint32_t *start_cum;    /* [M] */
+} pfa_tabular_config;
+size_t pfa_tabular_state_bytes(const pfa_tabular_config *cfg);
+int pfa_tabular_async_reset(void *state, const pfa_tabular_config *cfg, float *obs, float *rewards, uint8_t *terminals,
+                            uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_tabular_send(void *state, const pfa_tabular_config *cfg, const int64_t *actions, float *obs, float *rewards,
+                     uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_tabular_episode_stats(void *state, const pfa_tabular_config *cfg, double *out4, int32_t reset, pfa_stream_t stream);
+int pfa_tabular_last_infos(void *state, const pfa_tabular_config *cfg, uint8_t *finished, double *episode_return,
+                           int32_t *episode_length, double *score, pfa_stream_t stream);
+/* test introspection: out[e] = {state, episode, tick, done, ep_length} of env e */
+int pfa_tabular_debug_states(void *state, const pfa_tabular_config *cfg, int32_t *out5, pfa_stream_t stream);
+/* clean_pufferl.evaluate's loop for a Tabular vecenv and the MLP policy, one persistent kernel (as pfa_rollout_mlp_stochastic;
+ * dims->obs_stride == cfg->obs_stride in 16 / 32 / 64 / 96 / 128, dims->num_actions == cfg->num_actions in 2..15). */
+int pfa_rollout_mlp_tabular(void *state, const pfa_tabular_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                            const pfa_experience *exp, const float *noise, const pfa_noise_key *key, int64_t env_offset,
+                            float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks,
+                            pfa_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Structured-observation unpack — replaces pufferlib.pytorch.nativize_tensor
  * (pufferlib/pytorch.py:96-145): flat emulated rows [num_rows][row_bytes] (device, 16-byte aligned) -> one dense tensor
  * per leaf of the observation space, in one launch.  A field is a leaf as pufferlib.pytorch.nativize_dtype
@@ -576,6 +625,11 @@ int pfa_rollout_lstm_synth(void *state, const pfa_synth_config *cfg, const float
                            const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                            const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                            uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* ... and over the Tabular vecenv (pfa_tabular_*): observation rows of 16 .. 160 floats, one Discrete head of 2..15 actions. */
+int pfa_rollout_lstm_tabular(void *state, const pfa_tabular_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                             const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                             const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                             uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 /* --- the recurrent policy in training mode (csrc/lstm_seq.hip): forward over the `steps` (= bptt_horizon) time steps
  * of a minibatch of `rows` independent segments and back-propagation through time (clean_pufferl.py:186-193, :244).
  * Time-major buffers: obs_tm [steps][rows][obs_stride], xe / dh_heads / dxe [steps][rows][128], gates_act / dgates

@@ -16,7 +16,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, '_lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libpufferlib_amd.so')
-SOURCES = ['common.cpp', 'dist.cpp', 'p2p.hip', 'gae.hip', 'squared.hip', 'pixel_squared.hip', 'rollout.hip', 'ppo_update.hip', 'lstm.hip', 'gemm.hip', 'lstm_fused.hip', 'lstm_seq.hip', 'stochastic.hip', 'memory.hip', 'bandit.hip', 'multiagent.hip', 'spaces.hip', 'synthetic.hip', 'nativize.hip', 'igemm.hip', 'cnn_heads.hip', 'general.hip', 'ppo_wide.hip']
+SOURCES = ['common.cpp', 'dist.cpp', 'p2p.hip', 'gae.hip', 'squared.hip', 'pixel_squared.hip', 'rollout.hip', 'ppo_update.hip', 'lstm.hip', 'gemm.hip', 'lstm_fused.hip', 'lstm_seq.hip', 'stochastic.hip', 'memory.hip', 'bandit.hip', 'multiagent.hip', 'spaces.hip', 'synthetic.hip', 'tabular.hip', 'nativize.hip', 'igemm.hip', 'cnn_heads.hip', 'general.hip', 'ppo_wide.hip']
 # every header under csrc/ (sorted: the order is part of source_hash) + the public C header: a header missing from a hand-kept list is a
 # library that silently is not rebuilt when only that header changes
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.hpp')) + [os.path.join('..', '..', 'include', 'pufferlib_amd.h')]
@@ -98,6 +98,14 @@ class SpacesConfig(C.Structure):
 class SynthConfig(C.Structure):
     _fields_ = [('num_envs', C.c_int32), ('obs_values', C.c_int32), ('obs_stride', C.c_int32), ('num_actions', C.c_int32),
                 ('episode_length', C.c_int32), ('obs_high', C.c_int32), ('seed', C.c_uint64), ('env_offset', C.c_int64)]
+
+
+class TabularConfig(C.Structure):
+    _fields_ = [('num_envs', C.c_int32), ('num_states', C.c_int32), ('num_actions', C.c_int32), ('num_outcomes', C.c_int32),
+                ('num_starts', C.c_int32), ('obs_dim', C.c_int32), ('obs_stride', C.c_int32), ('horizon', C.c_int32),
+                ('seed', C.c_uint64), ('env_offset', C.c_int64), ('next', C.c_void_p), ('cum', C.c_void_p), ('reward', C.c_void_p),
+                ('terminal', C.c_void_p), ('score', C.c_void_p), ('obs', C.c_void_p), ('start_states', C.c_void_p),
+                ('start_cum', C.c_void_p)]
 
 
 class IgemmOperand(C.Structure):
@@ -237,6 +245,16 @@ _SIGNATURES = {
     'pfa_frames_send': (C.c_int, [P, C.POINTER(SynthConfig), P, P, P, P, P, P, P]),
     'pfa_synth_episode_stats': (C.c_int, [P, C.POINTER(SynthConfig), P, C.c_int32, P]),
     'pfa_synth_last_infos': (C.c_int, [P, C.POINTER(SynthConfig), P, P, P, P, P]),
+    'pfa_tabular_state_bytes': (C.c_size_t, [C.POINTER(TabularConfig)]),
+    'pfa_tabular_async_reset': (C.c_int, [P, C.POINTER(TabularConfig), P, P, P, P, P, P]),
+    'pfa_tabular_send': (C.c_int, [P, C.POINTER(TabularConfig), P, P, P, P, P, P, P]),
+    'pfa_tabular_episode_stats': (C.c_int, [P, C.POINTER(TabularConfig), P, C.c_int32, P]),
+    'pfa_tabular_last_infos': (C.c_int, [P, C.POINTER(TabularConfig), P, P, P, P, P]),
+    'pfa_tabular_debug_states': (C.c_int, [P, C.POINTER(TabularConfig), P, P]),
+    'pfa_rollout_mlp_tabular': (C.c_int, [P, C.POINTER(TabularConfig), P, C.POINTER(MlpDims), C.POINTER(Experience), P, C.POINTER(NoiseKey),
+                                          C.c_int64, P, P, P, P, P, P]),
+    'pfa_rollout_lstm_tabular': (C.c_int, [P, C.POINTER(TabularConfig), P, C.POINTER(MlpDims), P, P, P, C.POINTER(Experience),
+                                           P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P, P]),
     'pfa_multiagent_episode_stats': (C.c_int, [P, C.c_int32, P, C.c_int32, P]),
     'pfa_nativize_rows': (C.c_int, [P, C.c_int64, C.c_int32, P, C.c_int32, P]),
     'pfa_ppo_workspace_bytes': (C.c_size_t, [C.POINTER(MlpDims), C.c_int64, C.POINTER(PpoHparams)]),

@@ -17,6 +17,7 @@
 #include "philox.hpp"
 #include "sampler.hpp"
 #include "env_adapters.hpp"
+#include "tabular_env.hpp"
 
 namespace pfa {
 
@@ -193,6 +194,7 @@ __global__ void __launch_bounds__(kLstmThreads) rollout_lstm_kernel(typename Env
 }
 
 int check_synth_config(const pfa_synth_config *c);   // synthetic.hip
+int check_tabular_config(const pfa_tabular_config *c);   // tabular.hip
 
 static int check_lstm_dims(const pfa_mlp_dims *d) {
     PFA_REQUIRE(d != nullptr, "lstm: null dims");
@@ -327,4 +329,18 @@ extern "C" int pfa_rollout_lstm_synth(void *state, const pfa_synth_config *cfg, 
                 dims->obs_stride);
     return launch_rollout_lstm<SynthRollEnv>("rollout_lstm_synth", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset, obs,
                                              rewards, terminals, truncations, masks, stream);
+}
+
+extern "C" int pfa_rollout_lstm_tabular(void *state, const pfa_tabular_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                                        const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                                        const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                                        uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    if (int rc = check_lstm_dims(dims)) return rc;
+    if (int rc = check_tabular_config(cfg)) return rc;
+    PFA_REQUIRE(dims->num_actions == cfg->num_actions && dims->num_actions >= 2,
+                "rollout_lstm_tabular: the policy must have one Discrete(%d) head of 2..15 actions (got %d)", cfg->num_actions, dims->num_actions);
+    PFA_REQUIRE(dims->obs_stride == cfg->obs_stride, "rollout_lstm_tabular: env obs_stride %d != policy obs_stride %d", cfg->obs_stride,
+                dims->obs_stride);
+    return launch_rollout_lstm<TabularRollEnv>("rollout_lstm_tabular", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset,
+                                               obs, rewards, terminals, truncations, masks, stream);
 }

@@ -128,7 +128,8 @@ class Engine:
             _lib.check(L.pfa_store_step(C.byref(exp.c), t, N, fp.obs_stride, _lib.ptr(vec.obs_buf), _lib.ptr(vec.rewards),
                                         _lib.ptr(vec.terminals_u8), _lib.ptr(actions), _lib.ptr(logprob), _lib.ptr(value),
                                         stream), 'store_step')
-            vec.ensure_tape(1)
+            if hasattr(vec, 'ensure_tape'):      # (the families with a reset tape; the counter-based ones draw in place)
+                vec.ensure_tape(1)
             vec.device_send(actions)
         vec.sends -= T      # the caller (clean_pufferl.evaluate) accounts for the T sends of a rollout
 

@@ -74,11 +74,13 @@ def make_squared(distance_to_target=3, num_targets=1, **kwargs):
 
 def env_creator(name='squared'):
     """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only; plus pixel_squared, this package's frame
-    rendering of it (the reference has no such name)."""
+    rendering of it, and tabular, the creator of a user-given TabularMDP (the reference has no such names)."""
     if name == 'squared':
         return make_squared
     if name == 'pixel_squared':
         return make_pixel_squared
+    if name == 'tabular':
+        return make_tabular
     raise ValueError('Invalid environment name')
 
 
@@ -912,6 +914,343 @@ class Frames(Synthetic):
     def _k_send(self, actions):
         _lib.check(self.L.pfa_frames_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
                    'send')
+
+
+class TabularMDP:
+    """A finite MDP — or, with equal observation rows for different states, a POMDP — as tables: what `vector.Tabular` runs on the
+    device.  Validated at construction, immutable afterwards (the arrays are read-only copies), hashable by identity.
+
+      next_state [S][A][K] int     outcome k of action a in state s ([S][A]: one outcome each, a deterministic MDP)
+      prob       [S][A][K] float64 outcome probabilities, every (s, a) row summing to 1 within 1e-9 (omitted with K = 1)
+      reward     [S][A][K] float64 (or [S][A], the same for every outcome): the env's Python-float reward, cast to float32 on the
+                                   buffer write and summed as float64 into the episode return (GymnasiumPufferEnv / EpisodeStats)
+      terminal   [S] bool          entering such a state ends the episode
+      obs        [S][D] float32    the row shown in state s, 1 <= D <= 160
+      start      int, or (states[M], prob[M]): the initial-state distribution (no terminal state in it)
+      horizon    int >= 1          the step that makes the episode this long ends it, reported as `terminal` (the reference drops
+                                   truncations and only a terminal triggers the auto-reset)
+      score      [S] float64, optional: infos['score'] = the entry of the state the episode ended in; default: the episode's return
+
+    Limits: S <= 2^20, 1 <= A <= 1024, K <= 8, M <= S.  Every violation is a ValueError naming the field and the number.
+
+    Probabilities become integer thresholds once, here, in float64 — the device kernels and any restatement read THESE integers:
+      cum[s][a][k] = floor(2^32 * (prob[s][a][0] + ... + prob[s][a][k])) clipped to 2^32 - 1, as uint32   (`cum`, `start_cum`)
+      outcome of a 32-bit word = the first k with word < cum[k]; if there is none (word >= cum[K-1], which only rounding makes
+      possible) the last outcome with non-zero probability at this resolution, i.e. the last k whose cum[k] exceeds cum[k-1]
+    — in one expression (`outcome`): the number of k with cum[k] <= min(word, cum[K-1] - 1).  A zero-probability outcome has
+    cum[k] == cum[k-1] and is never drawn; probability 1.0 gives cum = 2^32 - 1 and relies on the fallback for the one word 2^32 - 1.
+    The start distribution is treated the same way."""
+    MAX_STATES, MAX_ACTIONS, MAX_OUTCOMES, MAX_OBS = 1 << 20, 1024, 8, 160
+
+    def __init__(self, next_state, prob=None, reward=0.0, terminal=None, obs=None, start=0, horizon=None, score=None):
+        nxt = np.asarray(next_state)
+        if nxt.ndim == 2:
+            nxt = nxt[:, :, None]
+        if nxt.ndim != 3 or nxt.size == 0:
+            raise ValueError(f'next_state: expected [S][A][K] (or [S][A]), got shape {nxt.shape}')
+        S, A, K = nxt.shape
+        if S > self.MAX_STATES:
+            raise ValueError(f'next_state: {S} states, at most {self.MAX_STATES}')
+        if A > self.MAX_ACTIONS:
+            raise ValueError(f'next_state: {A} actions, at most {self.MAX_ACTIONS}')
+        if K > self.MAX_OUTCOMES:
+            raise ValueError(f'next_state: {K} outcomes per action, at most {self.MAX_OUTCOMES}')
+        if not np.issubdtype(nxt.dtype, np.integer):
+            if not np.all(np.isfinite(nxt)) or np.any(nxt != np.floor(nxt)):
+                raise ValueError('next_state: entries must be finite integers')
+        bad = (nxt < 0) | (nxt >= S)
+        if bad.any():
+            raise ValueError(f'next_state: index {int(nxt[bad][0])} at {tuple(int(i) for i in np.argwhere(bad)[0])} outside [0, {S})')
+        nxt = nxt.astype(np.int32)
+
+        if prob is None:
+            if K != 1:
+                raise ValueError(f'prob: required with {K} outcomes per action')
+            pr = np.ones((S, A, 1), np.float64)
+        else:
+            pr = np.asarray(prob, np.float64)
+            if pr.ndim == 2:
+                pr = pr[:, :, None]
+            if pr.shape != (S, A, K):
+                raise ValueError(f'prob: shape {pr.shape}, expected {(S, A, K)}')
+        if not np.all(np.isfinite(pr)):
+            raise ValueError('prob: non-finite value')
+        if (pr < 0).any():
+            raise ValueError(f'prob: negative probability {float(pr[pr < 0][0])} at {tuple(int(i) for i in np.argwhere(pr < 0)[0])}')
+        csum = np.cumsum(pr, axis=2)
+        off = np.abs(csum[:, :, -1] - 1.0) > 1e-9
+        if off.any():
+            s_, a_ = (int(i) for i in np.argwhere(off)[0])
+            raise ValueError(f'prob: row (state {s_}, action {a_}) sums to {float(csum[s_, a_, -1])!r}, not 1')
+
+        rw = np.asarray(reward, np.float64)
+        if rw.shape == (S, A):
+            rw = rw[:, :, None]
+        if rw.shape not in ((), (S, A, 1), (S, A, K)):
+            raise ValueError(f'reward: shape {rw.shape}, expected {(S, A, K)} or {(S, A)}')
+        rw = np.broadcast_to(rw, (S, A, K))
+        if not np.all(np.isfinite(rw)):
+            raise ValueError('reward: non-finite value')
+
+        term = np.zeros(S, bool) if terminal is None else np.asarray(terminal)
+        if term.shape != (S,):
+            raise ValueError(f'terminal: shape {term.shape}, expected {(S,)}')
+        term = term.astype(bool)
+
+        if obs is None:
+            raise ValueError('obs: required, [S][D] float32')
+        ob = np.asarray(obs, np.float32)
+        if ob.ndim == 1:
+            ob = ob[:, None]
+        if ob.ndim != 2 or ob.shape[0] != S:
+            raise ValueError(f'obs: shape {ob.shape}, expected ({S}, D)')
+        D = ob.shape[1]
+        if not 1 <= D <= self.MAX_OBS:
+            raise ValueError(f'obs: rows of {D} values, the device rows hold 1..{self.MAX_OBS}')
+        if not np.all(np.isfinite(ob)):
+            raise ValueError('obs: non-finite value')
+
+        if np.ndim(start) == 0:
+            st_states, st_prob = np.asarray([start]), np.ones(1, np.float64)
+        else:
+            try:
+                st_states, st_prob = start
+            except (TypeError, ValueError):
+                raise ValueError('start: expected a state index or (states[M], prob[M])') from None
+            st_states, st_prob = np.asarray(st_states), np.asarray(st_prob, np.float64)
+        if st_states.ndim != 1 or st_states.shape != st_prob.shape or st_states.size == 0:
+            raise ValueError(f'start: states of shape {st_states.shape} and prob of shape {st_prob.shape}, expected two [M] arrays')
+        M = st_states.size
+        if M > S:
+            raise ValueError(f'start: {M} entries for {S} states')
+        if not np.all(np.isfinite(st_prob)) or not np.all(np.isfinite(st_states.astype(np.float64))):
+            raise ValueError('start: non-finite value')
+        if np.any(st_states != np.floor(st_states)) or (st_states < 0).any() or (st_states >= S).any():
+            badv = st_states[(st_states != np.floor(st_states)) | (st_states < 0) | (st_states >= S)][0]
+            raise ValueError(f'start: state {badv} outside [0, {S})')
+        st_states = st_states.astype(np.int32)
+        if (st_prob < 0).any():
+            raise ValueError(f'start: negative probability {float(st_prob[st_prob < 0][0])}')
+        st_csum = np.cumsum(st_prob)
+        if abs(st_csum[-1] - 1.0) > 1e-9:
+            raise ValueError(f'start: probabilities sum to {float(st_csum[-1])!r}, not 1')
+        if term[st_states].any():
+            raise ValueError(f'start: state {int(st_states[term[st_states]][0])} is terminal')
+
+        if horizon is None or int(horizon) != horizon or int(horizon) < 1 or int(horizon) >= 2 ** 31:
+            raise ValueError(f'horizon: {horizon!r}, expected an integer >= 1')
+
+        sc = None
+        if score is not None:
+            sc = np.asarray(score, np.float64)
+            if sc.shape != (S,):
+                raise ValueError(f'score: shape {sc.shape}, expected {(S,)}')
+            if not np.all(np.isfinite(sc)):
+                raise ValueError('score: non-finite value')
+
+        def frozen(a):
+            a = np.array(a, copy=True, order='C')
+            a.setflags(write=False)
+            return a
+        d = self.__dict__
+        d['num_states'], d['num_actions'], d['num_outcomes'], d['num_starts'], d['obs_dim'] = S, A, K, M, D
+        d['next_state'], d['prob'], d['reward'], d['terminal'], d['obs'] = frozen(nxt), frozen(pr), frozen(rw), frozen(term), frozen(ob)
+        d['start_states'], d['start_prob'], d['horizon'] = frozen(st_states), frozen(st_prob), int(horizon)
+        d['score'] = None if sc is None else frozen(sc)
+        d['cum'], d['start_cum'] = frozen(self.thresholds(csum)), frozen(self.thresholds(st_csum))
+
+    def __setattr__(self, name, value):
+        raise AttributeError('TabularMDP is immutable')
+
+    __delattr__ = __setattr__
+
+    @staticmethod
+    def thresholds(cumulative):
+        """floor(2^32 * cumulative probability) clipped to 2^32 - 1, as uint32 (float64 arithmetic; the product is exact)."""
+        return np.minimum(np.floor(np.asarray(cumulative, np.float64) * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+    @staticmethod
+    def outcome(cum, word):
+        """The outcome a 32-bit word selects from one row of thresholds (the rule in the class docstring)."""
+        cum = np.asarray(cum, np.uint32)
+        return int(np.searchsorted(cum, min(int(word), int(cum[-1]) - 1), side='right'))
+
+    @classmethod
+    def gridworld(cls, rows, cols, goal=None, slip=0.0, horizon=None):
+        """rows x cols cells, state = row * cols + col, one-hot observation (D = rows * cols <= 160), actions 0..3 = up / down / left /
+        right; a move off the grid stays.  With slip > 0 a move has three outcomes: as intended with probability 1 - slip, to either
+        side (the two perpendicular directions) with slip / 2 each.  Entering `goal` ((row, col) or a state index; default: the last
+        cell) gives reward 1 and ends the episode; every other step gives 0.  Uniform start over the non-goal cells."""
+        rows, cols = int(rows), int(cols)
+        S = rows * cols
+        if rows < 1 or cols < 1 or S < 2:
+            raise ValueError(f'gridworld: {rows} x {cols} cells, need at least two')
+        g = S - 1 if goal is None else (int(goal[0]) * cols + int(goal[1]) if np.ndim(goal) else int(goal))
+        if not 0 <= g < S or (np.ndim(goal) and not (0 <= goal[0] < rows and 0 <= goal[1] < cols)):
+            raise ValueError(f'gridworld: goal {goal!r} outside the {rows} x {cols} grid')
+        if not 0.0 <= slip <= 1.0:
+            raise ValueError(f'gridworld: slip {slip!r} outside [0, 1]')
+        moves = ((-1, 0), (1, 0), (0, -1), (0, 1))
+        sides = ((2, 3), (2, 3), (0, 1), (0, 1))
+
+        def to(s, m):
+            r, c = divmod(s, cols)
+            r2, c2 = r + moves[m][0], c + moves[m][1]
+            return r2 * cols + c2 if 0 <= r2 < rows and 0 <= c2 < cols else s
+        K = 3 if slip > 0 else 1
+        nxt = np.zeros((S, 4, K), np.int32)
+        for s in range(S):
+            for a in range(4):
+                nxt[s, a, 0] = to(s, a)
+                if K == 3:
+                    nxt[s, a, 1], nxt[s, a, 2] = to(s, sides[a][0]), to(s, sides[a][1])
+        prob = np.broadcast_to(np.array([1.0 - slip, slip / 2, slip / 2]), (S, 4, 3)) if K == 3 else None
+        terminal = np.arange(S) == g
+        starts = np.flatnonzero(~terminal)
+        return cls(nxt, prob, reward=(nxt == g).astype(np.float64), terminal=terminal, obs=np.eye(S, dtype=np.float32),
+                   start=(starts, np.full(starts.size, 1.0 / starts.size)), horizon=4 * (rows + cols) if horizon is None else horizon)
+
+    @classmethod
+    def tmaze(cls, length):
+        """The cue-and-recall task: a cue (0 or 1, equally likely) is shown in the first observation only, then `length - 1` blank
+        corridor cells follow, then a junction; in the corridor either action walks on, at the junction action == cue ends the episode
+        with reward and score 1, the other action with 0.  D = 3: (cue is 0, cue is 1, at the junction); A = 2; an episode takes
+        length + 1 steps.  States: cue c at position p (0 .. length) = c * (length + 1) + p, then the two end states."""
+        length = int(length)
+        if length < 1:
+            raise ValueError(f'tmaze: length {length}, need at least 1')
+        P = length + 1
+        S = 2 * P + 2
+        win, lose = 2 * P, 2 * P + 1
+        nxt = np.zeros((S, 2), np.int32)
+        obs = np.zeros((S, 3), np.float32)
+        for c in (0, 1):
+            for p in range(length):
+                nxt[c * P + p] = c * P + p + 1
+            nxt[c * P + length, c], nxt[c * P + length, 1 - c] = win, lose
+            obs[c * P, c] = 1.0
+            obs[c * P + length, 2] = 1.0
+        nxt[win], nxt[lose] = win, lose
+        terminal = np.zeros(S, bool)
+        terminal[[win, lose]] = True
+        score = np.zeros(S, np.float64)
+        score[win] = 1.0
+        return cls(nxt, reward=(nxt == win).astype(np.float64), terminal=terminal, obs=obs, start=([0, P], [0.5, 0.5]), horizon=P,
+                   score=score)
+
+
+def make_tabular(mdp=None, obs_stride=None, **kwargs):
+    """Env creator token of a user-given `TabularMDP`: vector.make(make_tabular, env_kwargs=dict(mdp=mdp), backend=Tabular, ...).
+    obs_stride: floats per device observation row (default: the narrowest of 16 / 32 / 64 / 96 / 128 that holds the row; 160 for
+    wider rows under the recurrent policy)."""
+    return TabularSpec(mdp)
+
+
+class TabularSpec(_SimpleSpec):
+    """What ``driver_env`` exposes for a TabularMDP: Box(obs.min(), obs.max(), (D,), float32) and Discrete(A)."""
+
+    def __init__(self, mdp):
+        if not isinstance(mdp, TabularMDP):
+            raise APIUsageError(f'make_tabular needs mdp=<vector.TabularMDP> (got {type(mdp).__name__})')
+        super().__init__(float(mdp.obs.min()), float(mdp.obs.max()), mdp.num_actions)
+        self.mdp = mdp
+        self.single_observation_space = spaces.Box(low=float(mdp.obs.min()), high=float(mdp.obs.max()), shape=(mdp.obs_dim,), dtype=np.float32)
+        self.observation_space = self.single_observation_space
+        self.emulated = namespace(observation_dtype=np.dtype(np.float32),
+                                  emulated_observation_dtype=np.dtype((np.float32, (mdp.obs_dim,))))
+
+
+class Tabular(_DeviceVecEnv):
+    """Device-resident vecenv of N copies of one user-given `TabularMDP` (csrc/tabular_env.hpp, csrc/tabular.hip): the tables are
+    uploaded once and walked by the kernels; randomness is counter-based — Philox keyed by (seed, global env, episode, tick) — so there
+    is no tape and envs `env_offset ..` of a larger vecenv are reproduced exactly.  It has a fused rollout kernel for either policy (up
+    to 15 actions); other policy shapes step it through ``device_send``.  Episodes end on different sends in different envs: in
+    info_mode 'sync' every send reads the finished flags back (one small D2H), in 'lazy' none does."""
+    FAMILY = 'tabular'
+    ABI = 'pfa_tabular'
+    SEEDED = True
+    CONFIG_NAME = 'Tabular '
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_tabular'
+
+    def __init__(self, env_creators, env_args, env_kwargs, num_envs, obs_stride=None, **kwargs):
+        self._obs_stride_arg = obs_stride
+        self._mdps = {}
+        super().__init__(env_creators, env_args, env_kwargs, num_envs, **kwargs)
+
+    def _creator_spec(self, creator, args, kwargs):
+        mdp, stride = _creator_kwargs(creator, args, kwargs, ('mdp', 'obs_stride'), (None, None), self.FAMILY)
+        if not isinstance(mdp, TabularMDP):
+            raise APIUsageError(f'make_tabular needs mdp=<vector.TabularMDP> (got {type(mdp).__name__})')
+        self._mdps[id(mdp)] = mdp
+        stride = self._obs_stride_arg if stride is None else stride
+        return id(mdp), (None if stride is None else int(stride))
+
+    def _spec(self, mdp_id, stride):
+        from .cleanrl import KERNEL_STRIDES, RECURRENT_STRIDES
+        mdp = self._mdps[mdp_id]
+        D = mdp.obs_dim
+        if stride is None:
+            if D > KERNEL_STRIDES[-1]:
+                raise APIUsageError(f'observation rows of {D} values: the feed-forward kernels take rows of up to {KERNEL_STRIDES[-1]} floats; '
+                                    f'pass obs_stride={RECURRENT_STRIDES[-1]} (the recurrent policy\'s widest row)')
+            stride = next(s for s in KERNEL_STRIDES if D <= s)
+        elif stride not in RECURRENT_STRIDES or stride < D:
+            raise APIUsageError(f'obs_stride {stride}: must be one of {RECURRENT_STRIDES} and hold the {D} observation values')
+        self.obs_stride = stride
+        return TabularSpec(mdp)
+
+    def _alloc_state(self):
+        import torch
+        mdp, dev = self.driver_env.mdp, self.device
+        self.mdp = mdp
+        self.obs_dim = mdp.obs_dim
+        self.observations = self.obs_buf[:, :self.obs_dim]
+        obs = np.zeros((mdp.num_states, self.obs_stride), np.float32)
+        obs[:, :mdp.obs_dim] = mdp.obs
+
+        def up(a, as_int32=False):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(np.array(a.view(np.int32) if as_int32 else a)).to(dev)
+        # the device tables, kept alive by the vecenv (uint32 thresholds travel as their int32 bit patterns)
+        self.tables = dict(next=up(mdp.next_state), cum=up(mdp.cum, True), reward=up(mdp.reward), terminal=up(mdp.terminal.astype(np.uint8)),
+                           score=None if mdp.score is None else up(mdp.score), obs=up(obs), start_states=up(mdp.start_states),
+                           start_cum=up(mdp.start_cum, True))
+        t = self.tables
+        self.cfg = _lib.TabularConfig(self.num_agents, mdp.num_states, mdp.num_actions, mdp.num_outcomes, mdp.num_starts, mdp.obs_dim,
+                                      self.obs_stride, mdp.horizon, 0, self.env_offset,
+                                      *(None if t[k] is None else t[k].data_ptr()
+                                        for k in ('next', 'cum', 'reward', 'terminal', 'score', 'obs', 'start_states', 'start_cum')))
+        nbytes = self.L.pfa_tabular_state_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise APIUsageError(self.L.pfa_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+
+    def _finishing_send(self, sends):
+        return True         # episodes end on different sends in different envs
+
+    def _k_reset(self, seed):
+        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.cfg.env_offset = int(self.env_offset)
+        _lib.check(self.L.pfa_tabular_async_reset(_lib.ptr(self.state), C.byref(self.cfg), *self._live(), _lib.stream_handle()), 'async_reset')
+
+    def _k_send(self, actions):
+        _lib.check(self.L.pfa_tabular_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
+                   'send')
+
+    def fused_rollout_mlp(self, fp, experience, noise, key, stream):
+        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/tabular.hip)."""
+        _lib.check(self.L.pfa_rollout_mlp_tabular(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
+                                                  C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
+                                                  stream), 'rollout_mlp_tabular')
+        self.sends += experience.horizon
+
+    def debug_states(self):
+        """[N][5] int32: (state, episode, tick, done, ep_length) of every env — test introspection."""
+        import torch
+        out = torch.zeros(self.num_agents, 5, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.pfa_tabular_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), _lib.stream_handle()),
+                   'debug_states')
+        return out.cpu().numpy()
 
 
 def make_bandit(num_actions=10, reward_scale=1, reward_noise=1, **kwargs):
