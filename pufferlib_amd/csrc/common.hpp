@@ -42,6 +42,21 @@ struct ScopedKernelTimer {  // brackets ONE kernel launch with HIP events on its
 
 #define PFA_LAUNCH_CHECK() PFA_CHECK_HIP(hipGetLastError())
 
+// The observation row strides (floats) the tile code is instantiated for, up to `max`: 16, then every multiple of 32.
+inline bool valid_row_stride(int stride, int max) { return (stride == 16 || (stride >= 32 && stride % 32 == 0)) && stride <= max; }
+
+// What every fused rollout entry point requires beside its own env and policy: `name` prefixes the error text.  `buffers` = the
+// entry point's pointers are all there (`exp` among them); `heads` = pfa_mlp_dims.heads of the policy.
+inline int check_rollout_args(const char *name, bool buffers, uint32_t heads, const pfa_experience *exp, const float *noise,
+                              const pfa_noise_key *key) {
+    PFA_REQUIRE(buffers, "%s: null buffer", name);
+    PFA_REQUIRE(heads == 0, "%s: the fused rollout samples one Discrete head", name);
+    PFA_REQUIRE(exp->horizon_T >= 1, "%s: horizon must be >= 1", name);
+    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones, "%s: null experience buffer", name);
+    PFA_REQUIRE(noise || key, "%s: need an explicit noise tensor or a Philox key", name);
+    return 0;
+}
+
 // csrc/dist.cpp: process-wide RCCL communicator (one process per GPU)
 int dist_world();
 bool dist_ready();

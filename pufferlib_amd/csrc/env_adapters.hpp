@@ -1,6 +1,6 @@
 // env_adapters.hpp — one definition of "what one send() does to one env" per device env family, shared by the family's protocol send
 // kernel (env_send_kernel below), the fused recurrent rollout (rollout_lstm_kernel, lstm_fused.hip) and, for the families that have
-// one, the fused MLP rollout.
+// one, the fused MLP rollout (rollout_mlp_env_kernel, rollout_env.hpp; Squared keeps its tuned kernel in rollout.hip).
 //
 // An env adapter is a plain struct that holds the env's state in registers of its owner thread (in the fused rollouts: lane 0 of the
 // env's 16-lane sampling group) and supplies what differs per env family:
@@ -136,6 +136,17 @@ struct SynthRollEnv {
         v.fin[e].last_fin = last_fin;
     }
 };
+
+// Owner thread of the fused rollouts, after store: what the next recv() returns for env e beside its observation row.  (`terminal`
+// arrives as the byte to store: as a bool it comes back from the inliner as a compare the kernels did not have.  The experience-row
+// store has no such helper: every spelling of it moved an s_nop of the Tabular MLP instantiations — docs/lab-notebook.md.)
+__device__ __forceinline__ void store_live(int e, float reward, uint8_t terminal, float *live_rew, uint8_t *live_term,
+                                           uint8_t *live_trunc, uint8_t *live_mask) {
+    live_rew[e] = reward;
+    live_term[e] = terminal;
+    live_trunc[e] = 0;
+    live_mask[e] = 1;
+}
 
 // The protocol send() of a family over its adapter, one thread per env: the thread is the owner and all 16 lanes of its env, `row` is
 // the env's row of the live observation buffer (`stride` floats apart).

@@ -183,10 +183,7 @@ __global__ void __launch_bounds__(kLstmThreads) rollout_lstm_kernel(typename Env
 
     if (owner) {
         env.store(v, e, le, sh);
-        live_rew[e] = reward;
-        live_term[e] = terminal ? 1 : 0;
-        live_trunc[e] = 0;
-        live_mask[e] = 1;
+        store_live(e, reward, terminal ? 1 : 0, live_rew, live_term, live_trunc, live_mask);
     }
     lstm_unstage_obs<DP>(L.xs, live_obs, first, v.n, (size_t)DP);
     store_cstate(cell, first + c, first + c < v.n, cst);
@@ -199,9 +196,7 @@ int check_tabular_config(const pfa_tabular_config *c);   // tabular.hip
 static int check_lstm_dims(const pfa_mlp_dims *d) {
     PFA_REQUIRE(d != nullptr, "lstm: null dims");
     PFA_REQUIRE(d->hidden == kHidden, "lstm: hidden must be %d (got %d)", kHidden, d->hidden);
-    PFA_REQUIRE(d->obs_stride == 16 || d->obs_stride == 32 || d->obs_stride == 64 || d->obs_stride == 96 || d->obs_stride == 128 ||
-                    d->obs_stride == 160,
-                "lstm: obs_stride must be one of 16/32/64/96/128/160 (got %d)", d->obs_stride);
+    PFA_REQUIRE(valid_row_stride(d->obs_stride, 160), "lstm: obs_stride must be one of 16/32/64/96/128/160 (got %d)", d->obs_stride);
     PFA_REQUIRE(d->num_actions >= 1 && d->num_actions <= 15, "lstm: num_actions must be in 1..15 (got %d)", d->num_actions);
     PFA_REQUIRE(d->heads == 0 || heads_count(d->heads, d->num_actions) >= 1, "lstm: head sizes 0x%x do not sum to num_actions %d",
                 d->heads, d->num_actions);
@@ -267,11 +262,9 @@ static int launch_rollout_lstm(const char *name, void *state, const Config *cfg,
                                const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                                const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                                uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    PFA_REQUIRE(state && params && wpack && h && c && exp && obs && rewards && terminals && truncations && masks, "%s: null buffer", name);
-    PFA_REQUIRE(dims->heads == 0, "%s: the fused rollout samples one Discrete head", name);
-    PFA_REQUIRE(exp->horizon_T >= 1, "%s: horizon must be >= 1", name);
-    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones, "%s: null experience buffer", name);
-    PFA_REQUIRE(noise || key, "%s: need an explicit noise tensor or a Philox key", name);
+    if (int rc = check_rollout_args(name, state && params && wpack && h && c && exp && obs && rewards && terminals && truncations && masks,
+                                    dims->heads, exp, noise, key))
+        return rc;
     const typename Env::View v = Env::view(state, *cfg);
     const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
     const unsigned grid = (unsigned)((cfg->num_envs + 15) / 16);

@@ -286,7 +286,7 @@ static int check_shape(bool flat, int hidden, int obs_dim, int obs_stride, int a
     } else {
         PFA_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256 || hidden == 512, "mlp view: hidden %d is not one of 64/128/256/512", hidden);
     }
-    PFA_REQUIRE(obs_stride == 16 || obs_stride == 32 || obs_stride == 64 || (flat && (obs_stride == 96 || obs_stride == 128)),
+    PFA_REQUIRE(valid_row_stride(obs_stride, flat ? 128 : 64),
                 "mlp: obs_stride must be one of %s (got %d)", flat ? "16/32/64/96/128" : "16/32/64", obs_stride);
     PFA_REQUIRE(obs_dim >= 1 && obs_dim <= obs_stride, "mlp: obs_dim %d out of range", obs_dim);
     PFA_REQUIRE(a >= 1 && a <= 15, "mlp: num_actions must be in 1..15 (got %d)", a);
@@ -316,32 +316,14 @@ static int policy_of_view(const pfa_mlp_view *p, TilePolicy *out) {
     return 0;
 }
 
-// DP = observation row stride, KS = forward k-steps: the 7x7 grid's 49 columns need 13 of the 64-float row's 16 (rollout_tile.hpp),
-// MW = hidden tiles per wave (hidden = 64 MW).  `launch` is called with the Tile of the policy's shape.
-template <int DP_, int KS_, int MW_>
-struct Tile {
-    static constexpr int DP = DP_, KS = KS_, MW = MW_;
-};
-template <int MW, class Launch>
-static void dispatch_stride(const TilePolicy &p, Launch launch) {
-    if (p.obs_stride == 64 && p.obs_dim > 48 && p.obs_dim <= 52) return launch(Tile<64, 13, MW>{});
-    switch (p.obs_stride) {
-        case 16: return launch(Tile<16, 4, MW>{});
-        case 32: return launch(Tile<32, 8, MW>{});
-        case 64: return launch(Tile<64, 16, MW>{});
-    }
-    if constexpr (MW == kMW) {   // rows of 96 / 128 floats: the 128-wide form only (check_shape)
-        if (p.obs_stride == 96) return launch(Tile<96, 24, MW>{});
-        return launch(Tile<128, 32, MW>{});
-    }
-}
+// hidden -> MW, then dispatch_stride (rollout_tile.hpp): `launch` is called with the Tile of the policy's shape.
 template <class Launch>
 static void dispatch_tile(const TilePolicy &p, Launch launch) {
     switch (p.pv.hidden) {
-        case 64: return dispatch_stride<1>(p, launch);
-        case 128: return dispatch_stride<2>(p, launch);
-        case 256: return dispatch_stride<4>(p, launch);
-        default: return dispatch_stride<8>(p, launch);
+        case 64: return dispatch_stride<1>(p.obs_stride, p.obs_dim, launch);
+        case 128: return dispatch_stride<2>(p.obs_stride, p.obs_dim, launch);
+        case 256: return dispatch_stride<4>(p.obs_stride, p.obs_dim, launch);
+        default: return dispatch_stride<8>(p.obs_stride, p.obs_dim, launch);
     }
 }
 
@@ -367,13 +349,9 @@ static int launch_forward_sample(const TilePolicy &p, const float *obs, int64_t 
 static int launch_rollout_squared(const TilePolicy &p, void *state, const pfa_squared_config *cfg, const pfa_experience *exp,
                                   const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
                                   uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    PFA_REQUIRE(state && cfg && exp && obs && rewards && terminals && truncations && masks, "rollout: null buffer");
-    PFA_REQUIRE(p.heads == 0, "rollout: the fused rollout samples one Discrete head");
+    if (int rc = check_rollout_args("rollout", state && cfg && exp && obs && rewards && terminals && truncations && masks, p.heads, exp, noise, key))
+        return rc;
     PFA_REQUIRE(cfg->obs_stride == p.obs_stride, "rollout: env obs_stride %d != policy obs_stride %d", cfg->obs_stride, p.obs_stride);
-    PFA_REQUIRE(exp->horizon_T >= 1, "rollout: horizon must be >= 1");
-    PFA_REQUIRE(exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
-                "rollout: null experience buffer");
-    PFA_REQUIRE(noise || key, "rollout: need an explicit noise tensor or a Philox key");
     PFA_REQUIRE(cfg->num_targets <= kMaxTargets, "rollout: too many targets");
     SquaredView v = squared_view(state, *cfg);
     const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;

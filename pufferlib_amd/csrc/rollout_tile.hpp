@@ -1,7 +1,7 @@
 // rollout_tile.hpp — the policy-forward + sampling tile code shared by every rollout kernel of the MLP policy
 // (frameworks/cleanrl.py:60-66 Policy.forward with action=None = models.py:41-62 + cleanrl.py:25-47): the standalone
-// forward (rollout.hip), the fused Squared rollout (rollout.hip) and the fused Stochastic rollout (stochastic.hip) run exactly
-// this code, so the protocol path and every fused rollout give bit-identical numbers.
+// forward (rollout.hip), the fused Squared rollout (rollout.hip) and the env skeleton of the other families (rollout_env.hpp) run
+// exactly this code, so the protocol path and every fused rollout give bit-identical numbers.
 #pragma once
 #include "common.hpp"
 #include "lane_ops.hpp"
@@ -215,6 +215,27 @@ __device__ __forceinline__ LaneSample sample_lanes_heads(const float (*part)[kPa
     const int i = lo * kPartStride + le;
     const float mine = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
     return sample_row16_heads(mine, lo, a, heads, q);
+}
+
+// Host side: the one map from a policy's row shape to the instantiation every rollout-mode kernel of that policy takes.
+// DP = observation row stride, KS = forward k-steps: the 7x7 grid's 49 columns need 13 of the 64-float row's 16 (SliceFrags),
+// MW = hidden tiles per wave (hidden = 64 MW).  `launch` is called with the Tile of the shape.
+template <int DP_, int KS_, int MW_>
+struct Tile {
+    static constexpr int DP = DP_, KS = KS_, MW = MW_;
+};
+template <int MW, class Launch>
+static void dispatch_stride(int obs_stride, int obs_dim, Launch launch) {
+    if (obs_stride == 64 && obs_dim > 48 && obs_dim <= 52) return launch(Tile<64, 13, MW>{});
+    switch (obs_stride) {
+        case 16: return launch(Tile<16, 4, MW>{});
+        case 32: return launch(Tile<32, 8, MW>{});
+        case 64: return launch(Tile<64, 16, MW>{});
+    }
+    if constexpr (MW == kMW) {   // rows of 96 / 128 floats: the 128-wide form only
+        if (obs_stride == 96) return launch(Tile<96, 24, MW>{});
+        return launch(Tile<128, 32, MW>{});
+    }
 }
 
 }  // namespace pfa

@@ -8,11 +8,10 @@
 // cast to f32 by the buffer write (emulation.py:219), terminal when tick == horizon, the next send() is the auto-reset row
 // (reward 0, terminal False; vector.py:147-151).  EpisodeStats: f64 sum of the episode's rewards in order, length, score =
 // the last proximity.  Kernels: async_reset, send (protocol path), episode statistics, and the fused persistent rollout
-// with the MLP policy (same tile code as every other rollout, rollout_tile.hpp; observation row stride 16).
+// with the MLP policy (the env skeleton of rollout_env.hpp over the adapter below; observation row stride 16).
 #include "common.hpp"
-#include "env_adapters.hpp"
 #include "episode_fin.hpp"
-#include "rollout_tile.hpp"
+#include "rollout_env.hpp"
 
 namespace pfa {
 
@@ -101,7 +100,8 @@ __global__ void __launch_bounds__(256) stochastic_reset_kernel(StochasticView v,
     masks[e] = 1;
 }
 
-// The env adapter (env_adapters.hpp): the one definition of a send, for the protocol kernel and the fused rollout below.
+// The env adapter (env_adapters.hpp): the one definition of a send, for the protocol kernel and the fused rollout
+// (rollout_mlp_env_kernel<StochasticRollEnv, 16, 4>, rollout_env.hpp).
 struct StochasticRollEnv {
     using View = StochasticStepView;
     static constexpr bool kRefresh = false;
@@ -130,65 +130,6 @@ struct StochasticRollEnv {
         v.fin[e].last_fin = last_fin;
     }
 };
-
-// Fused persistent rollout, structure of rollout_mlp_squared_kernel (rollout.hip): 16 envs per 4-wave workgroup, env state
-// in registers of the owner lanes, the 16 observation rows in LDS as the MFMA B operand, weights in registers.
-__global__ void __launch_bounds__(kRollThreads) rollout_mlp_stochastic_kernel(StochasticStepView v, const float *params, int a,
-                                                                             pfa_experience ex, const float *noise, uint64_t seed,
-                                                                             uint64_t step0, long long env_offset, float *live_obs,
-                                                                             float *live_rew, uint8_t *live_term, uint8_t *live_trunc,
-                                                                             uint8_t *live_mask) {
-    constexpr int DP = kStoDP;
-    __shared__ float xs[XTile<DP>::kFloats];
-    __shared__ float part[kRollWaves][kPartFloats];
-    const int le = threadIdx.x >> 4, lo = threadIdx.x & 15;
-    const int e = blockIdx.x * 16 + le;
-    const bool env_ok = e < v.n;
-    const bool owner = lo == 0 && env_ok;
-    const int T = ex.horizon_T;
-
-    SliceFrags<DP> w;
-    w.load(params, a);
-    stage_rows<DP>(live_obs, (long long)blockIdx.x * 16, v.n, xs, 16);
-    StochasticRollEnv env;
-    StochasticRollEnv::Shared sh;
-    float reward = 0.0f;
-    bool terminal = false;
-    if (owner) {
-        env.load(v, e, le, sh);
-        reward = live_rew[e];
-        terminal = live_term[e] != 0;
-    }
-    __syncthreads();
-
-    for (int t = 0; t < T; ++t) {
-        unstage_rows<DP>(xs, ex.obs + (size_t)t * DP, (long long)blockIdx.x * 16, v.n, (size_t)T * DP, 16);
-        forward_slice<DP>(w, xs, part);
-        __syncthreads();
-        const float q = env_ok ? noise_lane(noise ? noise + ((size_t)t * v.n + e) * a : nullptr, seed, step0 + t,
-                                            (uint64_t)(env_offset + e), lo, a)
-                               : 1.0f;
-        const LaneSample sm = sample_lanes(part, le, lo, a, q);
-        if (owner) {
-            const size_t row = (size_t)e * T + t;
-            ex.rewards[row] = reward;
-            ex.dones[row] = terminal ? 1.0f : 0.0f;
-            ex.actions[row] = sm.action;
-            ex.logprobs[row] = sm.logprob;
-            ex.values[row] = sm.value;
-            env.step(v, e, le, sh, xs + le * XTile<DP>::XS, sm.action, reward, terminal);
-        }
-        __syncthreads();
-    }
-    if (owner) {
-        env.store(v, e, le, sh);
-        live_rew[e] = reward;
-        live_term[e] = terminal ? 1 : 0;
-        live_trunc[e] = 0;
-        live_mask[e] = 1;
-    }
-    unstage_rows<DP>(xs, live_obs, (long long)blockIdx.x * 16, v.n, (size_t)DP, 16);
-}
 
 }  // namespace pfa
 
@@ -226,20 +167,11 @@ extern "C" int pfa_rollout_mlp_stochastic(void *state, int32_t num_envs, double 
                                           const pfa_mlp_dims *dims, const pfa_experience *exp, const float *noise,
                                           const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
                                           uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    PFA_REQUIRE(state && num_envs >= 1 && horizon >= 1 && params && dims && exp && obs && rewards && terminals && truncations && masks,
-                "rollout_stochastic: bad arguments");
-    PFA_REQUIRE(dims->heads == 0, "rollout_stochastic: the fused rollout samples one Discrete head");
-    PFA_REQUIRE(dims->hidden == kHidden && dims->obs_stride == kStoDP && dims->obs_dim == 1,
-                "rollout_stochastic: the policy must take 1 observation value in rows of 16 floats");
-    PFA_REQUIRE(dims->num_actions >= 2 && dims->num_actions <= 15, "rollout_stochastic: num_actions out of range");
-    PFA_REQUIRE(exp->horizon_T >= 1 && exp->obs && exp->actions && exp->logprobs && exp->values && exp->rewards && exp->dones,
-                "rollout_stochastic: null experience buffer");
-    PFA_REQUIRE(noise || key, "rollout_stochastic: need an explicit noise tensor or a Philox key");
-    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
-    ScopedKernelTimer timer("rollout_mlp_stochastic", (hipStream_t)stream);
-    hipLaunchKernelGGL(rollout_mlp_stochastic_kernel, dim3((unsigned)((num_envs + 15) / 16)), dim3(kRollThreads), 0, (hipStream_t)stream,
-                       stochastic_view(state, num_envs, p, horizon), params, dims->num_actions, *exp, noise, seed, step,
-                       (long long)env_offset, obs, rewards, terminals, truncations, masks);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    PFA_REQUIRE(num_envs >= 1 && horizon >= 1 && dims, "rollout_mlp_stochastic: bad arguments");
+    PFA_REQUIRE(dims->obs_stride == kStoDP && dims->obs_dim == 1,
+                "rollout_mlp_stochastic: the policy must take 1 observation value in rows of 16 floats");
+    PFA_REQUIRE(dims->num_actions >= 2 && dims->num_actions <= 15, "rollout_mlp_stochastic: num_actions out of range");
+    return launch_rollout_mlp<StochasticRollEnv, kStoDP>("rollout_mlp_stochastic", state, stochastic_view(state, num_envs, p, horizon), params,
+                                                         dims, exp, noise, key, env_offset, obs, rewards, terminals, truncations, masks,
+                                                         stream);
 }

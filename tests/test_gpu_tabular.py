@@ -224,7 +224,7 @@ def _both_rollouts(mdp, n, T, recurrent, obs_stride, rollouts=1):
 @pytest.mark.parametrize('stride', [16, 32, 64, 96, 128])
 def test_fused_mlp_rollout_equals_the_stepwise_protocol_path(stride):
     """40 envs (two and a half 16-env tiles) x 32 steps on the slippery 3 x 3 gridworld with horizon 7 — several episode ends and reset
-    rows per env — once per row-stride instantiation of rollout_mlp_tabular_kernel: experience rows, live buffers, device state and
+    rows per env — once per row-stride instantiation of rollout_mlp_env_kernel<TabularRollEnv, DP, KS>: experience rows, live buffers, device state and
     the four last-infos buffers torch.equal; at stride 16 then one train() against the torch-fp32 oracle trainer fed the same rollout."""
     from pufferlib_amd import clean_pufferl
     from pufferlib_amd.vector import TabularMDP
