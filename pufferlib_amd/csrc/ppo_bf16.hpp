@@ -31,7 +31,7 @@
 // launch against this form's 46.5 in a same-box A/B: the landing buffer is one more LDS round trip for the staging pair, and with two
 // workgroups per CU the 2-way conflicts of this layout are not what the launch waits for.
 // The partial a workgroup leaves has the layout of ppo_mlp_grad_kernel<64, 0, 13, false, 3, true, PERM> (NativeLayout<64, 3, true>),
-// so ppo_reduce_kernel / ppo_reduce_adam_kernel and everything behind them are shared.
+// so ppo_reduce_adam_kernel (either form of the step) and everything behind it are shared.
 #pragma once
 #include "common.hpp"
 #include "mlp_tile.hpp"

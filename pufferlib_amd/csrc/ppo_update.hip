@@ -6,7 +6,8 @@
 //           time, fp32 MFMA (v_mfma_f32_16x16x4_f32) for every contraction; the hidden layer never leaves
 //           registers/LDS.  Each workgroup emits one partial flat gradient (+6 loss sums).  MFMA-bound:
 //           352 MFMA x 32 cycles per 16 rows vs 16*obs_stride*4 B of HBM reads.
-// Kernel B  ppo_reduce_kernel     deterministic sum of the workgroup partials -> flat gradient.
+// Kernel B  ppo_reduce_adam_kernel  deterministic sum of the workgroup partials -> flat gradient; by default the same launch goes on
+//           to the clip norm and Adam (ReduceMode), the two-kernel form leaves that to kernel C.
 // Kernel C  adam_clip_kernel      global grad-norm clip + Adam, single workgroup (P ~ 1e4).
 // Advantage normalisation statistics come from adv_stats kernels (fp64 sums, once per update, because the
 // minibatch partition is fixed: no shuffle, clean_pufferl.py:455-457).
@@ -65,7 +66,7 @@ struct GradLds {
 };
 
 // "Native" layout of one workgroup partial: gradients in MFMA C-fragment order (conflict-free LDS reduction and
-// coalesced global traffic); ppo_reduce_kernel undoes the permutation once.
+// coalesced global traffic); ppo_reduce_adam_kernel undoes the permutation once.
 template <int DP, int KTM = DP / 16, bool COL = false>
 struct NativeLayout {
     // only what the instantiation computes travels: KTM k-tiles of dW1 and, with COL, the one trailing column (the 7x7 grid's
@@ -80,7 +81,7 @@ struct NativeLayout {
 };
 
 // One instantiation of ppo_mlp_grad_kernel and everything the host derives from it: what its launch needs, the layout of the
-// partials it writes — which names the reduce kernels that may read them — and its MFMA count.  with_grad_shape (below, in front of
+// partials it writes — which names the reduce kernel that may read them — and its MFMA count.  with_grad_shape (below, in front of
 // the launches) is the table of the shapes that exist and the one place that maps a policy's dimensions to one of them.
 //   KKU  k-steps of the forward that carry data (ceil(obs_dim / 4))        MH   MultiDiscrete heads
 //   KTM / COL  dW1 on MFMA for the first KTM 16-column tiles, COL: + the one trailing column on the VALU (the 7x7 grid's column 48)
@@ -739,7 +740,7 @@ constexpr int kRedSl = 16;   // slices of the partial index per slot
 // instructions of the 4-byte form, the same bytes in flight per workgroup).  The four components are summed separately, each in the
 // order a one-slot lane would: slice sl takes partials sl, sl + 16, ... in sequence; the slices meet in the fixed tree of the tail.
 constexpr int kRedLanes = 16;                       // lanes per slice
-constexpr int kRedThreads = kRedLanes * kRedSl;     // workgroup of both reduce kernels; wave 0 runs the tail, one entry per lane
+constexpr int kRedThreads = kRedLanes * kRedSl;     // workgroup of the reduce kernel; wave 0 runs the tail, one entry per lane
 static_assert(4 * kRedLanes == 64 && kRedThreads >= 128, "64 entries per workgroup; wave 1 writes the padding zeros");
 template <class NL>
 __device__ __forceinline__ void reduce_slices(const float *partials, int nparts, float (*sh)[64], double (*shd)[64]) {
@@ -772,72 +773,6 @@ __device__ __forceinline__ void reduce_slices(const float *partials, int nparts,
 #pragma unroll
     for (int k = 0; k < 4; ++k) shd[sl][4 * l + k] = dacc[k];
 }
-template <int DP, int KTM = DP / 16, bool COL = false, bool PERM = false>
-__global__ void __launch_bounds__(kRedThreads) ppo_reduce_kernel(const float *partials, int nparts, int a, int obs_dim, float *grads,
-                                                                double *norm_partials) {
-    using NL = NativeLayout<DP, KTM, COL>;
-    __shared__ __attribute__((aligned(16))) float sh[kRedSl][64];
-    __shared__ double shd[kRedSl][64];   // the loss-sum slots are carried in f64
-    reduce_slices<NL>(partials, nparts, sh, shd);
-    __syncthreads();
-    const int ql = threadIdx.x & 63, sl = threadIdx.x >> 6;   // from here on a wave is 64 entries: wave 0 the tail, wave 1 the padding
-    const int q = blockIdx.x * 64 + ql;
-    const MlpOffsets off = mlp_offsets(DP, a);
-    if (sl == 1) {
-        // W1 columns no partial slot covers (k-tiles >= KTM past the COL column: observation padding): their gradient is zero by
-        // definition; written here so that the flat gradient is complete whatever the caller's buffer held
-        constexpr int kFirst = 16 * KTM + (COL ? 1 : 0), kPad = DP - kFirst, kDiv = kPad > 0 ? kPad : 1;
-        const int e = blockIdx.x * 64 + ql;
-        if (kPad > 0 && e < kHidden * kPad) grads[off.w1 + (e / kDiv) * DP + kFirst + e % kDiv] = 0.0f;
-    }
-    if (sl != 0) return;
-    float s = 0.0f;
-    int p = -1;
-    if (q < NL::kCount) {
-        float t[kRedSl];
-#pragma unroll
-        for (int w = 0; w < kRedSl; ++w) t[w] = sh[w][ql];
-#pragma unroll
-        for (int w = kRedSl / 2; w > 0; w >>= 1)
-#pragma unroll
-            for (int x = 0; x < w; ++x) t[x] += t[x + w];   // fixed tree: deterministic, whatever the slice count
-        s = t[0];
-        if (COL && q >= NL::kCol && q < NL::kDw2) {
-            p = off.w1 + (q - NL::kCol) * DP + 16 * KTM;
-            if (16 * KTM >= obs_dim) s = 0.0f;
-        } else if (q < NL::kCol) {
-            const int ln = q & 63, r = (q >> 6) & 3, m = (q >> 8) & (kMT - 1), kt = q >> 11;
-            p = off.w1 + (16 * m + (ln & 15)) * DP + 16 * kt + 4 * (ln >> 4) + r;
-            // columns >= obs_dim are observation padding: their gradient is zero by definition (kernel A2 keeps the bias's 1.0 in the
-            // first of them, which would otherwise put db1 there)
-            if (16 * kt + 4 * (ln >> 4) + r >= obs_dim) s = 0.0f;
-        } else if (q < NL::kDb1) {
-            const int t = q - NL::kDw2, ln = t & 63, r = (t >> 6) & 3, m = t >> 8;
-            const int o = slot_output(PERM, ln & 15), u = 16 * m + 4 * (ln >> 4) + r;
-            if (o < a) p = off.w2 + o * kHidden + u;
-            else if (o == a) p = off.wv + u;
-        } else if (q < NL::kDb2) {
-            p = off.b1 + (q - NL::kDb1);
-        } else if (q < NL::kStats) {
-            const int o = slot_output(PERM, q - NL::kDb2);
-            if (o < a) p = off.b2 + o;
-            else if (o == a) p = off.bv;
-        } else {
-            // loss sums: summed over the partials in f64 and left as (hi, lo) float pairs behind the gradient
-            double t = 0.0;
-#pragma unroll
-            for (int w = 0; w < kRedSl; ++w) t += shd[w][ql];
-            const float hi = (float)t;
-            grads[off.count + 2 * (q - NL::kStats)] = hi;
-            grads[off.count + 2 * (q - NL::kStats) + 1] = (float)(t - (double)hi);
-        }
-        if (p >= 0) grads[p] = s;
-    }
-    double sq = (p >= 0 && p < off.count) ? (double)s * (double)s : 0.0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    if (ql == 0) norm_partials[blockIdx.x] = sq;
-}
 
 // torch.optim.Adam's single-tensor update of one element (clean_pufferl.py:240-244), shared by adam_clip_kernel and the one-launch
 // form.  Every operation is an explicitly rounded one: left to the compiler, `a * b + c` contracts into an fma in one kernel and not
@@ -867,7 +802,7 @@ constexpr int kAdamThreads = 256;   // adam_clip_kernel's workgroup: its norm su
 // Each workgroup owns 64 entries of the fragment-order ("native") gradient layout from the sum of the partials to the parameter
 // update; the global clip norm needs every workgroup's sum of squares, so the launch carries one grid-wide barrier (all of its
 // <= 300 workgroups are co-resident on 256 CUs; waves that only helped summing the partials have exited by then, a waiting
-// workgroup is one wavefront).  What this saves over ppo_reduce_kernel + adam_clip_kernel: a launch (its ramp and the gap in
+// workgroup is one wavefront).  What this saves over the sums alone + adam_clip_kernel: a launch (its ramp and the gap in
 // front of it, ~16 times per update), the round trip of the flat gradient through L2, and — data parallel — the all-reduce as a
 // launch of its own: the exchange is 8-byte {value, sequence} stores into the peers' memory and a spin on the local copy
 // (p2p_ll.hpp), placed between the partial sum and the norm.  Arithmetic and summation order are those of the two-kernel form
@@ -892,9 +827,19 @@ struct AdamArgs {
     const double *log_ev4;
     double *log_out10;
 };
-template <int DP, int KTM, bool COL, bool PERM, bool DIST>
+// Kernel B alone (the two-kernel form: pfa_ppo_mlp_grad, then adam_clip_kernel) is the SAME text: ReduceMode::kSums ends behind the
+// workgroup's piece of sum(g^2), left in norm_partials, so both forms share the summation and the slot -> parameter map by construction.
+// The arguments behind `grads` follow the mode: kSums takes only where its piece goes, the Adam modes keep the kernarg layout they had.
+enum class ReduceMode { kSums, kAdam, kAdamDist };   // the sums alone / + norm hand-off and Adam / + the data-parallel exchange
+struct NormPieces { double *norm_partials; };        // [workgroups of the launch]
+struct NoArg {};
+template <ReduceMode MODE, class T, class SUMS = NoArg>
+using reduce_arg = std::conditional_t<MODE == ReduceMode::kSums, SUMS, T>;
+template <int DP, int KTM, bool COL, bool PERM, ReduceMode MODE>
 __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const float *partials, int nparts, int a, int obs_dim, float *grads,
-                                                                     GridWords gw, AdamArgs ad, LlArgs ll) {
+                                                                     reduce_arg<MODE, GridWords, NormPieces> gw, reduce_arg<MODE, AdamArgs> ad,
+                                                                     reduce_arg<MODE, LlArgs> ll) {
+    constexpr bool ADAM = MODE != ReduceMode::kSums, DIST = MODE == ReduceMode::kAdamDist;
     using NL = NativeLayout<DP, KTM, COL>;
     __shared__ __attribute__((aligned(16))) float sh[kRedSl][64];
     __shared__ double shd[kRedSl][64];   // the loss-sum slots are carried in f64
@@ -912,7 +857,9 @@ __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const floa
     PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 1);   // this wave's partial loads landed and summed
     __syncthreads();
     const MlpOffsets off = mlp_offsets(DP, a);
-    if (sl == 1) {   // observation-padding columns of W1 no partial slot covers: gradient zero by definition (see ppo_reduce_kernel)
+    if (sl == 1) {
+        // W1 columns no partial slot covers (k-tiles >= KTM past the COL column: observation padding): their gradient is zero by
+        // definition; written here so that the flat gradient is complete whatever the caller's buffer held
         constexpr int kFirst = 16 * KTM + (COL ? 1 : 0), kPad = DP - kFirst, kDiv = kPad > 0 ? kPad : 1;
         const int e = blockIdx.x * 64 + ql;
         if (kPad > 0 && e < kHidden * kPad) grads[off.w1 + (e / kDiv) * DP + kFirst + e % kDiv] = 0.0f;
@@ -928,7 +875,7 @@ __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const floa
 #pragma unroll
         for (int w = kRedSl / 2; w > 0; w >>= 1)
 #pragma unroll
-            for (int x = 0; x < w; ++x) t[x] += t[x + w];
+            for (int x = 0; x < w; ++x) t[x] += t[x + w];   // fixed tree: deterministic, whatever the slice count
         s = t[0];
         if (COL && q >= NL::kCol && q < NL::kDw2) {
             p = off.w1 + (q - NL::kCol) * DP + 16 * KTM;
@@ -936,6 +883,8 @@ __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const floa
         } else if (q < NL::kCol) {
             const int ln = q & 63, r = (q >> 6) & 3, m = (q >> 8) & (kMT - 1), kt = q >> 11;
             p = off.w1 + (16 * m + (ln & 15)) * DP + 16 * kt + 4 * (ln >> 4) + r;
+            // columns >= obs_dim are observation padding: their gradient is zero by definition (kernel A2 keeps the bias's 1.0 in the
+            // first of them, which would otherwise put db1 there)
             if (16 * kt + 4 * (ln >> 4) + r >= obs_dim) s = 0.0f;
         } else if (q < NL::kDb1) {
             const int t2 = q - NL::kDw2, ln = t2 & 63, r = (t2 >> 6) & 3, m = t2 >> 8;
@@ -949,20 +898,23 @@ __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const floa
             if (o < a) p = off.b2 + o;
             else if (o == a) p = off.bv;
         } else {
+            // loss sums: summed over the partials in f64 and left as (hi, lo) float pairs behind the gradient
             double t2 = 0.0;
 #pragma unroll
             for (int w = 0; w < kRedSl; ++w) t2 += shd[w][ql];
-            hi = (float)t2;                       // the (hi, lo) float pair of the f64 sum, as the two-kernel form leaves it
+            hi = (float)t2;
             lo = (float)(t2 - (double)hi);
         }
     }
     PFA_HSTAMP(kHandoffReduceRow + blockIdx.x, 2);   // past the barrier and the tree: this entry's sum is known
     // this entry's parameter and moments: in flight across the exchange and the barrier
     float p_i = 0.0f, m_i = 0.0f, v_i = 0.0f;
-    if (p >= 0) {
-        p_i = ad.params[p];
-        m_i = ad.exp_avg[p];
-        v_i = ad.exp_avg_sq[p];
+    if constexpr (ADAM) {
+        if (p >= 0) {
+            p_i = ad.params[p];
+            m_i = ad.exp_avg[p];
+            v_i = ad.exp_avg_sq[p];
+        }
     }
     if constexpr (DIST) {   // one hop: my entry into every peer's memory, theirs out of mine, summed in rank order
         if (p >= 0) ll_push(ll, (unsigned)q, s);
@@ -986,93 +938,97 @@ __global__ void __launch_bounds__(kRedThreads) ppo_reduce_adam_kernel(const floa
     double sq = (p >= 0 && p < off.count) ? (double)s * (double)s : 0.0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    // ---- grid-wide hand-off: publish this workgroup's piece of sum(g^2), collect everyone's ----
-    if (ql < 2) {
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(sq);
-        const unsigned half = ql == 0 ? (unsigned)bits : (unsigned)(bits >> 32);
-        __hip_atomic_store(gw.words + 2 * blockIdx.x + ql, ((unsigned long long)gw.gen << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 3);   // norm word published (and the entry's gradient, parameter and moments here)
-    if constexpr (DIST) {   // the ranks' status words ride the exchange: this workgroup's norm piece is out, nobody waits for this lane
-        if (status_lane) ll_status_wait(ll, status_mine);
-    }
-    // the norm in adam_clip_kernel's order: 256 strided partial sums, a butterfly per 64, then the four in order
-    const int npart = (int)gridDim.x;
-    double tot = 0.0;
-    // Lane ql collects the pieces of workgroups 64k + ql, k = 0 .. kPolls-1 (piece 64k + ql is term k / 4 of strided sum w = k % 4).
-    // Every poll is an agent-scope load the CU's caches cannot serve, a round trip of its own: all of a lane's polls are requested
-    // before the first is looked at, and a round re-requests only the words that do not show this launch's generation yet.
-    constexpr int kPolls = ((NL::kCount + 63) / 64 + 63) / 64;   // the launch has (kCount + 63) / 64 workgroups (GradShape::kReduceGrid)
-    unsigned long long w0[kPolls], w1[kPolls];
-    unsigned pending = 0;
+    if constexpr (!ADAM) {   // the two-kernel form: adam_clip_kernel sums the pieces, in the order the hand-off below restates
+        if (ql == 0) gw.norm_partials[blockIdx.x] = sq;
+    } else {
+        // ---- grid-wide hand-off: publish this workgroup's piece of sum(g^2), collect everyone's ----
+        if (ql < 2) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(sq);
+            const unsigned half = ql == 0 ? (unsigned)bits : (unsigned)(bits >> 32);
+            __hip_atomic_store(gw.words + 2 * blockIdx.x + ql, ((unsigned long long)gw.gen << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 3);   // norm word published (and the entry's gradient, parameter and moments here)
+        if constexpr (DIST) {   // the ranks' status words ride the exchange: this workgroup's norm piece is out, nobody waits for this lane
+            if (status_lane) ll_status_wait(ll, status_mine);
+        }
+        // the norm in adam_clip_kernel's order: 256 strided partial sums, a butterfly per 64, then the four in order
+        const int npart = (int)gridDim.x;
+        double tot = 0.0;
+        // Lane ql collects the pieces of workgroups 64k + ql, k = 0 .. kPolls-1 (piece 64k + ql is term k / 4 of strided sum w = k % 4).
+        // Every poll is an agent-scope load the CU's caches cannot serve, a round trip of its own: all of a lane's polls are requested
+        // before the first is looked at, and a round re-requests only the words that do not show this launch's generation yet.
+        constexpr int kPolls = ((NL::kCount + 63) / 64 + 63) / 64;   // the launch has (kCount + 63) / 64 workgroups (GradShape::kReduceGrid)
+        unsigned long long w0[kPolls], w1[kPolls];
+        unsigned pending = 0;
 #pragma unroll
-    for (int k = 0; k < kPolls; ++k)
-        if (64 * k + ql < npart) pending |= 1u << k;
-    {
-        // The wait is bounded (advisor, round 4): the hand-off relies on every workgroup of the launch being resident at once.
-        // The host checks that once per shape (reduce_adam_coresident: occupancy x CUs >= workgroups, else the two-kernel
-        // form runs), but a device shared with other processes or masked down to fewer CUs can still starve a workgroup; then
-        // the wait runs out, the status word is raised (clean_pufferl.train raises) and the norm becomes NaN, which poisons the
-        // parameters instead of hanging the GPU.
-        long long t0 = 0;
-        int spin = 0;
-        while (true) {
+        for (int k = 0; k < kPolls; ++k)
+            if (64 * k + ql < npart) pending |= 1u << k;
+        {
+            // The wait is bounded (advisor, round 4): the hand-off relies on every workgroup of the launch being resident at once.
+            // The host checks that once per shape (reduce_adam_coresident: occupancy x CUs >= workgroups, else the two-kernel
+            // form runs), but a device shared with other processes or masked down to fewer CUs can still starve a workgroup; then
+            // the wait runs out, the status word is raised (clean_pufferl.train raises) and the norm becomes NaN, which poisons the
+            // parameters instead of hanging the GPU.
+            long long t0 = 0;
+            int spin = 0;
+            while (true) {
 #pragma unroll
-            for (int k = 0; k < kPolls; ++k)
-                if (pending >> k & 1) {
-                    w0[k] = __hip_atomic_load(gw.words + 2 * (64 * k + ql), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    w1[k] = __hip_atomic_load(gw.words + 2 * (64 * k + ql) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int k = 0; k < kPolls; ++k)
+                    if (pending >> k & 1) {
+                        w0[k] = __hip_atomic_load(gw.words + 2 * (64 * k + ql), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        w1[k] = __hip_atomic_load(gw.words + 2 * (64 * k + ql) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+#pragma unroll
+                for (int k = 0; k < kPolls; ++k)
+                    if ((pending >> k & 1) && (unsigned)(w0[k] >> 32) == gw.gen && (unsigned)(w1[k] >> 32) == gw.gen) pending &= ~(1u << k);
+                if (pending == 0) break;
+                __builtin_amdgcn_s_sleep(1);
+                if ((++spin & 255) == 0) {
+                    const long long now = (long long)wall_clock64();
+                    if (t0 == 0) t0 = now;
+                    else if (now - t0 > gw.timeout_ticks) break;
                 }
+            }
+            if (pending != 0) __hip_atomic_store(gw.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
 #pragma unroll
-            for (int k = 0; k < kPolls; ++k)
-                if ((pending >> k & 1) && (unsigned)(w0[k] >> 32) == gw.gen && (unsigned)(w1[k] >> 32) == gw.gen) pending &= ~(1u << k);
-            if (pending == 0) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spin & 255) == 0) {
-                const long long now = (long long)wall_clock64();
-                if (t0 == 0) t0 = now;
-                else if (now - t0 > gw.timeout_ticks) break;
+        for (int w = 0; w < kAdamThreads / 64; ++w) {
+            double ss = 0.0;
+#pragma unroll
+            for (int k = w; k < kPolls; k += kAdamThreads / 64)
+                if (64 * k + ql < npart) ss += __longlong_as_double((long long)(((w1[k] & 0xffffffffull) << 32) | (w0[k] & 0xffffffffull)));
+            if (pending != 0) ss = __builtin_nan("");   // the wait ran out on this lane: the butterfly carries the NaN to every lane
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+            tot += ss;
+        }
+        PFA_HSTAMP(kHandoffReduceRow + blockIdx.x, 4);   // every workgroup's norm word seen
+        const float clip = clip_factor(tot, ad.max_grad_norm);
+        if (p >= 0) {
+            adam_element(p_i, m_i, v_i, s, clip, ad.neg_step_size, ad.bc2_sqrt, ad.beta1, ad.beta2, ad.eps);
+            ad.params[p] = p_i;
+            ad.exp_avg[p] = m_i;
+            ad.exp_avg_sq[p] = v_i;
+        }
+        if (stat) {
+            const int i = q - NL::kStats;
+            double run = 0.0;
+            if (ad.losses && i < 6) {
+                run = ad.losses[i] + ((double)hi + (double)lo) * ad.loss_scale;
+                ad.losses[i] = run;
+            }
+            if (ad.log_out10) {
+                static_assert(kNumStats == 8, "slots 6 and 7 carry the four explained-variance sums of the report");
+                if (i < 6) {
+                    ad.log_out10[i] = run;
+                } else {
+                    ad.log_out10[6 + 2 * (i - 6)] = ad.log_ev4[2 * (i - 6)];
+                    ad.log_out10[7 + 2 * (i - 6)] = ad.log_ev4[2 * (i - 6) + 1];
+                }
             }
         }
-        if (pending != 0) __hip_atomic_store(gw.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 5);   // exit: Adam's stores out
     }
-#pragma unroll
-    for (int w = 0; w < kAdamThreads / 64; ++w) {
-        double ss = 0.0;
-#pragma unroll
-        for (int k = w; k < kPolls; k += kAdamThreads / 64)
-            if (64 * k + ql < npart) ss += __longlong_as_double((long long)(((w1[k] & 0xffffffffull) << 32) | (w0[k] & 0xffffffffull)));
-        if (pending != 0) ss = __builtin_nan("");   // the wait ran out on this lane: the butterfly carries the NaN to every lane
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        tot += ss;
-    }
-    PFA_HSTAMP(kHandoffReduceRow + blockIdx.x, 4);   // every workgroup's norm word seen
-    const float clip = clip_factor(tot, ad.max_grad_norm);
-    if (p >= 0) {
-        adam_element(p_i, m_i, v_i, s, clip, ad.neg_step_size, ad.bc2_sqrt, ad.beta1, ad.beta2, ad.eps);
-        ad.params[p] = p_i;
-        ad.exp_avg[p] = m_i;
-        ad.exp_avg_sq[p] = v_i;
-    }
-    if (stat) {
-        const int i = q - NL::kStats;
-        double run = 0.0;
-        if (ad.losses && i < 6) {
-            run = ad.losses[i] + ((double)hi + (double)lo) * ad.loss_scale;
-            ad.losses[i] = run;
-        }
-        if (ad.log_out10) {
-            static_assert(kNumStats == 8, "slots 6 and 7 carry the four explained-variance sums of the report");
-            if (i < 6) {
-                ad.log_out10[i] = run;
-            } else {
-                ad.log_out10[6 + 2 * (i - 6)] = ad.log_ev4[2 * (i - 6)];
-                ad.log_out10[7 + 2 * (i - 6)] = ad.log_ev4[2 * (i - 6) + 1];
-            }
-        }
-    }
-    PFA_HSTAMP_DRAINED(kHandoffReduceRow + blockIdx.x, 5);   // exit: Adam's stores out
 }
 
 // Per-minibatch advantage sums (f64).  grid = (chunks, nmb); deterministic two-stage reduction.
@@ -1144,15 +1100,27 @@ __global__ void __launch_bounds__(256) ev_partial_kernel(const float *adv, const
     }
     if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = sh[threadIdx.x][0];
 }
+__device__ __forceinline__ double ev_sum(const double *partial, int q) {   // sum q of the kEvBlocks partials, in block order
+    double s = 0.0;
+    for (int b = 0; b < kEvBlocks; ++b) s += partial[b * 4 + q];
+    return s;
+}
 // out[0..5] = the six running loss means (f32 -> f64), out[6..9] = the four sums: one D2H copy serves train()'s log line.
-__global__ void ev_final_kernel(const double *partial, const double *losses, double *out10) {
+template <typename F>   // thread q < 10 writes entry q; the four threads that own a sum ask for theirs
+__device__ __forceinline__ void log_pack(const double *losses, F &&sum, double *out10) {
     const int q = threadIdx.x;
     if (q < 6) out10[q] = losses ? losses[q] : 0.0;
-    if (q >= 6 && q < 10) {
-        double s = 0.0;
-        for (int b = 0; b < kEvBlocks; ++b) s += partial[b * 4 + (q - 6)];
-        out10[q] = s;
-    }
+    else if (q < 10) out10[q] = sum(q - 6);
+}
+__global__ void ev_final_kernel(const double *partial, const double *losses, double *out10) {
+    log_pack(losses, [&](int q) { return ev_sum(partial, q); }, out10);
+}
+// The same in two halves (pfa_train_ev_sums / pfa_train_log_pack): out4 = the four sums; out10 from sums that were all-reduced since.
+__global__ void ev_final4_kernel(const double *partial, double *out4) {
+    if (threadIdx.x < 4) out4[threadIdx.x] = ev_sum(partial, threadIdx.x);
+}
+__global__ void log_pack_kernel(const double *losses, const double *ev4, double *out10) {
+    log_pack(losses, [&](int q) { return ev4[q]; }, out10);
 }
 
 // clip_grad_norm_ + torch.optim.Adam (single-tensor path) on the flat parameter vector.
@@ -1175,7 +1143,7 @@ __global__ void __launch_bounds__(kAdamThreads) adam_clip_kernel(float *params, 
         p_i = params[i];
     }
     double ss = 0.0;
-    if (norm_partials) {  // sum(g^2) pieces left by ppo_reduce_kernel (single rank: no all-reduce in between)
+    if (norm_partials) {  // sum(g^2) pieces left by ppo_reduce_adam_kernel<kSums> (single rank: no all-reduce in between)
         for (int i = threadIdx.x; i < n_norm_partials; i += kAdamThreads) ss += norm_partials[i];
         ss *= (double)grad_scale * (double)grad_scale;
     } else {
@@ -1208,21 +1176,22 @@ __global__ void __launch_bounds__(kAdamThreads) adam_clip_kernel(float *params, 
         losses[threadIdx.x] += ((double)loss_sums[2 * threadIdx.x] + (double)loss_sums[2 * threadIdx.x + 1]) * loss_scale;
 }
 
-static int check_update_args(const pfa_experience *ex, int64_t batch_rows, const pfa_mlp_dims *dims,
-                             const pfa_ppo_hparams *hp) {
+static int check_update_args(const pfa_experience *ex, int64_t batch_rows, const pfa_ppo_hparams *hp) {
     PFA_REQUIRE(ex && hp, "ppo: null argument");
     PFA_REQUIRE(hp->num_minibatches >= 1 && hp->bptt_horizon >= 1, "ppo: bad minibatch partition");
     PFA_REQUIRE(batch_rows % hp->num_minibatches == 0, "batch_size must be divisible by minibatch_size");
     const int64_t mbs = batch_rows / hp->num_minibatches;
     PFA_REQUIRE(mbs % hp->bptt_horizon == 0, "minibatch_size must be divisible by bptt_horizon");
-    (void)dims;
     return 0;
 }
 
 // THE TABLE of gradient shapes: every instantiation of ppo_mlp_grad_kernel the library launches, and the one place that maps a policy's
 // dimensions to one of them — f(shape) is called with the GradShape these dimensions run.  Everything that has to agree with the
-// gradient launch (the reduce kernels that read its partials, their grids, the MFMA count) reads it off that shape.  The caller
-// has checked obs_stride (16 / 32 / 64 / 96 / 128).
+// gradient launch (the reduce kernel that reads its partials, its grid, the MFMA count) reads it off that shape.  The caller
+// has checked obs_stride (grad_stride_ok).
+static bool grad_stride_ok(int obs_stride) {   // the row strides the table has shapes for
+    return obs_stride == 16 || obs_stride == 32 || obs_stride == 64 || obs_stride == 96 || obs_stride == 128;
+}
 template <typename F>
 static auto with_grad_shape(const pfa_mlp_dims *dims, F &&f) {
     const bool mh = dims->heads != 0;
@@ -1296,7 +1265,7 @@ extern "C" size_t pfa_ppo_workspace_bytes(const pfa_mlp_dims *dims, int64_t batc
 
 extern "C" int pfa_ppo_adv_stats(const pfa_experience *exp, int64_t batch_rows, const pfa_ppo_hparams *hp, double *stats,
                                  void *workspace, pfa_stream_t stream) {
-    if (int rc = check_update_args(exp, batch_rows, nullptr, hp)) return rc;
+    if (int rc = check_update_args(exp, batch_rows, hp)) return rc;
     PFA_REQUIRE(exp->advantages && stats && workspace, "ppo.adv_stats: null buffer");
     const int64_t mbs = batch_rows / hp->num_minibatches;
     // shares the workspace with pfa_ppo_mlp_grad: stream order keeps the two uses apart in time
@@ -1313,6 +1282,8 @@ extern "C" int pfa_ppo_adv_stats(const pfa_experience *exp, int64_t batch_rows, 
 
 template <class S, int ABL = 0>   // the kernel of a GradShape
 constexpr auto grad_kernel_of = &ppo_mlp_grad_kernel<S::kDP, ABL, S::kKKU, S::kMH, S::kKTM, S::kCol, S::kPerm>;
+template <class S, ReduceMode MODE>   // the reduce kernel that reads its partials (their layout belongs to the shape that wrote them)
+constexpr auto reduce_kernel_of = &ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, MODE>;
 // One launch of a gradient kernel with `lds_bytes` of dynamic LDS.  KERNEL is a template argument, so the once-only attribute call
 // is once per instantiation.
 struct GradLaunch {
@@ -1337,11 +1308,9 @@ static int launch_grad_kernel(const GradLaunch &at, int grid, int threads, size_
 static int launch_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb, const float *params,
                        const pfa_mlp_dims *dims, const pfa_ppo_hparams *hp, const double *adv_stats,
                        int64_t global_mb_rows, float *grads, void *workspace, pfa_stream_t stream, int *grid_out) {
-    if (int rc = check_update_args(exp, batch_rows, dims, hp)) return rc;
+    if (int rc = check_update_args(exp, batch_rows, hp)) return rc;
     PFA_REQUIRE(dims && dims->hidden == kHidden, "ppo.grad: hidden must be %d", kHidden);
-    PFA_REQUIRE(dims->obs_stride == 16 || dims->obs_stride == 32 || dims->obs_stride == 64 || dims->obs_stride == 96 ||
-                    dims->obs_stride == 128,
-                "ppo.grad: obs_stride must be 16/32/64/96/128");
+    PFA_REQUIRE(grad_stride_ok(dims->obs_stride), "ppo.grad: obs_stride must be 16/32/64/96/128");
     PFA_REQUIRE(dims->num_actions >= 1 && dims->num_actions <= 15, "ppo.grad: num_actions must be in 1..15");
     PFA_REQUIRE(dims->heads == 0 || heads_count(dims->heads, dims->num_actions) >= 1, "ppo.grad: head sizes 0x%x do not sum to num_actions %d",
                 dims->heads, dims->num_actions);
@@ -1389,13 +1358,13 @@ extern "C" int pfa_ppo_mlp_grad(const pfa_experience *exp, int64_t batch_rows, i
                                 int64_t global_mb_rows, float *grads, void *workspace, pfa_stream_t stream) {
     int grid = 0;
     if (int rc = launch_grad(exp, batch_rows, mb, params, dims, hp, adv_stats, global_mb_rows, grads, workspace, stream, &grid)) return rc;
-    float *partials = (float *)workspace;
-    double *normp = norm_partials_of(workspace, dims);
+    const float *partials = (const float *)workspace;
+    const NormPieces normp{norm_partials_of(workspace, dims)};
     ScopedKernelTimer timer2("ppo_reduce", (hipStream_t)stream);
-    with_grad_shape(dims, [&](auto s) {   // the layout of the partials belongs to the shape that wrote them
+    with_grad_shape(dims, [&](auto s) {
         using S = decltype(s);
-        hipLaunchKernelGGL((ppo_reduce_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm>), dim3(S::kReduceGrid), dim3(kRedThreads), 0, (hipStream_t)stream,
-                           partials, grid, dims->num_actions, dims->obs_dim, grads, normp);
+        hipLaunchKernelGGL((reduce_kernel_of<S, ReduceMode::kSums>), dim3(S::kReduceGrid), dim3(kRedThreads), 0, (hipStream_t)stream, partials, grid,
+                           dims->num_actions, dims->obs_dim, grads, normp, NoArg{}, NoArg{});
     });
     PFA_LAUNCH_CHECK();
     return 0;
@@ -1406,9 +1375,17 @@ extern "C" int pfa_ppo_mlp_grad_path(const pfa_mlp_dims *dims, int64_t mb_rows) 
 // MFMA instructions per 16-row tile of the instantiation pfa_ppo_mlp_grad dispatches for these dimensions behind one Discrete head
 extern "C" int pfa_ppo_mlp_grad_mfma_per_tile(int32_t obs_dim, int32_t obs_stride, int32_t num_actions) {
     if (num_actions < 1 || num_actions > 15) return 0;
-    if (obs_stride != 16 && obs_stride != 32 && obs_stride != 64 && obs_stride != 96 && obs_stride != 128) return 0;
+    if (!grad_stride_ok(obs_stride)) return 0;
     const pfa_mlp_dims dims{obs_dim, obs_stride, kHidden, num_actions, 0u};
     return with_grad_shape(&dims, [](auto s) { return decltype(s)::kMfmaPerTile; });
+}
+
+// torch.optim.Adam (single tensor) at optimizer step `step`: bias corrections and step size are python floats (f64)
+struct AdamScalars { float neg_step_size, bc2_sqrt; };
+static AdamScalars adam_scalars(float lr, float beta1, float beta2, int64_t step) {
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    return {(float)(-(double)lr / bc1), (float)std::sqrt(bc2)};
 }
 
 extern "C" int pfa_adam_clip_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t count, float lr,
@@ -1417,14 +1394,10 @@ extern "C" int pfa_adam_clip_step(float *params, const float *grads, float *exp_
                                   int32_t n_norm_partials, pfa_stream_t stream) {
     PFA_REQUIRE(params && grads && exp_avg && exp_avg_sq, "adam: null buffer");
     PFA_REQUIRE(count >= 1 && step >= 1, "adam: count and step must be >= 1");
-    // torch.optim.Adam (single tensor): bias corrections and step size are python floats (f64)
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    const float neg_step_size = (float)(-(double)lr / bc1);
-    const float bc2_sqrt = (float)std::sqrt(bc2);
+    const AdamScalars sc = adam_scalars(lr, beta1, beta2, step);
     ScopedKernelTimer timer("adam_clip", (hipStream_t)stream);
     hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)((count + kAdamThreads - 1) / kAdamThreads)), dim3(kAdamThreads), 0,
-                       (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, (long long)count, neg_step_size, bc2_sqrt, beta1,
+                       (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, (long long)count, sc.neg_step_size, sc.bc2_sqrt, beta1,
                        beta2, eps, max_grad_norm, grad_scale, loss_sums, losses, loss_scale, norm_partials, (int)n_norm_partials);
     PFA_LAUNCH_CHECK();
     return 0;
@@ -1487,21 +1460,18 @@ static bool reduce_adam_coresident(const pfa_mlp_dims *dims, bool dist) {
         using S = decltype(s);
         int &c = cache[dist ? 1 : 0][S::kIndex];
         if (!c) {
-            const bool ok = dist ? coresident(ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, true>, S::kReduceGrid)
-                                 : coresident(ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, false>, S::kReduceGrid);
-            c = ok ? 1 : 2;
+            const auto kernel = dist ? reduce_kernel_of<S, ReduceMode::kAdamDist> : reduce_kernel_of<S, ReduceMode::kAdam>;
+            c = coresident(kernel, S::kReduceGrid) ? 1 : 2;
         }
         return c == 1;
     });
 }
-static int launch_reduce_adam(const pfa_mlp_dims *dims, int nmb, int grid, float *params, float *grads, float *exp_avg, float *exp_avg_sq,
+static int launch_reduce_adam(const pfa_mlp_dims *dims, int grid, float *params, float *grads, float *exp_avg, float *exp_avg_sq,
                               float lr, float beta1, float beta2, float eps, int64_t step, float max_grad_norm, double *losses,
                               double loss_scale, void *workspace, const LlArgs *ll, hipStream_t stream, const double *log_ev4 = nullptr,
                               double *log_out10 = nullptr) {
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    AdamArgs ad{params, exp_avg, exp_avg_sq, (float)(-(double)lr / bc1), (float)std::sqrt(bc2), beta1, beta2, eps, max_grad_norm, losses, loss_scale,
-                log_ev4, log_out10};
+    const AdamScalars sc = adam_scalars(lr, beta1, beta2, step);
+    const AdamArgs ad{params, exp_avg, exp_avg_sq, sc.neg_step_size, sc.bc2_sqrt, beta1, beta2, eps, max_grad_norm, losses, loss_scale, log_ev4, log_out10};
     const float *partials = (const float *)workspace;
     static unsigned long long launches = 0;
     unsigned gen = (unsigned)(++launches);
@@ -1511,17 +1481,13 @@ static int launch_reduce_adam(const pfa_mlp_dims *dims, int nmb, int grid, float
     unsigned long long *gwords = grid_words_of(workspace);
     PFA_REQUIRE(gwords, "ppo.train: cannot allocate the grid hand-off words");
     PFA_REQUIRE((size_t)((native_count(dims->obs_stride) + 63) / 64) * 2 * sizeof(unsigned long long) <= kGridWordsBytes, "ppo.train: hand-off words too small");
-    (void)nmb;
     const GridWords gw{gwords, gen, gstatus, grid_timeout_ticks()};
-    const LlArgs none{};
     ScopedKernelTimer timer("ppo_reduce_adam", stream);
-    with_grad_shape(dims, [&](auto s) {   // the layout of the partials belongs to the shape that wrote them
+    with_grad_shape(dims, [&](auto s) {
         using S = decltype(s);
-        const dim3 g(S::kReduceGrid), b(kRedThreads);
-        if (ll) hipLaunchKernelGGL((ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, true>), g, b, 0, stream, partials, grid,
-                                   dims->num_actions, dims->obs_dim, grads, gw, ad, *ll);
-        else hipLaunchKernelGGL((ppo_reduce_adam_kernel<S::kDP, S::kKTM, S::kCol, S::kPerm, false>), g, b, 0, stream, partials, grid,
-                                dims->num_actions, dims->obs_dim, grads, gw, ad, none);
+        const auto kernel = ll ? reduce_kernel_of<S, ReduceMode::kAdamDist> : reduce_kernel_of<S, ReduceMode::kAdam>;
+        hipLaunchKernelGGL(kernel, dim3(S::kReduceGrid), dim3(kRedThreads), 0, stream, partials, grid, dims->num_actions, dims->obs_dim, grads, gw, ad,
+                           ll ? *ll : LlArgs{});
     });
     PFA_LAUNCH_CHECK();
     return 0;
@@ -1547,21 +1513,6 @@ extern "C" int pfa_ppo_grid_reset(void) {
     return was;
 }
 
-extern "C" int pfa_ppo_mlp_train_logged(const pfa_experience *exp, int64_t batch_rows, float *params, const pfa_mlp_dims *dims,
-                                        const pfa_ppo_hparams *hp, const double *adv_stats, float *grads, float *exp_avg,
-                                        float *exp_avg_sq, int64_t opt_step, float lr, float beta1, float beta2, float eps,
-                                        float max_grad_norm, int32_t update_epochs, double *losses, void *workspace,
-                                        int32_t data_parallel, const double *log_ev4, double *log_out10, int32_t *log_packed,
-                                        pfa_stream_t stream);
-extern "C" int pfa_ppo_mlp_train(const pfa_experience *exp, int64_t batch_rows, float *params, const pfa_mlp_dims *dims,
-                                 const pfa_ppo_hparams *hp, const double *adv_stats, float *grads, float *exp_avg,
-                                 float *exp_avg_sq, int64_t opt_step, float lr, float beta1, float beta2, float eps,
-                                 float max_grad_norm, int32_t update_epochs, double *losses, void *workspace,
-                                 int32_t data_parallel, pfa_stream_t stream) {
-    return pfa_ppo_mlp_train_logged(exp, batch_rows, params, dims, hp, adv_stats, grads, exp_avg, exp_avg_sq, opt_step, lr, beta1, beta2, eps,
-                                    max_grad_norm, update_epochs, losses, workspace, data_parallel, nullptr, nullptr, nullptr, stream);
-}
-
 // pfa_ppo_mlp_train + train()'s report: when the update runs in the one-launch form, its LAST reduce + Adam launch also writes
 // log_out10 = { losses[0..5], log_ev4[0..3] } (what pfa_train_log_pack leaves, minus its launch: the report is what the host waits
 // for at the end of train()); *log_packed (host) says whether it did — 0: call pfa_train_log_pack as before (two-kernel form, the
@@ -1574,7 +1525,7 @@ extern "C" int pfa_ppo_mlp_train_logged(const pfa_experience *exp, int64_t batch
                                         pfa_stream_t stream) {
     if (log_packed) *log_packed = 0;
     PFA_REQUIRE(!log_out10 || (log_ev4 && losses), "ppo.train: the report needs the explained-variance sums and the loss accumulator");
-    if (int rc = check_update_args(exp, batch_rows, dims, hp)) return rc;
+    if (int rc = check_update_args(exp, batch_rows, hp)) return rc;
     PFA_REQUIRE(update_epochs >= 0 && opt_step >= 0, "ppo.train: bad epoch / step count");
     PFA_REQUIRE(!data_parallel || dist_ready(), "ppo.train: data_parallel needs pfa_dist_init first");
     const int world = data_parallel ? dist_world() : 1;
@@ -1597,7 +1548,7 @@ extern "C" int pfa_ppo_mlp_train_logged(const pfa_experience *exp, int64_t batch
                 LlArgs ll{};
                 if (fused_dp) ll = p2p_ll_next();
                 const bool last = log_out10 && e == update_epochs - 1 && mb == hp->num_minibatches - 1;
-                if (int rc = launch_reduce_adam(dims, hp->num_minibatches, grid, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+                if (int rc = launch_reduce_adam(dims, grid, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
                                                 opt_step, max_grad_norm, losses, loss_scale, workspace, fused_dp ? &ll : nullptr,
                                                 (hipStream_t)stream, last ? log_ev4 : nullptr, last ? log_out10 : nullptr))
                     return rc;
@@ -1621,6 +1572,14 @@ extern "C" int pfa_ppo_mlp_train_logged(const pfa_experience *exp, int64_t batch
             }
         }
     return 0;
+}
+extern "C" int pfa_ppo_mlp_train(const pfa_experience *exp, int64_t batch_rows, float *params, const pfa_mlp_dims *dims,
+                                 const pfa_ppo_hparams *hp, const double *adv_stats, float *grads, float *exp_avg,
+                                 float *exp_avg_sq, int64_t opt_step, float lr, float beta1, float beta2, float eps,
+                                 float max_grad_norm, int32_t update_epochs, double *losses, void *workspace,
+                                 int32_t data_parallel, pfa_stream_t stream) {
+    return pfa_ppo_mlp_train_logged(exp, batch_rows, params, dims, hp, adv_stats, grads, exp_avg, exp_avg_sq, opt_step, lr, beta1, beta2, eps,
+                                    max_grad_norm, update_epochs, losses, workspace, data_parallel, nullptr, nullptr, nullptr, stream);
 }
 
 #ifdef PFA_BF16_TRACE
@@ -1683,19 +1642,6 @@ extern "C" int pfa_train_log_sums(const pfa_experience *exp, int64_t batch_rows,
 // GAE has run and ride the all-reduce of the advantage sums instead of one of their own at the end:
 //   pfa_train_ev_sums    out4 = sum y_true, sum y_true^2, sum adv, sum adv^2 of this rank's batch
 //   pfa_train_log_pack   out10 = { losses[0..5], ev4[0..3] }  (ev4 = the all-reduced sums)
-__global__ void ev_final4_kernel(const double *partial, double *out4) {
-    const int q = threadIdx.x;
-    if (q < 4) {
-        double s = 0.0;
-        for (int b = 0; b < kEvBlocks; ++b) s += partial[b * 4 + q];
-        out4[q] = s;
-    }
-}
-__global__ void log_pack_kernel(const double *losses, const double *ev4, double *out10) {
-    const int q = threadIdx.x;
-    if (q < 6) out10[q] = losses ? losses[q] : 0.0;
-    else if (q < 10) out10[q] = ev4[q - 6];
-}
 extern "C" int pfa_train_ev_sums(const pfa_experience *exp, int64_t batch_rows, int32_t num_envs, double *out4, void *workspace,
                                  pfa_stream_t stream) {
     PFA_REQUIRE(exp && exp->advantages && exp->values && out4 && workspace, "train_ev_sums: null buffer");

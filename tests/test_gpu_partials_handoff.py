@@ -1,5 +1,5 @@
 """The hand-off of the workgroup partials between the two launches of a PPO optimizer step (csrc/ppo_update.hip): the gradient
-kernel's epilogue stores one partial per workgroup in 16-byte pieces, the reduce kernels load them back in 16-byte pieces, four
+kernel's epilogue stores one partial per workgroup in 16-byte pieces, the reduce kernel loads them back in 16-byte pieces, four
 native slots per lane.  Neither may change a bit of the result: the sum per native slot has a documented order (16 slices of the
 partial index, sequential inside a slice, then a halving tree), restated here in numpy float32 from the partials themselves."""
 import ctypes as C
@@ -16,6 +16,13 @@ H, OUT, NSTATS, MT, SLICES = 128, 16, 8, 8, 16
 SHAPE_7X7 = (49, 64, 8, 0, 4)         # GradShape<64, 13, false, 3, true, true>: trimmed dW1 + the column-48 slots, permuted head rows
 SHAPE_MULTI = (12, 16, 5, 0x23, 4)    # obs_stride 16 behind a MultiDiscrete([3, 2]) head: untrimmed layout
 SHAPE_WIDE = (100, 128, 6, 0, 2)      # 128-float rows: two wavefront pairs, the two-buffer epilogue
+# the remaining reduce layouts (DP, KTM, COL, PERM) of with_grad_shape; every obs_dim leaves padding columns to be zeroed
+SHAPE_32 = (30, 32, 4, 0, 4)          # <32, 2, false, false>
+SHAPE_96 = (90, 96, 7, 0, 2)          # <96, 6, false, false>: two wavefront pairs
+SHAPE_64 = (60, 64, 6, 0, 4)          # <64, 4, false, false>: 64-float rows, untrimmed
+SHAPE_7X7_NATURAL = (49, 64, 13, 0, 4)   # <64, 3, true, false>: more than 11 actions keep the head rows in natural order
+ALL_LAYOUTS = ((SHAPE_7X7, '7x7-perm'), (SHAPE_MULTI, 'stride16-multidiscrete'), (SHAPE_WIDE, 'stride128-two-buffers'), (SHAPE_32, 'stride32'),
+               (SHAPE_96, 'stride96'), (SHAPE_64, 'stride64-untrimmed'), (SHAPE_7X7_NATURAL, '7x7-natural'))
 
 
 def _layout(obs_dim, dp, a, heads):
@@ -147,8 +154,9 @@ def _cases():
     for shape, name in ((SHAPE_7X7, '7x7-perm'), (SHAPE_MULTI, 'stride16-multidiscrete')):
         for grid in (1, 3, 17, 256):
             out.append(pytest.param(shape, grid, id=f'{name}-grid{grid}'))
-    for grid in (3, 17):
-        out.append(pytest.param(SHAPE_WIDE, grid, id=f'stride128-two-buffers-grid{grid}'))
+    for shape, name in ALL_LAYOUTS[2:]:
+        for grid in (3, 17):
+            out.append(pytest.param(shape, grid, id=f'{name}-grid{grid}'))
     return out
 
 
@@ -184,11 +192,12 @@ def test_flat_gradient_is_the_fixed_order_sum_of_the_partials(shape, grid):
 
 
 @pytest.mark.parametrize('grid', [3, 17])
-@pytest.mark.parametrize('shape', [pytest.param(SHAPE_7X7, id='7x7-perm'), pytest.param(SHAPE_MULTI, id='stride16-multidiscrete')])
+@pytest.mark.parametrize('shape', [pytest.param(shape, id=name) for shape, name in ALL_LAYOUTS])
 def test_one_launch_form_equals_the_two_kernel_form_at_small_grids(monkeypatch, shape, grid):
-    """Three optimizer steps through pfa_ppo_mlp_train in the one-launch form (ppo_reduce_adam_kernel) and in the two-kernel form
-    (PFA_FUSED_ADAM=0: ppo_reduce_kernel + adam_clip_kernel; the switch is read at every call): parameters, both moments and the
-    loss sums must be the same bits, with 3 and with 17 partials (the slice tail cuts inside a round of 16)."""
+    """Three optimizer steps through pfa_ppo_mlp_train in the one-launch form (ppo_reduce_adam_kernel through Adam) and in the
+    two-kernel form (PFA_FUSED_ADAM=0: the same kernel's sums-only instantiation + adam_clip_kernel; the switch is read at every
+    call): parameters, both moments and the loss sums must be the same bits at every reduce layout, with 3 and with 17 partials
+    (the slice tail cuts inside a round of 16)."""
     rows = 16 * shape[4] * grid
     runs = []
     for fused in ('1', '0'):

@@ -3,8 +3,8 @@ reduce + Adam launch requests the norm words of all the workgroups it is respons
 the gradient launch request their head biases and advantage sums in front of the table build.  Neither may change a bit:
 
   1. the one-launch step (ppo_reduce_adam_kernel: the grid-wide norm hand-off) against the two-launch form (PFA_FUSED_ADAM=0:
-     ppo_reduce_kernel + adam_clip_kernel, no hand-off at all) after two full updates — parameters, both Adam moments and the six loss
-     sums with array_equal, a fresh process per value, over every number of polls per lane the shape table can produce (2, 3, 4 and 5:
+     the same kernel's sums-only form + adam_clip_kernel, no hand-off at all) after two full updates — parameters, both Adam moments and
+     the six loss sums with array_equal, a fresh process per value, over every number of polls per lane the shape table can produce (2, 3, 4 and 5:
      step_roundtrips_cases.SHAPES; no shape has <= 64 reduce workgroups, i.e. one poll) and batch sizes with one and with several
      tiles per wavefront pair;
   2. the same with rewards scaled until the oracle's gradient norm is far above max_grad_norm (checked on the CPU before the GPU is
