@@ -461,6 +461,44 @@ int pfa_rollout_mlp_tabular(void *state, const pfa_tabular_config *cfg, const fl
                             pfa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CartPole vecenv — classic-control cart-pole (csrc/cartpole_env.hpp): f64 state (x, x_dot, theta, theta_dot), one explicit-Euler
+ * step of tau = 0.02 per send under a force of +-10 (action 1 / any other), reward 1 per step, terminal when |x| > 2.4, |theta| >
+ * 12 degrees or — max_steps > 0 — the episode is max_steps long; the send after it is the auto-reset row, which draws the four
+ * state values as -0.05 + 0.1 * (word * 2^-32) from Philox4x32-10(counter = (env_offset + env, episode, 0, 0), key = (seed lo,
+ * 0x4350 ^ seed hi)).  sin / cos are fixed polynomials and nothing is contracted, so a float64 host walker gives the same bits.
+ * Observation rows are 16 floats: the state as f32 in columns 0..3 (columns 1 and 3 are 0 when velocities == 0), zero behind.
+ * infos' score = the episode's return.  Protocol and live buffers as the other device envs.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t num_envs;
+    int32_t max_steps;      /* >= 0; 0 = no time limit */
+    int32_t velocities;     /* 0: x_dot and theta_dot are hidden from the observation */
+    int32_t reserved;
+    uint64_t seed;
+    int64_t env_offset;     /* global index of local env 0 (sharding) */
+} pfa_cartpole_config;
+size_t pfa_cartpole_state_bytes(const pfa_cartpole_config *cfg);
+int pfa_cartpole_async_reset(void *state, const pfa_cartpole_config *cfg, float *obs, float *rewards, uint8_t *terminals,
+                             uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_cartpole_send(void *state, const pfa_cartpole_config *cfg, const int64_t *actions, float *obs, float *rewards,
+                      uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_cartpole_episode_stats(void *state, const pfa_cartpole_config *cfg, double *out4, int32_t reset, pfa_stream_t stream);
+int pfa_cartpole_last_infos(void *state, const pfa_cartpole_config *cfg, uint8_t *finished, double *episode_return,
+                            int32_t *episode_length, double *score, pfa_stream_t stream);
+/* test introspection: states[e] = {x, x_dot, theta, theta_dot}, counters[e] = {episode, tick, done, ep_length} of env e */
+int pfa_cartpole_debug_states(void *state, const pfa_cartpole_config *cfg, double *states4, int32_t *counters4, pfa_stream_t stream);
+/* clean_pufferl.evaluate's loop for a CartPole vecenv and the MLP policy, one persistent kernel: the flat 128-wide buffer
+ * (dims->obs_stride == 16, dims->obs_dim == 4, dims->num_actions == 2) ... */
+int pfa_rollout_mlp_cartpole(void *state, const pfa_cartpole_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                             const pfa_experience *exp, const float *noise, const pfa_noise_key *key, int64_t env_offset,
+                             float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks,
+                             pfa_stream_t stream);
+/* ... or a pfa_mlp_view of hidden 64 / 128 / 256 / 512 (the same kernel with W1 fragments of that width; same row and head). */
+int pfa_rollout_mlp_view_cartpole(void *state, const pfa_cartpole_config *cfg, const pfa_mlp_view *view, const pfa_experience *exp,
+                                  const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
+                                  uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Structured-observation unpack — replaces pufferlib.pytorch.nativize_tensor
  * (pufferlib/pytorch.py:96-145): flat emulated rows [num_rows][row_bytes] (device, 16-byte aligned) -> one dense tensor
  * per leaf of the observation space, in one launch.  A field is a leaf as pufferlib.pytorch.nativize_dtype
@@ -630,6 +668,11 @@ int pfa_rollout_lstm_tabular(void *state, const pfa_tabular_config *cfg, const f
                              const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                              const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                              uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* ... and over the CartPole vecenv (pfa_cartpole_*): observation rows of 16 floats, one Discrete(2) head. */
+int pfa_rollout_lstm_cartpole(void *state, const pfa_cartpole_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                              const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                              const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                              uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 /* --- the recurrent policy in training mode (csrc/lstm_seq.hip): forward over the `steps` (= bptt_horizon) time steps
  * of a minibatch of `rows` independent segments and back-propagation through time (clean_pufferl.py:186-193, :244).
  * Time-major buffers: obs_tm [steps][rows][obs_stride], xe / dh_heads / dxe [steps][rows][128], gates_act / dgates

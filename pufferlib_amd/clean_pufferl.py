@@ -427,9 +427,9 @@ STEPWISE, FUSED_LSTM, FUSED_MLP = 'stepwise', 'fused recurrent', 'fused MLP'
 def rollout_form(vecenv_class, gen_engine, lstm_engine, mlp_view):
     """Which rollout evaluate() runs for a device vecenv class and the engines create() built: one persistent kernel where the env
     class declares one for the policy kind (ROLLOUT_LSTM, fused_rollout_mlp), else policy step + store + send per step."""
-    if gen_engine:       # GEMM-path policy: its Default(64 / 256 / 512) shapes share the Squared rollout kernel (general.tile_view),
-        #                  whose state layout is Squared's own: exactly that class, not a subclass
-        return FUSED_MLP if mlp_view and vecenv_class is Squared else STEPWISE
+    if gen_engine:       # GEMM-path policy: its Default(64 / 256 / 512) shapes share the rollout kernel of a class that declares the view
+        #                  form (Squared, CartPole); the kernel reads that class's own state layout: exactly the class, not a subclass
+        return FUSED_MLP if mlp_view and vecenv_class.__dict__.get('ROLLOUT_MLP_VIEW', False) else STEPWISE
     if lstm_engine:
         return FUSED_LSTM if vecenv_class.ROLLOUT_LSTM is not None else STEPWISE
     return FUSED_MLP if vecenv_class.fused_rollout_mlp is not None else STEPWISE

@@ -272,61 +272,8 @@ __global__ void __launch_bounds__(256) philox_exp_noise_kernel(float *out, long 
 // with its pfa_mlp_dims (hidden 128; rows of 16 / 32 / 64 / 96 / 128 floats; MultiDiscrete head masks in the standalone forward),
 // and a pfa_mlp_view of a module's own tensors (models.py:24-39 with hidden_size 64 / 128 / 256 / 512 — what
 // environments/classic_control, nethack / nmmo and atari's MLP heads use; rows of 16 / 32 / 64 floats, one Discrete head).  Both
-// resolve to a TilePolicy; one checker, one dispatch and one launcher per kernel serve both.
+// resolve to a TilePolicy (rollout_tile.hpp); one checker, one dispatch and one launcher per kernel serve both.
 // ---------------------------------------------------------------------------------------------
-struct TilePolicy {
-    MlpView pv;
-    int obs_dim, obs_stride;
-    uint32_t heads;
-};
-
-static int check_shape(bool flat, int hidden, int obs_dim, int obs_stride, int a, uint32_t heads) {
-    if (flat) {
-        PFA_REQUIRE(hidden == kHidden, "mlp: hidden must be %d (got %d)", kHidden, hidden);
-    } else {
-        PFA_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256 || hidden == 512, "mlp view: hidden %d is not one of 64/128/256/512", hidden);
-    }
-    PFA_REQUIRE(valid_row_stride(obs_stride, flat ? 128 : 64),
-                "mlp: obs_stride must be one of %s (got %d)", flat ? "16/32/64/96/128" : "16/32/64", obs_stride);
-    PFA_REQUIRE(obs_dim >= 1 && obs_dim <= obs_stride, "mlp: obs_dim %d out of range", obs_dim);
-    PFA_REQUIRE(a >= 1 && a <= 15, "mlp: num_actions must be in 1..15 (got %d)", a);
-    PFA_REQUIRE(heads == 0 || (flat && heads_count(heads, a) >= 1), "mlp: head sizes 0x%x do not sum to num_actions %d", heads, a);
-    return 0;
-}
-static int check_dims(const pfa_mlp_dims *d) {
-    PFA_REQUIRE(d != nullptr, "mlp: null dims");
-    return check_shape(true, d->hidden, d->obs_dim, d->obs_stride, d->num_actions, d->heads);
-}
-static int check_view(const pfa_mlp_view *p) {
-    PFA_REQUIRE(p != nullptr, "mlp view: null");
-    PFA_REQUIRE(p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv, "mlp view: null tensor");
-    PFA_REQUIRE(p->ldw1 >= p->obs_dim, "mlp view: obs_dim %d / ldw1 %d out of range", p->obs_dim, p->ldw1);
-    return check_shape(false, p->hidden, p->obs_dim, p->obs_stride, p->num_actions, 0);
-}
-static int policy_of_flat(const float *params, const pfa_mlp_dims *d, TilePolicy *out) {
-    if (int rc = check_dims(d)) return rc;
-    PFA_REQUIRE(params, "mlp: null parameter buffer");
-    *out = TilePolicy{mlp_view_of_flat(params, d->obs_stride, d->num_actions), d->obs_dim, d->obs_stride, d->heads};
-    return 0;
-}
-static int policy_of_view(const pfa_mlp_view *p, TilePolicy *out) {
-    if (int rc = check_view(p)) return rc;
-    *out = TilePolicy{MlpView{p->w1, p->ldw1, p->obs_dim, p->b1, p->w2, p->b2, p->wv, p->bv, p->num_actions, p->hidden}, p->obs_dim,
-                      p->obs_stride, 0};
-    return 0;
-}
-
-// hidden -> MW, then dispatch_stride (rollout_tile.hpp): `launch` is called with the Tile of the policy's shape.
-template <class Launch>
-static void dispatch_tile(const TilePolicy &p, Launch launch) {
-    switch (p.pv.hidden) {
-        case 64: return dispatch_stride<1>(p.obs_stride, p.obs_dim, launch);
-        case 128: return dispatch_stride<2>(p.obs_stride, p.obs_dim, launch);
-        case 256: return dispatch_stride<4>(p.obs_stride, p.obs_dim, launch);
-        default: return dispatch_stride<8>(p.obs_stride, p.obs_dim, launch);
-    }
-}
-
 static int launch_forward_sample(const TilePolicy &p, const float *obs, int64_t rows, const float *noise, const pfa_noise_key *key,
                                  int64_t row_offset, int64_t *actions, float *logprob, float *entropy, float *value, pfa_stream_t stream) {
     PFA_REQUIRE(rows >= 0, "mlp.forward: negative rows");

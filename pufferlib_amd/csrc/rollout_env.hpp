@@ -9,9 +9,10 @@ namespace pfa {
 
 // 16 envs per 4-wave workgroup for all T steps, env state in registers of the owner lanes, the 16 observation rows in LDS as the MFMA
 // B operand, weights in registers.  KS as the standalone forward chooses it for the policy's shape (dispatch_stride), so that the
-// protocol path and this kernel run the same products.
-template <class Env, int DP, int KS>
-__global__ void __launch_bounds__(kRollThreads) rollout_mlp_env_kernel(typename Env::View v, const float *params, int a, pfa_experience ex,
+// protocol path and this kernel run the same products.  Params = where the weights live: the flat 128-wide buffer (MW = kMW), or an
+// MlpView of any of the four widths (hidden = 64 MW) — the fragments are loaded once, the rest of the kernel does not see the form.
+template <class Env, int DP, int KS, int MW = kMW, class Params = const float *>
+__global__ void __launch_bounds__(kRollThreads) rollout_mlp_env_kernel(typename Env::View v, Params params, int a, pfa_experience ex,
                                                                       const float *noise, uint64_t seed, uint64_t step0,
                                                                       long long env_offset, float *live_obs, float *live_rew,
                                                                       uint8_t *live_term, uint8_t *live_trunc, uint8_t *live_mask) {
@@ -25,8 +26,12 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_env_kernel(typename 
     const bool owner = lo == 0 && env_ok;
     const int T = ex.horizon_T;
 
-    SliceFrags<DP, KS> w;
-    w.load(params, a);
+    SliceFrags<DP, KS, MW> w;
+    if constexpr (std::is_pointer_v<Params>) {
+        w.load(params, a);
+    } else {
+        w.load(params);
+    }
     stage_rows<DP>(live_obs, (long long)blockIdx.x * 16, v.n, xs, 16);
     Env env;
     float reward = 0.0f;
@@ -40,7 +45,7 @@ __global__ void __launch_bounds__(kRollThreads) rollout_mlp_env_kernel(typename 
 
     for (int t = 0; t < T; ++t) {
         unstage_rows<DP>(xs, ex.obs + (size_t)t * DP, (long long)blockIdx.x * 16, v.n, (size_t)T * DP, 16);
-        forward_slice<DP, KS>(w, xs, part);
+        forward_slice<DP, KS, MW>(w, xs, part);
         __syncthreads();
         const float q = env_ok ? noise_lane(noise ? noise + ((size_t)t * v.n + e) * a : nullptr, seed, step0 + t,
                                             (uint64_t)(env_offset + e), lo, a)
@@ -91,6 +96,26 @@ static int launch_rollout_mlp(const char *name, void *state, const typename Env:
     } else {
         dispatch_stride<kMW>(dims->obs_stride, dims->obs_dim, launch);
     }
+    PFA_LAUNCH_CHECK();
+    return 0;
+}
+
+// The view form of the same: a policy of any tile width (TilePolicy, rollout_tile.hpp: policy_of_view, or policy_of_flat for the flat
+// 128-wide buffer), launched through dispatch_tile — the hidden -> MW map of the standalone forward, so that the protocol path and
+// this kernel take the same Tile.  The entry point has checked its env and `p` against it.  kOnlyDP as above.
+template <class Env, int kOnlyDP = 0>
+static int launch_rollout_mlp_view(const char *name, void *state, const typename Env::View &v, const TilePolicy &p, const pfa_experience *exp,
+                                   const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
+                                   uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    if (int rc = check_rollout_args(name, state && exp && obs && rewards && terminals && truncations && masks, p.heads, exp, noise, key)) return rc;
+    const uint64_t seed = key ? key->seed : 0, step = key ? key->step : 0;
+    ScopedKernelTimer timer(name, (hipStream_t)stream);
+    dispatch_tile<kOnlyDP>(p, [&](auto tile) {
+        using T = decltype(tile);
+        hipLaunchKernelGGL((rollout_mlp_env_kernel<Env, T::DP, T::KS, T::MW, MlpView>), dim3((unsigned)((v.n + 15) / 16)), dim3(kRollThreads), 0,
+                           (hipStream_t)stream, v, p.pv, p.pv.a, *exp, noise, seed, step, (long long)env_offset, obs, rewards, terminals,
+                           truncations, masks);
+    });
     PFA_LAUNCH_CHECK();
     return 0;
 }

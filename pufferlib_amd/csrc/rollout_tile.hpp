@@ -3,6 +3,8 @@
 // forward (rollout.hip), the fused Squared rollout (rollout.hip) and the env skeleton of the other families (rollout_env.hpp) run
 // exactly this code, so the protocol path and every fused rollout give bit-identical numbers.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "lane_ops.hpp"
 #include "mlp_tile.hpp"
@@ -235,6 +237,72 @@ static void dispatch_stride(int obs_stride, int obs_dim, Launch launch) {
     if constexpr (MW == kMW) {   // rows of 96 / 128 floats: the 128-wide form only
         if (obs_stride == 96) return launch(Tile<96, 24, MW>{});
         return launch(Tile<128, 32, MW>{});
+    }
+}
+
+// A Default policy as the tile kernels take it, from either descriptor form: the flat parameter buffer of the 128-wide family with
+// its pfa_mlp_dims, or a pfa_mlp_view of a module's own tensors (hidden 64 / 128 / 256 / 512).  One checker per form; the standalone
+// forward, the Squared rollout (rollout.hip) and the view form of the env skeleton (rollout_env.hpp) all launch through dispatch_tile.
+struct TilePolicy {
+    MlpView pv;
+    int obs_dim, obs_stride;
+    uint32_t heads;
+};
+
+inline int check_shape(bool flat, int hidden, int obs_dim, int obs_stride, int a, uint32_t heads) {
+    if (flat) {
+        PFA_REQUIRE(hidden == kHidden, "mlp: hidden must be %d (got %d)", kHidden, hidden);
+    } else {
+        PFA_REQUIRE(hidden == 64 || hidden == 128 || hidden == 256 || hidden == 512, "mlp view: hidden %d is not one of 64/128/256/512", hidden);
+    }
+    PFA_REQUIRE(valid_row_stride(obs_stride, flat ? 128 : 64),
+                "mlp: obs_stride must be one of %s (got %d)", flat ? "16/32/64/96/128" : "16/32/64", obs_stride);
+    PFA_REQUIRE(obs_dim >= 1 && obs_dim <= obs_stride, "mlp: obs_dim %d out of range", obs_dim);
+    PFA_REQUIRE(a >= 1 && a <= 15, "mlp: num_actions must be in 1..15 (got %d)", a);
+    PFA_REQUIRE(heads == 0 || (flat && heads_count(heads, a) >= 1), "mlp: head sizes 0x%x do not sum to num_actions %d", heads, a);
+    return 0;
+}
+inline int check_dims(const pfa_mlp_dims *d) {
+    PFA_REQUIRE(d != nullptr, "mlp: null dims");
+    return check_shape(true, d->hidden, d->obs_dim, d->obs_stride, d->num_actions, d->heads);
+}
+inline int check_view(const pfa_mlp_view *p) {
+    PFA_REQUIRE(p != nullptr, "mlp view: null");
+    PFA_REQUIRE(p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv, "mlp view: null tensor");
+    PFA_REQUIRE(p->ldw1 >= p->obs_dim, "mlp view: obs_dim %d / ldw1 %d out of range", p->obs_dim, p->ldw1);
+    return check_shape(false, p->hidden, p->obs_dim, p->obs_stride, p->num_actions, 0);
+}
+inline int policy_of_flat(const float *params, const pfa_mlp_dims *d, TilePolicy *out) {
+    if (int rc = check_dims(d)) return rc;
+    PFA_REQUIRE(params, "mlp: null parameter buffer");
+    *out = TilePolicy{mlp_view_of_flat(params, d->obs_stride, d->num_actions), d->obs_dim, d->obs_stride, d->heads};
+    return 0;
+}
+inline int policy_of_view(const pfa_mlp_view *p, TilePolicy *out) {
+    if (int rc = check_view(p)) return rc;
+    *out = TilePolicy{MlpView{p->w1, p->ldw1, p->obs_dim, p->b1, p->w2, p->b2, p->wv, p->bv, p->num_actions, p->hidden}, p->obs_dim,
+                      p->obs_stride, 0};
+    return 0;
+}
+
+// hidden -> MW, then dispatch_stride: `launch` is called with the Tile of the policy's shape.  kOnlyDP != 0: the one row width the
+// caller's env has (only the four widths of that row are instantiated); it equals what dispatch_stride gives that row.
+template <int kOnlyDP = 0, class Launch>
+static void dispatch_tile(const TilePolicy &p, Launch launch) {
+    auto with_mw = [&](auto mw) {
+        constexpr int MW = decltype(mw)::value;
+        if constexpr (kOnlyDP != 0) {
+            static_assert(kOnlyDP == 16 || kOnlyDP == 32, "a row dispatch_stride never trims");
+            launch(Tile<kOnlyDP, kOnlyDP / 4, MW>{});
+        } else {
+            dispatch_stride<MW>(p.obs_stride, p.obs_dim, launch);
+        }
+    };
+    switch (p.pv.hidden) {
+        case 64: return with_mw(std::integral_constant<int, 1>{});
+        case 128: return with_mw(std::integral_constant<int, 2>{});
+        case 256: return with_mw(std::integral_constant<int, 4>{});
+        default: return with_mw(std::integral_constant<int, 8>{});
     }
 }
 

@@ -74,13 +74,16 @@ def make_squared(distance_to_target=3, num_targets=1, **kwargs):
 
 def env_creator(name='squared'):
     """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only; plus pixel_squared, this package's frame
-    rendering of it, and tabular, the creator of a user-given TabularMDP (the reference has no such names)."""
+    rendering of it, tabular, the creator of a user-given TabularMDP (the reference has no such names), and cartpole, the device
+    restatement of environments.classic_control's env (make_cartpole's max_steps=0 is that creator's env: no time limit)."""
     if name == 'squared':
         return make_squared
     if name == 'pixel_squared':
         return make_pixel_squared
     if name == 'tabular':
         return make_tabular
+    if name == 'cartpole':
+        return make_cartpole
     raise ValueError('Invalid environment name')
 
 
@@ -210,6 +213,9 @@ class _DeviceVecEnv:
     # fused_rollout_mlp(fp, experience, noise, key, stream): clean_pufferl.evaluate's T-step loop for the fused-kernel MLP policy as one
     # persistent kernel; None: the family has none (policy step + store + send per step)
     fused_rollout_mlp = None
+    # whether fused_rollout_mlp also takes view=<pfa_mlp_view of a Default(64 / 128 / 256 / 512)>.  The view rollout reads the state layout
+    # of the class that declares it: clean_pufferl.rollout_form looks in that class's own __dict__, never in a base class's
+    ROLLOUT_MLP_VIEW = False
     PREFETCH = False        # whether the trainer draws the next rollout's reset tape (and action noise) on its side stream under a fused rollout
     FAMILY = ''
     ABI = ''                # prefix of the family's entry points: ABI + '_episode_stats', ABI + '_last_infos'
@@ -420,6 +426,7 @@ class Squared(_ResetTape, _DeviceVecEnv):
     CONFIG_NAME = 'Squared '
     ABI = 'pfa_squared'
     ROLLOUT_LSTM = 'pfa_rollout_lstm_squared'
+    ROLLOUT_MLP_VIEW = True
 
     def __init__(self, env_creators, env_args, env_kwargs, num_envs, obs_stride=None, **kwargs):
         self._obs_stride_arg = obs_stride
@@ -1251,6 +1258,89 @@ class Tabular(_DeviceVecEnv):
         _lib.check(self.L.pfa_tabular_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), _lib.stream_handle()),
                    'debug_states')
         return out.cpu().numpy()
+
+
+def make_cartpole(max_steps=500, velocities=True, **kwargs):
+    """Env creator token of classic-control cart-pole: vector.make(make_cartpole, backend=CartPole, ...).  max_steps: the time limit
+    that ends an episode (500 is CartPole-v1's registered limit; 0 = none, which is what the reference's classic_control creator
+    builds).  velocities=False hides x_dot and theta_dot from the observation: the partially observed task."""
+    return CartPoleSpec(max_steps, velocities)
+
+
+class CartPoleSpec(_SimpleSpec):
+    """What ``driver_env`` exposes for cart-pole: gymnasium's Box(+-[4.8, f32 max, 24 degrees, f32 max], float32) and Discrete(2)."""
+
+    def __init__(self, max_steps=500, velocities=True):
+        import math
+        super().__init__(0, 1, 2)
+        self.max_steps, self.velocities = int(max_steps), bool(velocities)
+        fmax = np.finfo(np.float32).max
+        high = np.array([2.4 * 2, fmax, 12 * 2 * math.pi / 360 * 2, fmax], dtype=np.float32)
+        self.single_observation_space = spaces.Box(low=-high, high=high, shape=(4,), dtype=np.float32)
+        self.observation_space = self.single_observation_space
+        self.emulated = namespace(observation_dtype=np.dtype(np.float32), emulated_observation_dtype=np.dtype((np.float32, (4,))))
+
+
+class CartPole(_DeviceVecEnv):
+    """Device-resident vecenv of N classic-control cart-poles (csrc/cartpole_env.hpp, csrc/cartpole.hip): f64 dynamics, real-valued
+    observations.  The start states are counter-based — Philox keyed by (seed, global env, episode) — so there is no tape and envs
+    `env_offset ..` of a larger vecenv are reproduced exactly.  It has a fused rollout kernel for the recurrent policy and for
+    Default at every tile width (64 / 128 / 256 / 512).  Episodes end on different sends in different envs: in info_mode 'sync' every
+    send reads the finished flags back (one small D2H), in 'lazy' none does."""
+    FAMILY, NAMES, DEFAULTS = 'cartpole', ('max_steps', 'velocities'), (500, True)
+    ABI = 'pfa_cartpole'
+    SEEDED = True
+    CONFIG_NAME = 'CartPole '
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_cartpole'
+    ROLLOUT_MLP_VIEW = True
+
+    def _spec(self, max_steps, velocities):
+        return CartPoleSpec(max_steps, velocities)
+
+    def _alloc_state(self):
+        import torch
+        sp = self.driver_env
+        self.obs_dim = 4
+        self.observations = self.obs_buf[:, :4]
+        self.cfg = _lib.CartPoleConfig(self.num_agents, sp.max_steps, 1 if sp.velocities else 0, 0, 0, self.env_offset)
+        nbytes = self.L.pfa_cartpole_state_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise APIUsageError(self.L.pfa_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _finishing_send(self, sends):
+        return True         # episodes end on different sends in different envs
+
+    def _k_reset(self, seed):
+        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.cfg.env_offset = int(self.env_offset)
+        _lib.check(self.L.pfa_cartpole_async_reset(_lib.ptr(self.state), C.byref(self.cfg), *self._live(), _lib.stream_handle()), 'async_reset')
+
+    def _k_send(self, actions):
+        _lib.check(self.L.pfa_cartpole_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
+                   'send')
+
+    def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
+        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/cartpole.hip) over the flat 128-wide parameters `fp`, or
+        over `view`: the pfa_mlp_view of a Default of another width (general.tile_view)."""
+        if view is not None:
+            _lib.check(self.L.pfa_rollout_mlp_view_cartpole(_lib.ptr(self.state), C.byref(self.cfg), C.byref(view), C.byref(experience.c),
+                                                            _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(), stream),
+                       'rollout_mlp_view_cartpole')
+        else:
+            _lib.check(self.L.pfa_rollout_mlp_cartpole(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
+                                                       C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
+                                                       stream), 'rollout_mlp_cartpole')
+        self.sends += experience.horizon
+
+    def debug_states(self):
+        """([N][4] float64: x, x_dot, theta, theta_dot; [N][4] int32: episode, tick, done, ep_length) — test introspection."""
+        import torch
+        states = torch.zeros(self.num_agents, 4, dtype=torch.float64, device=self.device)
+        counters = torch.zeros(self.num_agents, 4, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.pfa_cartpole_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(states), _lib.ptr(counters),
+                                                    _lib.stream_handle()), 'debug_states')
+        return states.cpu().numpy(), counters.cpu().numpy()
 
 
 def make_bandit(num_actions=10, reward_scale=1, reward_noise=1, **kwargs):
