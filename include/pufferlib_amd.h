@@ -499,6 +499,49 @@ int pfa_rollout_mlp_view_cartpole(void *state, const pfa_cartpole_config *cfg, c
                                   uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Acrobot vecenv — classic-control acrobot (csrc/acrobot_env.hpp; gymnasium's AcrobotEnv, "book" equations, no torque noise): f64
+ * state (th1, th2, w1, w2), one classical RK4 step of dt = 0.2 per send under a torque of action - 1, the angles wrapped into
+ * [-pi, pi], the velocities clamped to +-4 pi and +-9 pi.  Reward -1 per step, 0 on the step after which -cos th1 - cos(th1 + th2)
+ * > 1; terminal then, or when — max_steps > 0 — the episode is max_steps long; the send after it is the auto-reset row, which draws
+ * the four state values as -0.1 + 0.2 * (word * 2^-32) from Philox4x32-10(counter = (env_offset + env, episode, 0, 0), key = (seed
+ * lo, 0x4143 ^ seed hi)).  sin / cos are csrc/f64_sincos.hpp's and nothing is contracted, so a float64 host walker gives the same
+ * bits.  Observation rows are 16 floats: (cos th1, sin th1, cos th2, sin th2, w1, w2) as f32 in columns 0..5 (columns 4 and 5 are 0
+ * when velocities == 0), zero behind.  infos' score = the episode's return.  Protocol and live buffers as the other device envs.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t num_envs;
+    int32_t max_steps;      /* >= 0; 0 = no time limit */
+    int32_t velocities;     /* 0: w1 and w2 are hidden from the observation */
+    int32_t reserved;
+    uint64_t seed;
+    int64_t env_offset;     /* global index of local env 0 (sharding) */
+} pfa_acrobot_config;
+size_t pfa_acrobot_state_bytes(const pfa_acrobot_config *cfg);
+int pfa_acrobot_async_reset(void *state, const pfa_acrobot_config *cfg, float *obs, float *rewards, uint8_t *terminals,
+                            uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_acrobot_send(void *state, const pfa_acrobot_config *cfg, const int64_t *actions, float *obs, float *rewards,
+                     uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_acrobot_episode_stats(void *state, const pfa_acrobot_config *cfg, double *out4, int32_t reset, pfa_stream_t stream);
+int pfa_acrobot_last_infos(void *state, const pfa_acrobot_config *cfg, uint8_t *finished, double *episode_return,
+                           int32_t *episode_length, double *score, pfa_stream_t stream);
+/* test introspection: states[e] = {th1, th2, w1, w2}, counters[e] = {episode, tick, done, ep_length} of env e ... */
+int pfa_acrobot_debug_states(void *state, const pfa_acrobot_config *cfg, double *states4, int32_t *counters4, pfa_stream_t stream);
+/* ... and the inverse: env e becomes an episode ep_length steps old (return -ep_length) in that state, and its row of the live
+ * observations `obs` and its live terminal flag (= done) follow.  The caller keeps the states inside the state box. */
+int pfa_acrobot_debug_set_states(void *state, const pfa_acrobot_config *cfg, const double *states4, const int32_t *counters4,
+                                 float *obs, uint8_t *terminals, pfa_stream_t stream);
+/* clean_pufferl.evaluate's loop for an Acrobot vecenv and the MLP policy, one persistent kernel: the flat 128-wide buffer
+ * (dims->obs_stride == 16, dims->obs_dim == 6, dims->num_actions == 3) ... */
+int pfa_rollout_mlp_acrobot(void *state, const pfa_acrobot_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                            const pfa_experience *exp, const float *noise, const pfa_noise_key *key, int64_t env_offset,
+                            float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks,
+                            pfa_stream_t stream);
+/* ... or a pfa_mlp_view of hidden 64 / 128 / 256 / 512 (the same kernel with W1 fragments of that width; same row and head). */
+int pfa_rollout_mlp_view_acrobot(void *state, const pfa_acrobot_config *cfg, const pfa_mlp_view *view, const pfa_experience *exp,
+                                 const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
+                                 uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Structured-observation unpack — replaces pufferlib.pytorch.nativize_tensor
  * (pufferlib/pytorch.py:96-145): flat emulated rows [num_rows][row_bytes] (device, 16-byte aligned) -> one dense tensor
  * per leaf of the observation space, in one launch.  A field is a leaf as pufferlib.pytorch.nativize_dtype
@@ -673,6 +716,11 @@ int pfa_rollout_lstm_cartpole(void *state, const pfa_cartpole_config *cfg, const
                               const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                               const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                               uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* ... and over the Acrobot vecenv (pfa_acrobot_*): observation rows of 16 floats, one Discrete(3) head. */
+int pfa_rollout_lstm_acrobot(void *state, const pfa_acrobot_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                             const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                             const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                             uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 /* --- the recurrent policy in training mode (csrc/lstm_seq.hip): forward over the `steps` (= bptt_horizon) time steps
  * of a minibatch of `rows` independent segments and back-propagation through time (clean_pufferl.py:186-193, :244).
  * Time-major buffers: obs_tm [steps][rows][obs_stride], xe / dh_heads / dxe [steps][rows][128], gates_act / dgates

@@ -16,7 +16,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, '_lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libpufferlib_amd.so')
-SOURCES = ['common.cpp', 'dist.cpp', 'p2p.hip', 'gae.hip', 'squared.hip', 'pixel_squared.hip', 'rollout.hip', 'ppo_update.hip', 'lstm.hip', 'gemm.hip', 'lstm_fused.hip', 'lstm_seq.hip', 'stochastic.hip', 'memory.hip', 'bandit.hip', 'multiagent.hip', 'spaces.hip', 'synthetic.hip', 'tabular.hip', 'cartpole.hip', 'nativize.hip', 'igemm.hip', 'cnn_heads.hip', 'general.hip', 'ppo_wide.hip']
+SOURCES = ['common.cpp', 'dist.cpp', 'p2p.hip', 'gae.hip', 'squared.hip', 'pixel_squared.hip', 'rollout.hip', 'ppo_update.hip', 'lstm.hip', 'gemm.hip', 'lstm_fused.hip', 'lstm_seq.hip', 'stochastic.hip', 'memory.hip', 'bandit.hip', 'multiagent.hip', 'spaces.hip', 'synthetic.hip', 'tabular.hip', 'cartpole.hip', 'acrobot.hip', 'nativize.hip', 'igemm.hip', 'cnn_heads.hip', 'general.hip', 'ppo_wide.hip']
 # every header under csrc/ (sorted: the order is part of source_hash) + the public C header: a header missing from a hand-kept list is a
 # library that silently is not rebuilt when only that header changes
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.hpp')) + [os.path.join('..', '..', 'include', 'pufferlib_amd.h')]
@@ -109,6 +109,11 @@ class TabularConfig(C.Structure):
 
 
 class CartPoleConfig(C.Structure):
+    _fields_ = [('num_envs', C.c_int32), ('max_steps', C.c_int32), ('velocities', C.c_int32), ('reserved', C.c_int32),
+                ('seed', C.c_uint64), ('env_offset', C.c_int64)]
+
+
+class AcrobotConfig(C.Structure):
     _fields_ = [('num_envs', C.c_int32), ('max_steps', C.c_int32), ('velocities', C.c_int32), ('reserved', C.c_int32),
                 ('seed', C.c_uint64), ('env_offset', C.c_int64)]
 
@@ -272,6 +277,19 @@ _SIGNATURES = {
                                                 C.c_int64, P, P, P, P, P, P]),
     'pfa_rollout_lstm_cartpole': (C.c_int, [P, C.POINTER(CartPoleConfig), P, C.POINTER(MlpDims), P, P, P, C.POINTER(Experience),
                                             P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P, P]),
+    'pfa_acrobot_state_bytes': (C.c_size_t, [C.POINTER(AcrobotConfig)]),
+    'pfa_acrobot_async_reset': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P, P]),
+    'pfa_acrobot_send': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P, P, P]),
+    'pfa_acrobot_episode_stats': (C.c_int, [P, C.POINTER(AcrobotConfig), P, C.c_int32, P]),
+    'pfa_acrobot_last_infos': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P]),
+    'pfa_acrobot_debug_states': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P]),
+    'pfa_acrobot_debug_set_states': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P]),
+    'pfa_rollout_mlp_acrobot': (C.c_int, [P, C.POINTER(AcrobotConfig), P, C.POINTER(MlpDims), C.POINTER(Experience), P, C.POINTER(NoiseKey),
+                                          C.c_int64, P, P, P, P, P, P]),
+    'pfa_rollout_mlp_view_acrobot': (C.c_int, [P, C.POINTER(AcrobotConfig), C.POINTER(MlpView), C.POINTER(Experience), P, C.POINTER(NoiseKey),
+                                               C.c_int64, P, P, P, P, P, P]),
+    'pfa_rollout_lstm_acrobot': (C.c_int, [P, C.POINTER(AcrobotConfig), P, C.POINTER(MlpDims), P, P, P, C.POINTER(Experience),
+                                           P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P, P]),
     'pfa_multiagent_episode_stats': (C.c_int, [P, C.c_int32, P, C.c_int32, P]),
     'pfa_nativize_rows': (C.c_int, [P, C.c_int64, C.c_int32, P, C.c_int32, P]),
     'pfa_ppo_workspace_bytes': (C.c_size_t, [C.POINTER(MlpDims), C.c_int64, C.POINTER(PpoHparams)]),

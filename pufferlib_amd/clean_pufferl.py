@@ -428,7 +428,7 @@ def rollout_form(vecenv_class, gen_engine, lstm_engine, mlp_view):
     """Which rollout evaluate() runs for a device vecenv class and the engines create() built: one persistent kernel where the env
     class declares one for the policy kind (ROLLOUT_LSTM, fused_rollout_mlp), else policy step + store + send per step."""
     if gen_engine:       # GEMM-path policy: its Default(64 / 256 / 512) shapes share the rollout kernel of a class that declares the view
-        #                  form (Squared, CartPole); the kernel reads that class's own state layout: exactly the class, not a subclass
+        #                  form (Squared, CartPole, Acrobot); the kernel reads that class's own state layout: exactly the class, not a subclass
         return FUSED_MLP if mlp_view and vecenv_class.__dict__.get('ROLLOUT_MLP_VIEW', False) else STEPWISE
     if lstm_engine:
         return FUSED_LSTM if vecenv_class.ROLLOUT_LSTM is not None else STEPWISE

@@ -19,6 +19,7 @@
 #include "env_adapters.hpp"
 #include "tabular_env.hpp"
 #include "cartpole_env.hpp"
+#include "acrobot_env.hpp"
 
 namespace pfa {
 
@@ -349,4 +350,16 @@ extern "C" int pfa_rollout_lstm_cartpole(void *state, const pfa_cartpole_config 
     PFA_REQUIRE(dims->obs_stride == kCartDP, "rollout_lstm_cartpole: observation rows are %d floats (got %d)", kCartDP, dims->obs_stride);
     return launch_rollout_lstm<CartPoleRollEnv, kCartDP>("rollout_lstm_cartpole", state, cfg, params, dims, wpack, h, c, exp, noise, key,
                                                          env_offset, obs, rewards, terminals, truncations, masks, stream);
+}
+
+extern "C" int pfa_rollout_lstm_acrobot(void *state, const pfa_acrobot_config *cfg, const float *params, const pfa_mlp_dims *dims,
+                                        const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                                        const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                                        uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    if (int rc = check_lstm_dims(dims)) return rc;
+    if (int rc = check_acrobot_config(cfg)) return rc;
+    PFA_REQUIRE(dims->num_actions == 3, "rollout_lstm_acrobot: the policy must have one Discrete(3) head (got %d actions)", dims->num_actions);
+    PFA_REQUIRE(dims->obs_stride == kAcroDP, "rollout_lstm_acrobot: observation rows are %d floats (got %d)", kAcroDP, dims->obs_stride);
+    return launch_rollout_lstm<AcrobotRollEnv, kAcroDP>("rollout_lstm_acrobot", state, cfg, params, dims, wpack, h, c, exp, noise, key,
+                                                        env_offset, obs, rewards, terminals, truncations, masks, stream);
 }

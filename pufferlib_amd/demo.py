@@ -8,7 +8,7 @@ mapped to ``pufferlib.vector.Serial / Multiprocessing / Ray`` (demo.py:159-167).
   1. makes ``clean_pufferl`` resolve to ``pufferlib_amd.clean_pufferl`` (same function surface: create / evaluate / train / close /
      try_load_checkpoint / rollout, the same ``data`` namespace);
   2. rebinds ``pufferlib.vector.Serial`` to ``DeviceOrHost``: a backend factory that builds the device-resident vecenv of this
-     package when the env creator is one of the ocean envs it hosts (squared, pixel_squared, stochastic, memory, bandit, multiagent, spaces) or this package's own make_tabular / make_cartpole
+     package when the env creator is one of the ocean envs it hosts (squared, pixel_squared, stochastic, memory, bandit, multiagent, spaces) or this package's own make_tabular / make_cartpole / make_acrobot
      and the reference's own ``Serial`` otherwise (the trainer then takes its host-vecenv path, pufferlib_amd/hostpath.py);
      ``--host-vec`` keeps the reference backends untouched;
   3. supplies a stand-in for ``rich_argparse`` if it is not installed (demo.py only uses its help formatter);
@@ -55,7 +55,7 @@ def device_backend_for(creator):
     from . import vector
     name = _creator_name(creator)
     for key, cls in (('pixel_squared', 'PixelSquared'), ('squared', 'Squared'), ('stochastic', 'Stochastic'), ('memory', 'Memory'), ('bandit', 'Bandit'),
-                     ('multiagent', 'Multiagent'), ('spaces', 'Spaces'), ('synthetic', 'Synthetic'), ('tabular', 'Tabular'), ('cartpole', 'CartPole')):
+                     ('multiagent', 'Multiagent'), ('spaces', 'Spaces'), ('synthetic', 'Synthetic'), ('tabular', 'Tabular'), ('cartpole', 'CartPole'), ('acrobot', 'Acrobot')):
         if key in name and hasattr(vector, cls):
             return getattr(vector, cls)
     return None

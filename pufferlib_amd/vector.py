@@ -74,8 +74,9 @@ def make_squared(distance_to_target=3, num_targets=1, **kwargs):
 
 def env_creator(name='squared'):
     """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only; plus pixel_squared, this package's frame
-    rendering of it, tabular, the creator of a user-given TabularMDP (the reference has no such names), and cartpole, the device
-    restatement of environments.classic_control's env (make_cartpole's max_steps=0 is that creator's env: no time limit)."""
+    rendering of it, tabular, the creator of a user-given TabularMDP (the reference has no such names), cartpole, the device
+    restatement of environments.classic_control's env (make_cartpole's max_steps=0 is that creator's env: no time limit), and
+    acrobot, gymnasium's Acrobot-v1 (the reference binds no such env)."""
     if name == 'squared':
         return make_squared
     if name == 'pixel_squared':
@@ -84,6 +85,8 @@ def env_creator(name='squared'):
         return make_tabular
     if name == 'cartpole':
         return make_cartpole
+    if name == 'acrobot':
+        return make_acrobot
     raise ValueError('Invalid environment name')
 
 
@@ -1341,6 +1344,109 @@ class CartPole(_DeviceVecEnv):
         _lib.check(self.L.pfa_cartpole_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(states), _lib.ptr(counters),
                                                     _lib.stream_handle()), 'debug_states')
         return states.cpu().numpy(), counters.cpu().numpy()
+
+
+def make_acrobot(max_steps=500, velocities=True, **kwargs):
+    """Env creator token of classic-control acrobot: vector.make(make_acrobot, backend=Acrobot, ...).  max_steps: the time limit that
+    ends an episode (500 is Acrobot-v1's registered limit; 0 = none).  velocities=False hides the two angular velocities from the
+    observation: the partially observed task."""
+    return AcrobotSpec(max_steps, velocities)
+
+
+class AcrobotSpec(_SimpleSpec):
+    """What ``driver_env`` exposes for acrobot: gymnasium's Box(+-[1, 1, 1, 1, 4 pi, 9 pi], float32) and Discrete(3)."""
+
+    def __init__(self, max_steps=500, velocities=True):
+        import math
+        super().__init__(0, 1, 3)
+        self.max_steps, self.velocities = int(max_steps), bool(velocities)
+        high = np.array([1.0, 1.0, 1.0, 1.0, 4 * math.pi, 9 * math.pi], dtype=np.float32)
+        self.single_observation_space = spaces.Box(low=-high, high=high, shape=(6,), dtype=np.float32)
+        self.observation_space = self.single_observation_space
+        self.emulated = namespace(observation_dtype=np.dtype(np.float32), emulated_observation_dtype=np.dtype((np.float32, (6,))))
+
+
+class Acrobot(_DeviceVecEnv):
+    """Device-resident vecenv of N classic-control acrobots (csrc/acrobot_env.hpp, csrc/acrobot.hip): f64 RK4 dynamics, observations
+    (cos th1, sin th1, cos th2, sin th2, w1, w2), three torques, reward -1 per step until the tip swings above the bar.  The start
+    states are counter-based — Philox keyed by (seed, global env, episode) — so there is no tape and envs `env_offset ..` of a larger
+    vecenv are reproduced exactly.  It has a fused rollout kernel for the recurrent policy and for Default at every tile width (64 /
+    128 / 256 / 512).  Episodes end on different sends in different envs: in info_mode 'sync' every send reads the finished flags back
+    (one small D2H), in 'lazy' none does."""
+    FAMILY, NAMES, DEFAULTS = 'acrobot', ('max_steps', 'velocities'), (500, True)
+    ABI = 'pfa_acrobot'
+    SEEDED = True
+    CONFIG_NAME = 'Acrobot '
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_acrobot'
+    ROLLOUT_MLP_VIEW = True
+
+    def _spec(self, max_steps, velocities):
+        return AcrobotSpec(max_steps, velocities)
+
+    def _alloc_state(self):
+        import torch
+        sp = self.driver_env
+        self.obs_dim = 6
+        self.observations = self.obs_buf[:, :6]
+        self.cfg = _lib.AcrobotConfig(self.num_agents, sp.max_steps, 1 if sp.velocities else 0, 0, 0, self.env_offset)
+        nbytes = self.L.pfa_acrobot_state_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise APIUsageError(self.L.pfa_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _finishing_send(self, sends):
+        return True         # episodes end on different sends in different envs
+
+    def _k_reset(self, seed):
+        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.cfg.env_offset = int(self.env_offset)
+        _lib.check(self.L.pfa_acrobot_async_reset(_lib.ptr(self.state), C.byref(self.cfg), *self._live(), _lib.stream_handle()), 'async_reset')
+
+    def _k_send(self, actions):
+        _lib.check(self.L.pfa_acrobot_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
+                   'send')
+
+    def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
+        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/acrobot.hip) over the flat 128-wide parameters `fp`, or
+        over `view`: the pfa_mlp_view of a Default of another width (general.tile_view)."""
+        if view is not None:
+            _lib.check(self.L.pfa_rollout_mlp_view_acrobot(_lib.ptr(self.state), C.byref(self.cfg), C.byref(view), C.byref(experience.c),
+                                                           _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(), stream),
+                       'rollout_mlp_view_acrobot')
+        else:
+            _lib.check(self.L.pfa_rollout_mlp_acrobot(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
+                                                      C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
+                                                      stream), 'rollout_mlp_acrobot')
+        self.sends += experience.horizon
+
+    def debug_states(self):
+        """([N][4] float64: th1, th2, w1, w2; [N][4] int32: episode, tick, done, ep_length) — test introspection."""
+        import torch
+        states = torch.zeros(self.num_agents, 4, dtype=torch.float64, device=self.device)
+        counters = torch.zeros(self.num_agents, 4, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.pfa_acrobot_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(states), _lib.ptr(counters),
+                                                   _lib.stream_handle()), 'debug_states')
+        return states.cpu().numpy(), counters.cpu().numpy()
+
+    def debug_set_states(self, states, counters):
+        """The inverse of debug_states(), for tests that put envs on the rare branches on purpose (an angle about to wrap, a velocity
+        at its clamp, a state one step below the height threshold): env e becomes an episode ep_length steps old, with return
+        -ep_length, in the given state; its live observation row and terminal flag follow.  The states must lie inside the state box
+        (|th| <= pi, |w1| <= 4 pi, |w2| <= 9 pi) and the counters must be non-negative."""
+        import math
+        import torch
+        states, counters = np.asarray(states), np.asarray(counters)
+        n = self.num_agents
+        if states.shape != (n, 4) or counters.shape != (n, 4):
+            raise APIUsageError(f'Acrobot.debug_set_states: states and counters must have shape ({n}, 4), got {states.shape} and {counters.shape}')
+        states, counters = np.ascontiguousarray(states, dtype=np.float64), np.ascontiguousarray(counters, dtype=np.int32)
+        if not (np.abs(states) <= np.array([math.pi, math.pi, 4 * math.pi, 9 * math.pi])).all() or (counters < 0).any():
+            raise APIUsageError('Acrobot.debug_set_states: a state outside the state box (|th| <= pi, |w1| <= 4 pi, |w2| <= 9 pi) or a negative counter')
+        st, cn = torch.as_tensor(states).to(self.device), torch.as_tensor(counters).to(self.device)
+        _lib.check(self.L.pfa_acrobot_debug_set_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(st), _lib.ptr(cn),
+                                                       _lib.ptr(self.obs_buf), _lib.ptr(self.terminals_u8), _lib.stream_handle()),
+                   'debug_set_states')
+        torch.cuda.current_stream().synchronize()       # st and cn are freed on return
 
 
 def make_bandit(num_actions=10, reward_scale=1, reward_noise=1, **kwargs):
