@@ -108,14 +108,13 @@ class TabularConfig(C.Structure):
                 ('start_cum', C.c_void_p)]
 
 
-class CartPoleConfig(C.Structure):
+class ControlConfig(C.Structure):
+    """pfa_cartpole_config and pfa_acrobot_config: the classic-control families share one layout."""
     _fields_ = [('num_envs', C.c_int32), ('max_steps', C.c_int32), ('velocities', C.c_int32), ('reserved', C.c_int32),
                 ('seed', C.c_uint64), ('env_offset', C.c_int64)]
 
 
-class AcrobotConfig(C.Structure):
-    _fields_ = [('num_envs', C.c_int32), ('max_steps', C.c_int32), ('velocities', C.c_int32), ('reserved', C.c_int32),
-                ('seed', C.c_uint64), ('env_offset', C.c_int64)]
+CartPoleConfig = AcrobotConfig = ControlConfig
 
 
 class IgemmOperand(C.Structure):
@@ -172,6 +171,30 @@ class PpoHparams(C.Structure):
 
 
 P = C.c_void_p
+
+
+def _counter_seeded_family(family, config, mlp_view=False, **debug):
+    """The entries of a family whose entry points all take (state, config) and whose randomness is counter-based (no tape): the
+    protocol, the fused MLP rollout over the flat buffer (and over a pfa_mlp_view where `mlp_view`), the fused recurrent rollout,
+    and the family's test-introspection entry points `debug`: name -> argument types between the config and the stream."""
+    cfg, live = C.POINTER(config), [P, P, P, P, P]
+    rollout = [C.POINTER(Experience), P, C.POINTER(NoiseKey), C.c_int64, *live, P]
+    sigs = {
+        f'pfa_{family}_state_bytes': (C.c_size_t, [cfg]),
+        f'pfa_{family}_async_reset': (C.c_int, [P, cfg, *live, P]),
+        f'pfa_{family}_send': (C.c_int, [P, cfg, P, *live, P]),
+        f'pfa_{family}_episode_stats': (C.c_int, [P, cfg, P, C.c_int32, P]),
+        f'pfa_{family}_last_infos': (C.c_int, [P, cfg, P, P, P, P, P]),
+        f'pfa_rollout_mlp_{family}': (C.c_int, [P, cfg, P, C.POINTER(MlpDims), *rollout]),
+        f'pfa_rollout_lstm_{family}': (C.c_int, [P, cfg, P, C.POINTER(MlpDims), P, P, P, *rollout]),
+    }
+    if mlp_view:
+        sigs[f'pfa_rollout_mlp_view_{family}'] = (C.c_int, [P, cfg, C.POINTER(MlpView), *rollout])
+    for name, args in debug.items():
+        sigs[f'pfa_{family}_{name}'] = (C.c_int, [P, cfg, *args, P])
+    return sigs
+
+
 _SIGNATURES = {
     # name: (restype, argtypes) — must list every symbol include/pufferlib_amd.h declares
     'pfa_version': (C.c_int, []),
@@ -255,41 +278,9 @@ _SIGNATURES = {
     'pfa_frames_send': (C.c_int, [P, C.POINTER(SynthConfig), P, P, P, P, P, P, P]),
     'pfa_synth_episode_stats': (C.c_int, [P, C.POINTER(SynthConfig), P, C.c_int32, P]),
     'pfa_synth_last_infos': (C.c_int, [P, C.POINTER(SynthConfig), P, P, P, P, P]),
-    'pfa_tabular_state_bytes': (C.c_size_t, [C.POINTER(TabularConfig)]),
-    'pfa_tabular_async_reset': (C.c_int, [P, C.POINTER(TabularConfig), P, P, P, P, P, P]),
-    'pfa_tabular_send': (C.c_int, [P, C.POINTER(TabularConfig), P, P, P, P, P, P, P]),
-    'pfa_tabular_episode_stats': (C.c_int, [P, C.POINTER(TabularConfig), P, C.c_int32, P]),
-    'pfa_tabular_last_infos': (C.c_int, [P, C.POINTER(TabularConfig), P, P, P, P, P]),
-    'pfa_tabular_debug_states': (C.c_int, [P, C.POINTER(TabularConfig), P, P]),
-    'pfa_rollout_mlp_tabular': (C.c_int, [P, C.POINTER(TabularConfig), P, C.POINTER(MlpDims), C.POINTER(Experience), P, C.POINTER(NoiseKey),
-                                          C.c_int64, P, P, P, P, P, P]),
-    'pfa_rollout_lstm_tabular': (C.c_int, [P, C.POINTER(TabularConfig), P, C.POINTER(MlpDims), P, P, P, C.POINTER(Experience),
-                                           P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P, P]),
-    'pfa_cartpole_state_bytes': (C.c_size_t, [C.POINTER(CartPoleConfig)]),
-    'pfa_cartpole_async_reset': (C.c_int, [P, C.POINTER(CartPoleConfig), P, P, P, P, P, P]),
-    'pfa_cartpole_send': (C.c_int, [P, C.POINTER(CartPoleConfig), P, P, P, P, P, P, P]),
-    'pfa_cartpole_episode_stats': (C.c_int, [P, C.POINTER(CartPoleConfig), P, C.c_int32, P]),
-    'pfa_cartpole_last_infos': (C.c_int, [P, C.POINTER(CartPoleConfig), P, P, P, P, P]),
-    'pfa_cartpole_debug_states': (C.c_int, [P, C.POINTER(CartPoleConfig), P, P, P]),
-    'pfa_rollout_mlp_cartpole': (C.c_int, [P, C.POINTER(CartPoleConfig), P, C.POINTER(MlpDims), C.POINTER(Experience), P, C.POINTER(NoiseKey),
-                                           C.c_int64, P, P, P, P, P, P]),
-    'pfa_rollout_mlp_view_cartpole': (C.c_int, [P, C.POINTER(CartPoleConfig), C.POINTER(MlpView), C.POINTER(Experience), P, C.POINTER(NoiseKey),
-                                                C.c_int64, P, P, P, P, P, P]),
-    'pfa_rollout_lstm_cartpole': (C.c_int, [P, C.POINTER(CartPoleConfig), P, C.POINTER(MlpDims), P, P, P, C.POINTER(Experience),
-                                            P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P, P]),
-    'pfa_acrobot_state_bytes': (C.c_size_t, [C.POINTER(AcrobotConfig)]),
-    'pfa_acrobot_async_reset': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P, P]),
-    'pfa_acrobot_send': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P, P, P]),
-    'pfa_acrobot_episode_stats': (C.c_int, [P, C.POINTER(AcrobotConfig), P, C.c_int32, P]),
-    'pfa_acrobot_last_infos': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P]),
-    'pfa_acrobot_debug_states': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P]),
-    'pfa_acrobot_debug_set_states': (C.c_int, [P, C.POINTER(AcrobotConfig), P, P, P, P, P]),
-    'pfa_rollout_mlp_acrobot': (C.c_int, [P, C.POINTER(AcrobotConfig), P, C.POINTER(MlpDims), C.POINTER(Experience), P, C.POINTER(NoiseKey),
-                                          C.c_int64, P, P, P, P, P, P]),
-    'pfa_rollout_mlp_view_acrobot': (C.c_int, [P, C.POINTER(AcrobotConfig), C.POINTER(MlpView), C.POINTER(Experience), P, C.POINTER(NoiseKey),
-                                               C.c_int64, P, P, P, P, P, P]),
-    'pfa_rollout_lstm_acrobot': (C.c_int, [P, C.POINTER(AcrobotConfig), P, C.POINTER(MlpDims), P, P, P, C.POINTER(Experience),
-                                           P, C.POINTER(NoiseKey), C.c_int64, P, P, P, P, P, P]),
+    **_counter_seeded_family('tabular', TabularConfig, debug_states=[P]),
+    **_counter_seeded_family('cartpole', ControlConfig, debug_states=[P, P], mlp_view=True),
+    **_counter_seeded_family('acrobot', ControlConfig, debug_states=[P, P], debug_set_states=[P, P, P, P], mlp_view=True),
     'pfa_multiagent_episode_stats': (C.c_int, [P, C.c_int32, P, C.c_int32, P]),
     'pfa_nativize_rows': (C.c_int, [P, C.c_int64, C.c_int32, P, C.c_int32, P]),
     'pfa_ppo_workspace_bytes': (C.c_size_t, [C.POINTER(MlpDims), C.c_int64, C.POINTER(PpoHparams)]),

@@ -20,14 +20,11 @@
 // conversion per observation value, so that a float64 walker on the host that spells the same operations gives the same bits
 // (tests/acrobot_reference.py).  The four RK4 stages are one rolled loop: the right-hand side stands in a kernel once.
 #pragma once
-#include "common.hpp"
-#include "episode_fin.hpp"
-#include "philox.hpp"
+#include "control_env.hpp"
 #include "f64_sincos.hpp"
 
 namespace pfa {
 
-constexpr int kAcroDP = 16;     // floats per observation row
 constexpr int kAcroWraps = 64;  // turns of each wrap loop at the most
 constexpr double kAcroPi = 3.141592653589793, kAcroMaxVel1 = 4.0 * kAcroPi, kAcroMaxVel2 = 9.0 * kAcroPi;
 
@@ -35,49 +32,7 @@ struct AcrobotEnv {
     double th1, th2, w1, w2, ep_return;
     int episode, tick, done, ep_length;
 };
-struct AcrobotView {
-    AcrobotEnv *env;
-    EpisodeFin *fin;
-    int n, max_steps;
-    bool velocities;
-    uint32_t key0, key1;
-    long long env_offset;
-};
-__host__ __device__ inline size_t acrobot_state_bytes(int n) { return (size_t)n * (sizeof(AcrobotEnv) + sizeof(EpisodeFin)); }
-__host__ __device__ inline AcrobotView acrobot_view(void *state, const pfa_acrobot_config &c) {
-    AcrobotView v;
-    v.env = (AcrobotEnv *)state;
-    v.fin = (EpisodeFin *)((char *)state + (size_t)c.num_envs * sizeof(AcrobotEnv));
-    v.n = c.num_envs;
-    v.max_steps = c.max_steps;
-    v.velocities = c.velocities != 0;
-    v.key0 = (uint32_t)c.seed;
-    v.key1 = 0x4143u ^ (uint32_t)(c.seed >> 32);
-    v.env_offset = c.env_offset;
-    return v;
-}
-
-// What the entry points of the family refuse (acrobot.hip).
-int check_acrobot_config(const pfa_acrobot_config *c);
-
-__device__ __forceinline__ void acrobot_draw(const AcrobotView &v, int e, AcrobotEnv &s) {
-#pragma clang fp contract(off)
-    const u32x4 w = philox4x32_10((uint32_t)(v.env_offset + e), (uint32_t)s.episode, 0u, 0u, v.key0, v.key1);
-    constexpr double k = 1.0 / 4294967296.0;
-    s.th1 = -0.1 + 0.2 * ((double)w.x * k);
-    s.th2 = -0.1 + 0.2 * ((double)w.y * k);
-    s.w1 = -0.1 + 0.2 * ((double)w.z * k);
-    s.w2 = -0.1 + 0.2 * ((double)w.w * k);
-}
-
-__device__ __forceinline__ void acrobot_begin_episode(const AcrobotView &v, int e, AcrobotEnv &s) {
-    s.episode += 1;
-    s.tick = 0;
-    s.done = 0;
-    s.ep_length = 0;
-    s.ep_return = 0.0;
-    acrobot_draw(v, e, s);
-}
+using AcrobotView = ControlView<AcrobotEnv>;
 
 // gymnasium's _dsdt with m1 = m2 = l1 = I1 = I2 = 1, lc1 = lc2 = 0.5, g = 9.8 (the products with 1 are dropped: they are exact)
 __device__ __forceinline__ void acrobot_dsdt(double th1, double th2, double w1, double w2, double torque, double &a1, double &a2) {
@@ -145,52 +100,46 @@ __device__ __forceinline__ double acrobot_observe(const AcrobotView &v, const Ac
     return c1;
 }
 
-// one send of env e, observation row included; returns true when the episode finished (and was accounted)
-__device__ __forceinline__ bool acrobot_send(const AcrobotView &v, int e, AcrobotEnv &s, int action, float *row, float &reward, bool &terminal) {
+// The physics traits of the family (control_env.hpp).
+struct AcrobotPhysics {
+    using State = AcrobotEnv;
+    using Config = pfa_acrobot_config;
+    static constexpr const char *kName = "acrobot";
+    static constexpr int kObs = 6, kActions = 3;
+    static constexpr uint32_t kKeyTag = 0x4143u;   // 'AC'
+    static constexpr double kDrawLo = -0.1, kDrawWidth = 0.2;
+    __device__ __forceinline__ static void values(const State &s, double *d) { d[0] = s.th1, d[1] = s.th2, d[2] = s.w1, d[3] = s.w2; }
+    __device__ __forceinline__ static void set_values(State &s, double th1, double th2, double w1, double w2) {
+        s.th1 = th1, s.th2 = th2, s.w1 = w1, s.w2 = w2;
+    }
+    __device__ __forceinline__ static void observe(const AcrobotView &v, const State &s, float *row) { acrobot_observe(v, s, row); }
+    __device__ __forceinline__ static bool send(const AcrobotView &v, int e, State &s, int action, float *row, float &reward, bool &terminal) {
 #pragma clang fp contract(off)
-    const bool stepped = !s.done;
-    if (stepped) {
-        acrobot_advance(s, action);
-    } else {
-        acrobot_begin_episode(v, e, s);
-    }
-    const double c1 = acrobot_observe(v, s, row);
-    reward = 0.0f;
-    terminal = false;
-    if (stepped) {
-        double sn, c12;
-        f64_sincos(s.th1 + s.th2, sn, c12);
-        const bool up = -c1 - c12 > 1.0;
-        const double r = up ? 0.0 : -1.0;
-        s.tick += 1;
-        s.ep_length += 1;
-        s.ep_return = s.ep_return + r;
-        reward = (float)r;
-        terminal = up || (v.max_steps > 0 && s.tick == v.max_steps);
-        s.done = terminal;
-        if (terminal) episode_account(v.fin[e], s.ep_return, s.ep_length, s.ep_return);
-    }
-    return terminal;
-}
-
-// The env adapter (env_adapters.hpp), in the shape of CartPoleRollEnv: the owner steps and writes the six observation values itself.
-struct AcrobotRollEnv {
-    using View = AcrobotView;
-    static View view(void *state, const pfa_acrobot_config &c) { return acrobot_view(state, c); }
-    static constexpr bool kRefresh = false;
-    struct Shared {};
-    AcrobotEnv s = {};
-    int last_fin = 0;
-
-    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
-    __device__ __forceinline__ void step(const View &v, int e, int, Shared &, float *row, int action, float &reward, bool &terminal) {
-        last_fin = acrobot_send(v, e, s, action, row, reward, terminal) ? 1 : 0;
-    }
-    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
-    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
-        v.env[e] = s;
-        v.fin[e].last_fin = last_fin;
+        const bool stepped = !s.done;
+        if (stepped) {
+            acrobot_advance(s, action);
+        } else {
+            control_begin_episode<AcrobotPhysics>(v, e, s);
+        }
+        const double c1 = acrobot_observe(v, s, row);
+        reward = 0.0f;
+        terminal = false;
+        if (stepped) {
+            double sn, c12;
+            f64_sincos(s.th1 + s.th2, sn, c12);
+            const bool up = -c1 - c12 > 1.0;
+            const double r = up ? 0.0 : -1.0;
+            s.tick += 1;
+            s.ep_length += 1;
+            s.ep_return = s.ep_return + r;
+            reward = (float)r;
+            terminal = up || (v.max_steps > 0 && s.tick == v.max_steps);
+            s.done = terminal;
+            if (terminal) episode_account(v.fin[e], s.ep_return, s.ep_length, s.ep_return);
+        }
+        return terminal;
     }
 };
+struct AcrobotRollEnv : ControlRollEnv<AcrobotPhysics> {};
 
 }  // namespace pfa

@@ -19,64 +19,17 @@
 // below 1e-20 there), and the arithmetic is compiled without contraction — a fused multiply-add rounds once where the walker
 // rounds twice.
 #pragma once
-#include "common.hpp"
-#include "episode_fin.hpp"
-#include "philox.hpp"
+#include "control_env.hpp"
 
 namespace pfa {
 
-constexpr int kCartDP = 16;   // floats per observation row
 constexpr double kCartXLimit = 2.4, kCartThetaLimit = 0.20943951023931953;   // 12 * 2 * pi / 360 in f64
 
 struct CartPoleEnv {
     double x, x_dot, theta, theta_dot, ep_return;
     int episode, tick, done, ep_length;
 };
-struct CartPoleView {
-    CartPoleEnv *env;
-    EpisodeFin *fin;
-    int n, max_steps;
-    bool velocities;
-    uint32_t key0, key1;
-    long long env_offset;
-};
-__host__ __device__ inline size_t cartpole_state_bytes(int n) { return (size_t)n * (sizeof(CartPoleEnv) + sizeof(EpisodeFin)); }
-__host__ __device__ inline CartPoleView cartpole_view(void *state, const pfa_cartpole_config &c) {
-    CartPoleView v;
-    v.env = (CartPoleEnv *)state;
-    v.fin = (EpisodeFin *)((char *)state + (size_t)c.num_envs * sizeof(CartPoleEnv));
-    v.n = c.num_envs;
-    v.max_steps = c.max_steps;
-    v.velocities = c.velocities != 0;
-    v.key0 = (uint32_t)c.seed;
-    v.key1 = 0x4350u ^ (uint32_t)(c.seed >> 32);
-    v.env_offset = c.env_offset;
-    return v;
-}
-
-// What the entry points of the family refuse (cartpole.hip).
-int check_cartpole_config(const pfa_cartpole_config *c);
-
-__device__ __forceinline__ void cartpole_draw(const CartPoleView &v, int e, CartPoleEnv &s) {
-#pragma clang fp contract(off)
-    const u32x4 w = philox4x32_10((uint32_t)(v.env_offset + e), (uint32_t)s.episode, 0u, 0u, v.key0, v.key1);
-    constexpr double k = 1.0 / 4294967296.0;
-    s.x = -0.05 + 0.1 * ((double)w.x * k);
-    s.x_dot = -0.05 + 0.1 * ((double)w.y * k);
-    s.theta = -0.05 + 0.1 * ((double)w.z * k);
-    s.theta_dot = -0.05 + 0.1 * ((double)w.w * k);
-}
-
-__device__ __forceinline__ void cartpole_begin_episode(const CartPoleView &v, int e, CartPoleEnv &s, float &reward, bool &terminal) {
-    s.episode += 1;
-    s.tick = 0;
-    s.done = 0;
-    s.ep_length = 0;
-    s.ep_return = 0.0;
-    cartpole_draw(v, e, s);
-    reward = 0.0f;
-    terminal = false;
-}
+using CartPoleView = ControlView<CartPoleEnv>;
 
 // sin / cos of |theta| <= 0.21 as Horner polynomials in z = theta^2 (through theta^13 / theta^12)
 __device__ __forceinline__ void cartpole_sincos(double theta, double &sn, double &cs) {
@@ -138,35 +91,35 @@ __device__ __forceinline__ void cartpole_observe(const CartPoleView &v, const Ca
     row[3] = v.velocities ? (float)s.theta_dot : 0.0f;
 }
 
-// The env adapter (env_adapters.hpp), in the shape of MemoryRollEnv: the owner steps and writes the four observation values itself.
-struct CartPoleRollEnv {
-    using View = CartPoleView;
-    static View view(void *state, const pfa_cartpole_config &c) { return cartpole_view(state, c); }
-    static constexpr bool kRefresh = false;
-    struct Shared {};
-    CartPoleEnv s = {};
-    int last_fin = 0;
-
-    __device__ __forceinline__ void load(const View &v, int e, int, Shared &) { s = v.env[e]; }
-    __device__ __forceinline__ void step(const View &v, int e, int, Shared &, float *row, int action, float &reward, bool &terminal) {
-        last_fin = 0;
+// The physics traits of the family (control_env.hpp).
+struct CartPolePhysics {
+    using State = CartPoleEnv;
+    using Config = pfa_cartpole_config;
+    static constexpr const char *kName = "cartpole";
+    static constexpr int kObs = 4, kActions = 2;
+    static constexpr uint32_t kKeyTag = 0x4350u;   // 'CP'
+    static constexpr double kDrawLo = -0.05, kDrawWidth = 0.1;
+    __device__ __forceinline__ static void values(const State &s, double *d) { d[0] = s.x, d[1] = s.x_dot, d[2] = s.theta, d[3] = s.theta_dot; }
+    __device__ __forceinline__ static void set_values(State &s, double x, double x_dot, double theta, double theta_dot) {
+        s.x = x, s.x_dot = x_dot, s.theta = theta, s.theta_dot = theta_dot;
+    }
+    __device__ __forceinline__ static void observe(const CartPoleView &v, const State &s, float *row) { cartpole_observe(v, s, row); }
+    __device__ __forceinline__ static bool send(const CartPoleView &v, int e, State &s, int action, float *row, float &reward, bool &terminal) {
+        bool fin = false;
         if (s.done) {
-            cartpole_begin_episode(v, e, s, reward, terminal);
+            control_begin_episode<CartPolePhysics>(v, e, s);
+            reward = 0.0f;
+            terminal = false;
         } else {
             double fr, fs;
             int fl;
-            if (cartpole_step(v, s, action, reward, terminal, fr, fl, fs)) {
-                episode_account(v.fin[e], fr, fl, fs);
-                last_fin = 1;
-            }
+            fin = cartpole_step(v, s, action, reward, terminal, fr, fl, fs);
+            if (fin) episode_account(v.fin[e], fr, fl, fs);
         }
         cartpole_observe(v, s, row);
-    }
-    __device__ __forceinline__ void refresh(const View &, int, int, int, Shared &, float *) {}
-    __device__ __forceinline__ void store(const View &v, int e, int, Shared &) {
-        v.env[e] = s;
-        v.fin[e].last_fin = last_fin;
+        return fin;
     }
 };
+struct CartPoleRollEnv : ControlRollEnv<CartPolePhysics> {};
 
 }  // namespace pfa

@@ -172,15 +172,64 @@ __global__ void __launch_bounds__(256) env_send_kernel(typename Env::View v, int
     masks[e] = 1;
 }
 
-// Host side of a family's `*_send` entry point, which has checked its own config: `name` prefixes the error text.
-template <class Env>
-static int launch_env_send(const char *name, void *state, const typename Env::View &v, int stride, const int64_t *actions, float *obs,
-                           float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    PFA_REQUIRE(state && actions && obs && rewards && terminals && truncations && masks, "%s: null buffer", name);
-    hipLaunchKernelGGL(env_send_kernel<Env>, dim3((unsigned)((v.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, stride,
-                       (const long long *)actions, obs, rewards, terminals, truncations, masks);
+// The launch shape of every per-env protocol kernel: one thread per env, blocks of 256.
+template <class Kernel, class... Args>
+static int launch_per_env(Kernel kernel, int n, pfa_stream_t stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, args...);
     PFA_LAUNCH_CHECK();
     return 0;
+}
+
+// Host side of a family's `*_send` entry point, which has checked its own config: `family` names it in the error text.
+template <class Env>
+static int launch_env_send(const char *family, void *state, const typename Env::View &v, int stride, const int64_t *actions, float *obs,
+                           float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    PFA_REQUIRE(state && actions && obs && rewards && terminals && truncations && masks, "%s.send: null buffer", family);
+    return launch_per_env(env_send_kernel<Env>, v.n, stream, v, stride, (const long long *)actions, obs, rewards, terminals, truncations,
+                          masks);
+}
+
+// The protocol front of a family whose entry points take (state, config): what `pfa_<family>_state_bytes`, `_async_reset`, `_send`,
+// `_episode_stats` and `_last_infos` do, so that each of them is a one-line forward.  Beside the adapter's members above, such an Env
+// exposes
+//   Config, check(cfg)    the family's config type of the public header and what the entry points refuse of it (0 = fine)
+//   kName                 the family name in error texts
+//   state_bytes(n)        bytes of vecenv state for n envs
+//   stride(cfg)           floats per row of the live observation buffer
+// and `fin` in its View.  The reset kernel stays the family's own: (View, obs, rewards, terminals, truncations, masks).
+template <class Env>
+static size_t env_state_bytes(const typename Env::Config *cfg) {
+    return Env::check(cfg) ? 0 : Env::state_bytes(cfg->num_envs);
+}
+
+template <class Env, class Kernel>
+static int env_async_reset(Kernel reset_kernel, void *state, const typename Env::Config *cfg, float *obs, float *rewards,
+                           uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    if (int rc = Env::check(cfg)) return rc;
+    PFA_REQUIRE(state && obs && rewards && terminals && truncations && masks, "%s.async_reset: null buffer", Env::kName);
+    return launch_per_env(reset_kernel, cfg->num_envs, stream, Env::view(state, *cfg), obs, rewards, terminals, truncations, masks);
+}
+
+template <class Env>
+static int env_send(void *state, const typename Env::Config *cfg, const int64_t *actions, float *obs, float *rewards, uint8_t *terminals,
+                    uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    if (int rc = Env::check(cfg)) return rc;
+    return launch_env_send<Env>(Env::kName, state, Env::view(state, *cfg), Env::stride(*cfg), actions, obs, rewards, terminals, truncations,
+                                masks, stream);
+}
+
+template <class Env>
+static int env_episode_stats(void *state, const typename Env::Config *cfg, double *out4, int32_t reset, pfa_stream_t stream) {
+    if (int rc = Env::check(cfg)) return rc;
+    return launch_episode_stats(Env::kName, state, Env::view(state, *cfg).fin, cfg->num_envs, out4, reset, nullptr, stream);
+}
+
+template <class Env>
+static int env_last_infos(void *state, const typename Env::Config *cfg, uint8_t *finished, double *episode_return, int32_t *episode_length,
+                          double *score, pfa_stream_t stream) {
+    if (int rc = Env::check(cfg)) return rc;
+    return launch_episode_infos(Env::kName, state, Env::view(state, *cfg).fin, cfg->num_envs, finished, episode_return, episode_length, score,
+                                stream);
 }
 
 }  // namespace pfa

@@ -193,7 +193,6 @@ __global__ void __launch_bounds__(kLstmThreads) rollout_lstm_kernel(typename Env
 }
 
 int check_synth_config(const pfa_synth_config *c);   // synthetic.hip
-int check_tabular_config(const pfa_tabular_config *c);   // tabular.hip
 
 static int check_lstm_dims(const pfa_mlp_dims *d) {
     PFA_REQUIRE(d != nullptr, "lstm: null dims");
@@ -340,26 +339,34 @@ extern "C" int pfa_rollout_lstm_tabular(void *state, const pfa_tabular_config *c
                                                obs, rewards, terminals, truncations, masks, stream);
 }
 
+// The classic-control families (control_env.hpp): one row width, one Discrete head of the physics' action count.
+template <class Env>
+static int rollout_lstm_control(const char *name, void *state, const typename Env::Config *cfg, const float *params, const pfa_mlp_dims *dims,
+                                const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
+                                const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                                uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
+    constexpr int kActions = Env::Physics::kActions;
+    if (int rc = check_lstm_dims(dims)) return rc;
+    if (int rc = Env::check(cfg)) return rc;
+    PFA_REQUIRE(dims->num_actions == kActions, "%s: the policy must have one Discrete(%d) head (got %d actions)", name, kActions,
+                dims->num_actions);
+    PFA_REQUIRE(dims->obs_stride == kControlDP, "%s: observation rows are %d floats (got %d)", name, kControlDP, dims->obs_stride);
+    return launch_rollout_lstm<Env, kControlDP>(name, state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset, obs, rewards,
+                                                terminals, truncations, masks, stream);
+}
+
 extern "C" int pfa_rollout_lstm_cartpole(void *state, const pfa_cartpole_config *cfg, const float *params, const pfa_mlp_dims *dims,
                                          const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                                          const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                                          uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    if (int rc = check_lstm_dims(dims)) return rc;
-    if (int rc = check_cartpole_config(cfg)) return rc;
-    PFA_REQUIRE(dims->num_actions == 2, "rollout_lstm_cartpole: the policy must have one Discrete(2) head (got %d actions)", dims->num_actions);
-    PFA_REQUIRE(dims->obs_stride == kCartDP, "rollout_lstm_cartpole: observation rows are %d floats (got %d)", kCartDP, dims->obs_stride);
-    return launch_rollout_lstm<CartPoleRollEnv, kCartDP>("rollout_lstm_cartpole", state, cfg, params, dims, wpack, h, c, exp, noise, key,
-                                                         env_offset, obs, rewards, terminals, truncations, masks, stream);
+    return rollout_lstm_control<CartPoleRollEnv>("rollout_lstm_cartpole", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset,
+                                                 obs, rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_rollout_lstm_acrobot(void *state, const pfa_acrobot_config *cfg, const float *params, const pfa_mlp_dims *dims,
                                         const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                                         const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                                         uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    if (int rc = check_lstm_dims(dims)) return rc;
-    if (int rc = check_acrobot_config(cfg)) return rc;
-    PFA_REQUIRE(dims->num_actions == 3, "rollout_lstm_acrobot: the policy must have one Discrete(3) head (got %d actions)", dims->num_actions);
-    PFA_REQUIRE(dims->obs_stride == kAcroDP, "rollout_lstm_acrobot: observation rows are %d floats (got %d)", kAcroDP, dims->obs_stride);
-    return launch_rollout_lstm<AcrobotRollEnv, kAcroDP>("rollout_lstm_acrobot", state, cfg, params, dims, wpack, h, c, exp, noise, key,
-                                                        env_offset, obs, rewards, terminals, truncations, masks, stream);
+    return rollout_lstm_control<AcrobotRollEnv>("rollout_lstm_acrobot", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset,
+                                                obs, rewards, terminals, truncations, masks, stream);
 }

@@ -149,7 +149,7 @@ extern "C" int pfa_stochastic_async_reset(void *state, int32_t num_envs, float *
 extern "C" int pfa_stochastic_send(void *state, int32_t num_envs, double p, int32_t horizon, const int64_t *actions, float *obs,
                                    float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     PFA_REQUIRE(num_envs >= 1 && horizon >= 1, "stochastic.send: bad arguments");
-    return launch_env_send<StochasticRollEnv>("stochastic.send", state, stochastic_view(state, num_envs, p, horizon), kStoDP, actions, obs,
+    return launch_env_send<StochasticRollEnv>("stochastic", state, stochastic_view(state, num_envs, p, horizon), kStoDP, actions, obs,
                                               rewards, terminals, truncations, masks, stream);
 }
 

@@ -120,7 +120,7 @@ extern "C" int pfa_synth_async_reset(void *state, const pfa_synth_config *cfg, f
 extern "C" int pfa_synth_send(void *state, const pfa_synth_config *cfg, const int64_t *actions, float *obs, float *rewards,
                               uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     if (int rc = check_synth_config(cfg)) return rc;
-    return launch_env_send<SynthRollEnv>("synth.send", state, synth_view(state, *cfg), cfg->obs_stride, actions, obs, rewards, terminals,
+    return launch_env_send<SynthRollEnv>("synth", state, synth_view(state, *cfg), cfg->obs_stride, actions, obs, rewards, terminals,
                                          truncations, masks, stream);
 }
 

@@ -57,37 +57,25 @@ int check_tabular_config(const pfa_tabular_config *c) {
 
 using namespace pfa;
 
-extern "C" size_t pfa_tabular_state_bytes(const pfa_tabular_config *cfg) {
-    return check_tabular_config(cfg) ? 0 : tabular_state_bytes(cfg->num_envs);
-}
+extern "C" size_t pfa_tabular_state_bytes(const pfa_tabular_config *cfg) { return env_state_bytes<TabularRollEnv>(cfg); }
 
 extern "C" int pfa_tabular_async_reset(void *state, const pfa_tabular_config *cfg, float *obs, float *rewards, uint8_t *terminals,
                                        uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    if (int rc = check_tabular_config(cfg)) return rc;
-    PFA_REQUIRE(state && obs && rewards && terminals && truncations && masks, "tabular.async_reset: null buffer");
-    hipLaunchKernelGGL(tabular_reset_kernel, dim3((unsigned)((cfg->num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       tabular_view(state, *cfg), obs, rewards, terminals, truncations, masks);
-    PFA_LAUNCH_CHECK();
-    return 0;
+    return env_async_reset<TabularRollEnv>(tabular_reset_kernel, state, cfg, obs, rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_tabular_send(void *state, const pfa_tabular_config *cfg, const int64_t *actions, float *obs, float *rewards,
                                 uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
-    if (int rc = check_tabular_config(cfg)) return rc;
-    return launch_env_send<TabularRollEnv>("tabular.send", state, tabular_view(state, *cfg), cfg->obs_stride, actions, obs, rewards,
-                                           terminals, truncations, masks, stream);
+    return env_send<TabularRollEnv>(state, cfg, actions, obs, rewards, terminals, truncations, masks, stream);
 }
 
 extern "C" int pfa_tabular_episode_stats(void *state, const pfa_tabular_config *cfg, double *out4, int32_t reset, pfa_stream_t stream) {
-    if (int rc = check_tabular_config(cfg)) return rc;
-    return launch_episode_stats("tabular", state, tabular_view(state, *cfg).fin, cfg->num_envs, out4, reset, nullptr, stream);
+    return env_episode_stats<TabularRollEnv>(state, cfg, out4, reset, stream);
 }
 
 extern "C" int pfa_tabular_last_infos(void *state, const pfa_tabular_config *cfg, uint8_t *finished, double *episode_return,
                                       int32_t *episode_length, double *score, pfa_stream_t stream) {
-    if (int rc = check_tabular_config(cfg)) return rc;
-    return launch_episode_infos("tabular", state, tabular_view(state, *cfg).fin, cfg->num_envs, finished, episode_return, episode_length,
-                                score, stream);
+    return env_last_infos<TabularRollEnv>(state, cfg, finished, episode_return, episode_length, score, stream);
 }
 
 extern "C" int pfa_tabular_debug_states(void *state, const pfa_tabular_config *cfg, int32_t *out5, pfa_stream_t stream) {

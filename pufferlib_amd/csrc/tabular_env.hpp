@@ -149,8 +149,15 @@ __device__ __forceinline__ void tabular_copy_chunk(const TabularView &v, int sta
 
 // The env adapter (env_adapters.hpp), in the shape of SynthRollEnv: the owner steps and leaves the new state index in Shared, the 16
 // lanes of the env then copy its observation row, 16 values each.
+int check_tabular_config(const pfa_tabular_config *c);   // tabular.hip
+
 struct TabularRollEnv {
     using View = TabularView;
+    using Config = pfa_tabular_config;
+    static constexpr const char *kName = "tabular";
+    static int check(const Config *c) { return check_tabular_config(c); }
+    static size_t state_bytes(int n) { return tabular_state_bytes(n); }
+    static int stride(const Config &c) { return c.obs_stride; }
     static View view(void *state, const pfa_tabular_config &c) { return tabular_view(state, c); }
     static constexpr bool kRefresh = true;
     struct Shared {

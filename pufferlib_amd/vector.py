@@ -1170,7 +1170,48 @@ class TabularSpec(_SimpleSpec):
                                   emulated_observation_dtype=np.dtype((np.float32, (mdp.obs_dim,))))
 
 
-class Tabular(_DeviceVecEnv):
+class _CounterSeededVecEnv(_DeviceVecEnv):
+    """Base of the families that take (state, config) and draw from Philox counters keyed by (seed, global env, episode, ...): there is
+    no tape, envs `env_offset ..` of a larger vecenv are reproduced exactly, and episodes end on different sends in different envs.
+    A subclass provides ``ABI`` and ``_config()``: the family's config struct (its `seed` and `env_offset` are written by every
+    reset), after setting ``obs_dim`` / ``observations``.  Every entry point is addressed by its name: ABI + '_async_reset', ...,
+    'pfa_rollout_mlp_<family>' and, where the class declares ROLLOUT_MLP_VIEW, 'pfa_rollout_mlp_view_<family>'."""
+    SEEDED = True
+
+    def _alloc_state(self):
+        import torch
+        self.cfg = self._config()
+        nbytes = self._entry('_state_bytes')(C.byref(self.cfg))
+        if nbytes == 0:
+            raise APIUsageError(self.L.pfa_last_error().decode())
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._send_entry = self._entry('_send')     # looked up once: the stepwise path calls it every step
+
+    def _entry(self, suffix):
+        return getattr(self.L, self.ABI + suffix)
+
+    def _finishing_send(self, sends):
+        return True         # episodes end on different sends in different envs
+
+    def _k_reset(self, seed):
+        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.cfg.env_offset = int(self.env_offset)
+        _lib.check(self._entry('_async_reset')(*self._state_args(), *self._live(), _lib.stream_handle()), 'async_reset')
+
+    def _k_send(self, actions):
+        _lib.check(self._send_entry(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()), 'send')
+
+    def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
+        """clean_pufferl.evaluate's T-step loop as one persistent kernel over the flat 128-wide parameters `fp`, or over `view`: the
+        pfa_mlp_view of a Default of another width (general.tile_view), for the families that declare ROLLOUT_MLP_VIEW."""
+        name = ('rollout_mlp_' if view is None else 'rollout_mlp_view_') + self.ABI[len('pfa_'):]
+        policy = (_lib.ptr(fp.flat), C.byref(fp.dims)) if view is None else (C.byref(view),)
+        _lib.check(getattr(self.L, 'pfa_' + name)(*self._state_args(), *policy, C.byref(experience.c), _lib.ptr(noise), C.byref(key),
+                                                  self.env_offset, *self._live(), stream), name)
+        self.sends += experience.horizon
+
+
+class Tabular(_CounterSeededVecEnv):
     """Device-resident vecenv of N copies of one user-given `TabularMDP` (csrc/tabular_env.hpp, csrc/tabular.hip): the tables are
     uploaded once and walked by the kernels; randomness is counter-based — Philox keyed by (seed, global env, episode, tick) — so there
     is no tape and envs `env_offset ..` of a larger vecenv are reproduced exactly.  It has a fused rollout kernel for either policy (up
@@ -1178,7 +1219,6 @@ class Tabular(_DeviceVecEnv):
     info_mode 'sync' every send reads the finished flags back (one small D2H), in 'lazy' none does."""
     FAMILY = 'tabular'
     ABI = 'pfa_tabular'
-    SEEDED = True
     CONFIG_NAME = 'Tabular '
     ROLLOUT_LSTM = 'pfa_rollout_lstm_tabular'
 
@@ -1209,7 +1249,7 @@ class Tabular(_DeviceVecEnv):
         self.obs_stride = stride
         return TabularSpec(mdp)
 
-    def _alloc_state(self):
+    def _config(self):
         import torch
         mdp, dev = self.driver_env.mdp, self.device
         self.mdp = mdp
@@ -1226,33 +1266,10 @@ class Tabular(_DeviceVecEnv):
                            score=None if mdp.score is None else up(mdp.score), obs=up(obs), start_states=up(mdp.start_states),
                            start_cum=up(mdp.start_cum, True))
         t = self.tables
-        self.cfg = _lib.TabularConfig(self.num_agents, mdp.num_states, mdp.num_actions, mdp.num_outcomes, mdp.num_starts, mdp.obs_dim,
-                                      self.obs_stride, mdp.horizon, 0, self.env_offset,
-                                      *(None if t[k] is None else t[k].data_ptr()
-                                        for k in ('next', 'cum', 'reward', 'terminal', 'score', 'obs', 'start_states', 'start_cum')))
-        nbytes = self.L.pfa_tabular_state_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise APIUsageError(self.L.pfa_last_error().decode())
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-
-    def _finishing_send(self, sends):
-        return True         # episodes end on different sends in different envs
-
-    def _k_reset(self, seed):
-        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.cfg.env_offset = int(self.env_offset)
-        _lib.check(self.L.pfa_tabular_async_reset(_lib.ptr(self.state), C.byref(self.cfg), *self._live(), _lib.stream_handle()), 'async_reset')
-
-    def _k_send(self, actions):
-        _lib.check(self.L.pfa_tabular_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
-                   'send')
-
-    def fused_rollout_mlp(self, fp, experience, noise, key, stream):
-        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/tabular.hip)."""
-        _lib.check(self.L.pfa_rollout_mlp_tabular(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
-                                                  C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
-                                                  stream), 'rollout_mlp_tabular')
-        self.sends += experience.horizon
+        return _lib.TabularConfig(self.num_agents, mdp.num_states, mdp.num_actions, mdp.num_outcomes, mdp.num_starts, mdp.obs_dim,
+                                  self.obs_stride, mdp.horizon, 0, self.env_offset,
+                                  *(None if t[k] is None else t[k].data_ptr()
+                                    for k in ('next', 'cum', 'reward', 'terminal', 'score', 'obs', 'start_states', 'start_cum')))
 
     def debug_states(self):
         """[N][5] int32: (state, episode, tick, done, ep_length) of every env — test introspection."""
@@ -1261,6 +1278,29 @@ class Tabular(_DeviceVecEnv):
         _lib.check(self.L.pfa_tabular_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(out), _lib.stream_handle()),
                    'debug_states')
         return out.cpu().numpy()
+
+
+class _ControlVecEnv(_CounterSeededVecEnv):
+    """What the classic-control families share (csrc/control_env.hpp): a config of (max_steps, velocities), OBS_DIM real-valued
+    observation columns of the 16-float row, and four f64 state values per env."""
+    NAMES, DEFAULTS = ('max_steps', 'velocities'), (500, True)
+    OBS_DIM = 0
+
+    def _config(self):
+        sp = self.driver_env
+        self.obs_dim = self.OBS_DIM
+        self.observations = self.obs_buf[:, :self.OBS_DIM]
+        return _lib.ControlConfig(self.num_agents, sp.max_steps, 1 if sp.velocities else 0, 0, 0, self.env_offset)
+
+    def debug_states(self):
+        """([N][4] float64: the four state values in the order of the family's state struct (CartPole: x, x_dot, theta, theta_dot;
+        Acrobot: th1, th2, w1, w2); [N][4] int32: episode, tick, done, ep_length) — test introspection."""
+        import torch
+        states = torch.zeros(self.num_agents, 4, dtype=torch.float64, device=self.device)
+        counters = torch.zeros(self.num_agents, 4, dtype=torch.int32, device=self.device)
+        _lib.check(self._entry('_debug_states')(*self._state_args(), _lib.ptr(states), _lib.ptr(counters), _lib.stream_handle()),
+                   'debug_states')
+        return states.cpu().numpy(), counters.cpu().numpy()
 
 
 def make_cartpole(max_steps=500, velocities=True, **kwargs):
@@ -1284,66 +1324,21 @@ class CartPoleSpec(_SimpleSpec):
         self.emulated = namespace(observation_dtype=np.dtype(np.float32), emulated_observation_dtype=np.dtype((np.float32, (4,))))
 
 
-class CartPole(_DeviceVecEnv):
+class CartPole(_ControlVecEnv):
     """Device-resident vecenv of N classic-control cart-poles (csrc/cartpole_env.hpp, csrc/cartpole.hip): f64 dynamics, real-valued
     observations.  The start states are counter-based — Philox keyed by (seed, global env, episode) — so there is no tape and envs
     `env_offset ..` of a larger vecenv are reproduced exactly.  It has a fused rollout kernel for the recurrent policy and for
     Default at every tile width (64 / 128 / 256 / 512).  Episodes end on different sends in different envs: in info_mode 'sync' every
     send reads the finished flags back (one small D2H), in 'lazy' none does."""
-    FAMILY, NAMES, DEFAULTS = 'cartpole', ('max_steps', 'velocities'), (500, True)
+    FAMILY = 'cartpole'
     ABI = 'pfa_cartpole'
-    SEEDED = True
     CONFIG_NAME = 'CartPole '
     ROLLOUT_LSTM = 'pfa_rollout_lstm_cartpole'
     ROLLOUT_MLP_VIEW = True
+    OBS_DIM = 4
 
     def _spec(self, max_steps, velocities):
         return CartPoleSpec(max_steps, velocities)
-
-    def _alloc_state(self):
-        import torch
-        sp = self.driver_env
-        self.obs_dim = 4
-        self.observations = self.obs_buf[:, :4]
-        self.cfg = _lib.CartPoleConfig(self.num_agents, sp.max_steps, 1 if sp.velocities else 0, 0, 0, self.env_offset)
-        nbytes = self.L.pfa_cartpole_state_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise APIUsageError(self.L.pfa_last_error().decode())
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-
-    def _finishing_send(self, sends):
-        return True         # episodes end on different sends in different envs
-
-    def _k_reset(self, seed):
-        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.cfg.env_offset = int(self.env_offset)
-        _lib.check(self.L.pfa_cartpole_async_reset(_lib.ptr(self.state), C.byref(self.cfg), *self._live(), _lib.stream_handle()), 'async_reset')
-
-    def _k_send(self, actions):
-        _lib.check(self.L.pfa_cartpole_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
-                   'send')
-
-    def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
-        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/cartpole.hip) over the flat 128-wide parameters `fp`, or
-        over `view`: the pfa_mlp_view of a Default of another width (general.tile_view)."""
-        if view is not None:
-            _lib.check(self.L.pfa_rollout_mlp_view_cartpole(_lib.ptr(self.state), C.byref(self.cfg), C.byref(view), C.byref(experience.c),
-                                                            _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(), stream),
-                       'rollout_mlp_view_cartpole')
-        else:
-            _lib.check(self.L.pfa_rollout_mlp_cartpole(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
-                                                       C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
-                                                       stream), 'rollout_mlp_cartpole')
-        self.sends += experience.horizon
-
-    def debug_states(self):
-        """([N][4] float64: x, x_dot, theta, theta_dot; [N][4] int32: episode, tick, done, ep_length) — test introspection."""
-        import torch
-        states = torch.zeros(self.num_agents, 4, dtype=torch.float64, device=self.device)
-        counters = torch.zeros(self.num_agents, 4, dtype=torch.int32, device=self.device)
-        _lib.check(self.L.pfa_cartpole_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(states), _lib.ptr(counters),
-                                                    _lib.stream_handle()), 'debug_states')
-        return states.cpu().numpy(), counters.cpu().numpy()
 
 
 def make_acrobot(max_steps=500, velocities=True, **kwargs):
@@ -1366,67 +1361,22 @@ class AcrobotSpec(_SimpleSpec):
         self.emulated = namespace(observation_dtype=np.dtype(np.float32), emulated_observation_dtype=np.dtype((np.float32, (6,))))
 
 
-class Acrobot(_DeviceVecEnv):
+class Acrobot(_ControlVecEnv):
     """Device-resident vecenv of N classic-control acrobots (csrc/acrobot_env.hpp, csrc/acrobot.hip): f64 RK4 dynamics, observations
     (cos th1, sin th1, cos th2, sin th2, w1, w2), three torques, reward -1 per step until the tip swings above the bar.  The start
     states are counter-based — Philox keyed by (seed, global env, episode) — so there is no tape and envs `env_offset ..` of a larger
     vecenv are reproduced exactly.  It has a fused rollout kernel for the recurrent policy and for Default at every tile width (64 /
     128 / 256 / 512).  Episodes end on different sends in different envs: in info_mode 'sync' every send reads the finished flags back
     (one small D2H), in 'lazy' none does."""
-    FAMILY, NAMES, DEFAULTS = 'acrobot', ('max_steps', 'velocities'), (500, True)
+    FAMILY = 'acrobot'
     ABI = 'pfa_acrobot'
-    SEEDED = True
     CONFIG_NAME = 'Acrobot '
     ROLLOUT_LSTM = 'pfa_rollout_lstm_acrobot'
     ROLLOUT_MLP_VIEW = True
+    OBS_DIM = 6
 
     def _spec(self, max_steps, velocities):
         return AcrobotSpec(max_steps, velocities)
-
-    def _alloc_state(self):
-        import torch
-        sp = self.driver_env
-        self.obs_dim = 6
-        self.observations = self.obs_buf[:, :6]
-        self.cfg = _lib.AcrobotConfig(self.num_agents, sp.max_steps, 1 if sp.velocities else 0, 0, 0, self.env_offset)
-        nbytes = self.L.pfa_acrobot_state_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise APIUsageError(self.L.pfa_last_error().decode())
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-
-    def _finishing_send(self, sends):
-        return True         # episodes end on different sends in different envs
-
-    def _k_reset(self, seed):
-        self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.cfg.env_offset = int(self.env_offset)
-        _lib.check(self.L.pfa_acrobot_async_reset(_lib.ptr(self.state), C.byref(self.cfg), *self._live(), _lib.stream_handle()), 'async_reset')
-
-    def _k_send(self, actions):
-        _lib.check(self.L.pfa_acrobot_send(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(actions), *self._live(), _lib.stream_handle()),
-                   'send')
-
-    def fused_rollout_mlp(self, fp, experience, noise, key, stream, view=None):
-        """clean_pufferl.evaluate's T-step loop as one persistent kernel (csrc/acrobot.hip) over the flat 128-wide parameters `fp`, or
-        over `view`: the pfa_mlp_view of a Default of another width (general.tile_view)."""
-        if view is not None:
-            _lib.check(self.L.pfa_rollout_mlp_view_acrobot(_lib.ptr(self.state), C.byref(self.cfg), C.byref(view), C.byref(experience.c),
-                                                           _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(), stream),
-                       'rollout_mlp_view_acrobot')
-        else:
-            _lib.check(self.L.pfa_rollout_mlp_acrobot(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(fp.flat), C.byref(fp.dims),
-                                                      C.byref(experience.c), _lib.ptr(noise), C.byref(key), self.env_offset, *self._live(),
-                                                      stream), 'rollout_mlp_acrobot')
-        self.sends += experience.horizon
-
-    def debug_states(self):
-        """([N][4] float64: th1, th2, w1, w2; [N][4] int32: episode, tick, done, ep_length) — test introspection."""
-        import torch
-        states = torch.zeros(self.num_agents, 4, dtype=torch.float64, device=self.device)
-        counters = torch.zeros(self.num_agents, 4, dtype=torch.int32, device=self.device)
-        _lib.check(self.L.pfa_acrobot_debug_states(_lib.ptr(self.state), C.byref(self.cfg), _lib.ptr(states), _lib.ptr(counters),
-                                                   _lib.stream_handle()), 'debug_states')
-        return states.cpu().numpy(), counters.cpu().numpy()
 
     def debug_set_states(self, states, counters):
         """The inverse of debug_states(), for tests that put envs on the rare branches on purpose (an angle about to wrap, a velocity

@@ -13,6 +13,7 @@ from adam_moments import assert_moments_match
 
 sys.path.insert(0, os.path.dirname(__file__))
 import acrobot_reference as ar  # noqa: E402
+from control_cases import expected_form as _expected_form, policy as _policy, snapshot as _snapshot, u32 as _u32, u64 as _u64  # noqa: E402
 from test_acrobot_cpu import RANDOM_BASELINE, SET_AT, scripted_run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +26,6 @@ N, T = 40, 24                         # three 16-env workgroups, the last one ha
 def _make(n, max_steps=500, velocities=True, **kw):
     from pufferlib_amd import vector
     return vector.make(vector.make_acrobot, env_kwargs=dict(max_steps=max_steps, velocities=velocities), num_envs=n, backend=vector.Acrobot, **kw)
-
-
-def _u32(x):
-    return np.ascontiguousarray(x).view(np.uint32)
-
-
-def _u64(x):
-    return np.ascontiguousarray(x).view(np.uint64)
 
 
 @pytest.mark.parametrize('setting', [dict(max_steps=500), dict(max_steps=12), dict(velocities=False)], ids=['limit500', 'limit12', 'no_velocities'])
@@ -93,29 +86,6 @@ def test_protocol_path_equals_the_walker_bit_for_bit(setting):
             part.recv()
             part.send(ar.pump_actions(st[16:]))
         assert (pcn[:, 0] == 1).all()
-
-
-def _snapshot(data, vec, recurrent=False):
-    e = data.experience
-    out = [x.clone() for x in (e.obs, e.actions, e.logprobs, e.values, e.rewards, e.dones, vec.obs_buf, vec.rewards, vec.terminals_u8,
-                                vec.state)]
-    if recurrent:
-        out += [data.lstm_engine.lstm_h.clone(), data.lstm_engine.lstm_c.clone()]
-    return out + [torch.as_tensor(x) for x in vec.debug_states()]
-
-
-def _policy(vec, hidden, recurrent):
-    from pufferlib_amd import cleanrl, models
-    env = getattr(vec, 'driver_env', vec)          # a vecenv, or the spaces a policy is to be built for
-    base = models.Default(env, hidden_size=hidden)
-    return cleanrl.RecurrentPolicy(models.LSTMWrapper(env, base)) if recurrent else cleanrl.Policy(base)
-
-
-def _expected_form(data, recurrent):
-    from pufferlib_amd import clean_pufferl
-    gen = data.gen_engine
-    form = clean_pufferl.rollout_form(type(data.vecenv), gen is not None, recurrent, gen is not None and gen.mlp_view is not None)
-    assert form == (clean_pufferl.FUSED_LSTM if recurrent else clean_pufferl.FUSED_MLP)
 
 
 def _branch_start(vec):

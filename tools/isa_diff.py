@@ -9,14 +9,20 @@ and the blanks in front of a comment (the column padding behind a label depends 
 kernel is missing on either side or differs.
 With --opcodes in front, every kernel that differs also gets a line for changes that may re-order a kernel but must keep its
 instructions (a helper function taken out of it): instructions before -> after, the opcodes whose COUNT moved (_e32 / _e64 encodings
-of one opcode counted together), VGPRs, static LDS bytes and scratch bytes before -> after."""
+of one opcode counted together), VGPRs, static LDS bytes and scratch bytes before -> after.
+--rename OLD=NEW (any number, in front) compares kernel OLD of the old files with kernel NEW of the new ones: a kernel that became
+a template instantiation.  Inside the compared text the kernel's own symbol reads the same on both sides; an instantiation sits in
+a comdat `.section` of its own where the plain kernel had `.text`, so such a pair still "differs (code)" by that one directive, and
+--opcodes shows whether anything else moved."""
 import collections
 import re
 import sys
 
 
-def kernels(path):
+def kernels(path, rename=()):
     text = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid', open(path).read())
+    for old, new in rename:
+        text = re.sub(r'\b%s\b' % re.escape(old), new, text)
     text = re.sub(r'\.L([A-Za-z_]+?)\d+(_\d+)?\b', r'.L\1#\2', text)
     text = re.sub(r'\bBB\d+_(\d+)\b', r'BB#_\1', text)   # the same labels inside the compiler's comments ("Loop: Header=BB28_3")
     text = re.sub(r'[ \t]+;', ' ;', text)                # comments are padded to a column: an ordinal of 9 -> 10 moves the padding behind its labels
@@ -56,10 +62,16 @@ def opcode_line(a, b):
 
 def main(argv):
     bad = 0
-    with_opcodes = argv[:1] == ['--opcodes']
-    argv = argv[1:] if with_opcodes else argv
+    with_opcodes, rename = False, []
+    while argv and argv[0].startswith('--'):
+        if argv[0] == '--opcodes':
+            with_opcodes, argv = True, argv[1:]
+        elif argv[0] == '--rename':
+            rename, argv = rename + [tuple(argv[1].split('=', 1))], argv[2:]
+        else:
+            sys.exit(f'unknown option {argv[0]}')
     for old, new in zip(argv[0::2], argv[1::2]):
-        a, b = kernels(old), kernels(new)
+        a, b = kernels(old, rename), kernels(new)
         differ = [(k, [p for p in a[k] if a[k][p] != b[k].get(p)]) for k in sorted(set(a) & set(b)) if a[k] != b[k]]
         for k in sorted(set(a) ^ set(b)):
             print(f'  only in {old if k in a else new}: {k}')
