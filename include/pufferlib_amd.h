@@ -658,6 +658,11 @@ int pfa_ppo_mlp_train_logged(const pfa_experience *exp, int64_t batch_rows, floa
  * global_mb_rows), tail16 receives the loss sums as in pfa_ppo_mlp_grad.  workspace: pfa_ppo_wide_workspace_bytes(params).
  * Clip + Adam: pfa_adam_clip_step on the flat buffer.  pfa_ppo_wide_supported: 1 when the shape is one this kernel takes. */
 int pfa_ppo_wide_supported(const pfa_mlp_view *view);
+/* Which gradient kernel pfa_ppo_wide_grad launches for this view and local minibatch rows under the current product form
+ * (pfa_igemm_set_products), the counterpart of pfa_ppo_mlp_grad_path: 0 = ppo_wide_grad_kernel (exact fp32 MFMA chains),
+ * 1 = ppo_wide_grad_bf16_kernel (csrc/ppo_wide_bf16.hip: the opt-in form at hidden 256 on rows of 32 / 64 floats with minibatches of
+ * whole 32-row tiles; everything else stays on 0).  Both leave the same partials in the same workspace. */
+int pfa_ppo_wide_grad_path(const pfa_mlp_view *view, int64_t mb_rows);
 size_t pfa_ppo_wide_workspace_bytes(const pfa_mlp_view *view);
 int pfa_ppo_wide_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb, const pfa_mlp_view *params, const pfa_mlp_view *grads,
                       float *tail16, const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, void *workspace,

@@ -48,8 +48,10 @@ __version__ = '0.1.0'
 def set_matrix_products(form):
     """How the fp32 products of the matrix kernels are formed, process-wide (no reference counterpart: torch leaves this to its BLAS).
     'fp32' (default): exact fp32 MFMA products.  'bf16x6': every fp32 operand as three bf16 pieces, each product as its six partial
-    products on the bf16 matrix path with fp32 accumulation — the conv / linear rows form (csrc/igemm.hip) and the fused 128-wide
-    gradient step on 7x7-grid rows (csrc/ppo_bf16.hpp).  Results agree to the tests' 1e-5, not bit for bit.  Also settable with the
+    products on the bf16 matrix path with fp32 accumulation — the conv / linear rows form (csrc/igemm.hip), the fused 128-wide
+    gradient step on 7x7-grid rows (csrc/ppo_bf16.hpp) and the fused gradient step of Default(hidden_size=256) on rows of 32 / 64
+    floats with minibatches of whole 32-row tiles (csrc/ppo_wide_bf16.hip: 93 us per launch against 116 on the bench shape; hidden 64 /
+    512, 16-float rows and other minibatch sizes keep their fp32 kernel).  Results agree to the tests' 1e-5, not bit for bit.  Also settable with the
     environment variable PFA_MATRIX_PRODUCTS before the library is first used."""
     from . import _lib
     if form not in ('fp32', 'bf16x6'):

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "mlp_tile.hpp"
 #include "ppo_tile.hpp"
+#include "ppo_wide.hpp"
 #include "rollout_tile.hpp"
 
 namespace pfa {
@@ -52,26 +53,6 @@ __host__ __device__ constexpr bool wide_small_pass(int ms, int kku, int nw) { re
 // the same two barriers per tile — the streams add their accumulators up through LDS at the end (fixed order) and the workgroup
 // writes ONE partial: half (a quarter) of the partial traffic in both launches.
 __host__ __device__ constexpr int wide_streams(int ms, int kku, int nw) { return nw == 4 ? wide_wgs_per_cu(ms, kku) : 1; }
-
-// One workgroup partial (floats), fragment order.  MT = H / 16 hidden tiles, KTM 16-column tiles of dW1 on MFMA (+ COL: the
-// one trailing column 16 KTM, for rows of 16 KTM + 1 real columns like the 7x7 grid's 49).
-struct WideLayout {
-    int MT, KTM, col;
-    int kCol, kDw2, kDb1, kDb2, kStats, kCount;
-};
-__host__ __device__ inline WideLayout wide_layout(int hidden, int ktm, bool col) {
-    WideLayout l;
-    l.MT = hidden / 16;
-    l.KTM = ktm;
-    l.col = col ? 1 : 0;
-    l.kCol = ktm * l.MT * 256;                 // ((kt*MT + m)*4 + r)*64 + lane -> W1[16m + c][16kt + 4g + r]
-    l.kDw2 = l.kCol + (col ? hidden : 0);      // u = 16m + c -> W1[u][16 KTM]
-    l.kDb1 = l.kDw2 + l.MT * 256;              // (m*4 + r)*64 + lane -> W2v[o = c][16m + 4g + r]
-    l.kDb2 = l.kDb1 + hidden;
-    l.kStats = l.kDb2 + kOut;
-    l.kCount = l.kStats + kNumStats;
-    return l;
-}
 
 // LDS map (floats): two X tiles, the four partial out^T tiles, one hidden-slice patch and one dout patch per wave, the W2v
 // B-fragment table and the encoder bias.
@@ -484,8 +465,8 @@ struct WideShape {
     int kku, ktm;
     bool col;
 };
-static int wide_shape(const pfa_mlp_view *p, WideShape *s) {
-    PFA_REQUIRE(p && p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv, "ppo.wide: null view / tensor");
+static int wide_shape(const pfa_mlp_view *p, WideShape *s, bool tensors = true) {   // tensors = false: the dimensions alone
+    PFA_REQUIRE(p && (!tensors || (p->w1 && p->b1 && p->w2 && p->b2 && p->wv && p->bv)), "ppo.wide: null view / tensor");
     PFA_REQUIRE(p->hidden == 64 || p->hidden == 256 || p->hidden == 512, "ppo.wide: hidden %d is not one of 64 / 256 / 512 (128: pfa_ppo_mlp_grad)", p->hidden);
     PFA_REQUIRE(p->obs_stride == 16 || p->obs_stride == 32 || p->obs_stride == 64, "ppo.wide: obs_stride %d is not one of 16 / 32 / 64", p->obs_stride);
     PFA_REQUIRE(p->obs_dim >= 1 && p->obs_dim <= p->obs_stride && p->ldw1 >= p->obs_dim, "ppo.wide: obs_dim %d / ldw1 %d out of range", p->obs_dim, p->ldw1);
@@ -542,6 +523,11 @@ extern "C" int pfa_ppo_wide_supported(const pfa_mlp_view *view) {
     return wide_shape(view, &s) == 0 ? 1 : 0;
 }
 
+extern "C" int pfa_ppo_wide_grad_path(const pfa_mlp_view *view, int64_t mb_rows) {
+    WideShape s;   // (a view pfa_ppo_wide_grad would refuse takes no kernel: 0)
+    return wide_shape(view, &s, false) == 0 && wide_bf16_takes(view->hidden, view->obs_stride, mb_rows) ? 1 : 0;
+}
+
 extern "C" int pfa_ppo_wide_grad(const pfa_experience *exp, int64_t batch_rows, int32_t mb, const pfa_mlp_view *params, const pfa_mlp_view *grads,
                                  float *tail16, const pfa_ppo_hparams *hp, const double *adv_stats, int64_t global_mb_rows, void *workspace,
                                  pfa_stream_t stream) {
@@ -559,8 +545,16 @@ extern "C" int pfa_ppo_wide_grad(const pfa_experience *exp, int64_t batch_rows, 
     RowMap map{mb, hp->num_minibatches, hp->bptt_horizon};
     const MlpView pv{params->w1, params->ldw1, params->obs_dim, params->b1, params->w2, params->b2, params->wv, params->bv, params->num_actions, params->hidden};
     float *partials = (float *)workspace;
-    const int grid = wide_grid(mbs, params->hidden, s.kku);
-    {
+    // the opt-in bf16x6 product form (ppo_wide_bf16.hip): the same partial layout, never more partials than wide_slots
+    const bool bf16 = wide_bf16_takes(params->hidden, params->obs_stride, mbs);
+    const int grid = bf16 ? wide_bf16_grid(mbs) : wide_grid(mbs, params->hidden, s.kku);
+    if (bf16) {
+        ScopedKernelTimer timer("ppo_wide_grad_bf16", (hipStream_t)stream);
+        if (int rc = wide_bf16_launch(grid, (hipStream_t)stream, *exp, map, (long long)mbs, pv, params->obs_stride, s.col, *hp, adv_stats,
+                                      (double)global_mb_rows, partials))
+            return rc;
+        PFA_LAUNCH_CHECK();
+    } else {
         ScopedKernelTimer timer("ppo_wide_grad", (hipStream_t)stream);
         auto launch = [&](auto hidden) {
             return wide_launch_rows<decltype(hidden)::value>(params->obs_stride, s.col, grid, (hipStream_t)stream, *exp, map, (long long)mbs, pv, *hp,

@@ -1,0 +1,136 @@
+"""pfa_ppo_wide_grad in the opt-in bf16x6 product form (csrc/ppo_wide_bf16.hip: hidden 256 on rows of 32 / 64 floats, minibatches of
+whole 32-row tiles) against the float64 gradient of tests/ppo_grad_reference.py — per tensor max |device - f64| <= max(4 e32, 1e-5
+max |f64|), a bound from the reference's own fp32 run — and the dispatch around it: which shapes take the kernel
+(pfa_ppo_wide_grad_path) and that the others compute, under the switch, the bits they compute without it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import ppo_grad_reference as R
+
+ROWS = ((25, 32), (49, 64), (64, 64))       # (obs_dim, stride): 32-float rows, the trimmed 7x7 grid, full 64-float rows
+# the first of 1, 2, 3, ... at which the float64 reference alone keeps every row 16 fp32 chain errors from each kink
+# (test_every_case_is_clear_of_the_kinks, no GPU); seed 1 unless listed here
+SEEDS = {'wide-bf16x6-h256-d49of64-96rows-mb1of2-bptt4': 2}
+
+
+def _case(tag, dim, stride, hidden=256, **kw):
+    return R.Case(tag, dim, stride, 8, 0, hidden=hidden, seed=SEEDS.get(tag, 1), **kw)
+
+
+def _bf16_cases():
+    """Per row shape: one 32-row tile; 96 rows as minibatch 1 of 2 with segments of 4 rows (three workgroups, the strided segment map).
+    Then norm_adv off and clip_vloss off."""
+    out = []
+    for dim, stride in ROWS:
+        out.append(_case(f'wide-bf16x6-h256-d{dim}of{stride}-32rows', dim, stride, rows=32))
+        out.append(_case(f'wide-bf16x6-h256-d{dim}of{stride}-96rows-mb1of2-bptt4', dim, stride, rows=96, nmb=2, mb=1, horizon=4))
+    out.append(_case('wide-bf16x6-h256-d49of64-no-norm-adv', 49, 64, rows=64, norm_adv=0))
+    out.append(_case('wide-bf16x6-h256-d25of32-no-clip-vloss', 25, 32, rows=64, clip_vloss=0))
+    return out
+
+
+def _fp32_cases():
+    """Shapes the switch must leave on the fp32 kernel: hidden 64, hidden 512, 16-float rows, a 48-row minibatch."""
+    return [_case('wide-stays-fp32-h64', 49, 64, hidden=64, rows=32), _case('wide-stays-fp32-h512', 49, 64, hidden=512, rows=32),
+            _case('wide-stays-fp32-16-float-rows', 9, 16, rows=32), _case('wide-stays-fp32-48rows', 49, 64, rows=48, nmb=2, mb=1, horizon=4)]
+
+
+BF16_CASES, FP32_CASES = _bf16_cases(), _fp32_cases()
+_ids = lambda cases: [pytest.param(c, id=c.tag) for c in cases]     # noqa: E731
+_refs = {}
+
+
+def test_wide_grad_path_names_the_kernel_of_every_shape():
+    """Host state only (no GPU): 1 for the bf16x6 cases under the switch, 0 for the shapes outside the form and for everything with
+    the switch off."""
+    from pufferlib_amd import _lib
+    L = _lib.lib()
+    path = lambda c: L.pfa_ppo_wide_grad_path(C.byref(_lib.MlpView(0, c.obs_dim, c.obs_dim, c.stride, c.hidden, c.actions, 0, 0, 0, 0, 0, 0)), c.rows)     # noqa: E731
+    try:
+        _lib.check(L.pfa_igemm_set_products(1), 'set_products')
+        assert [path(c) for c in BF16_CASES] == [1] * len(BF16_CASES) and [path(c) for c in FP32_CASES] == [0] * len(FP32_CASES)
+        view = lambda dim, a: C.byref(_lib.MlpView(0, dim, dim, 64, 256, a, 0, 0, 0, 0, 0, 0))     # noqa: E731
+        assert (L.pfa_ppo_wide_grad_path(view(49, 15), 32), L.pfa_ppo_wide_grad_path(view(49, 16), 32), L.pfa_ppo_wide_grad_path(view(65, 8), 32)) \
+            == (1, 0, 0), 'a view pfa_ppo_wide_grad refuses (16 actions, obs_dim > stride) takes no kernel'
+    finally:
+        _lib.check(L.pfa_igemm_set_products(0), 'set_products')
+    assert [path(c) for c in BF16_CASES + FP32_CASES] == [0] * len(BF16_CASES + FP32_CASES)
+
+
+def _reference(case):
+    if case.tag not in _refs:
+        torch.set_num_threads(4)
+        _refs[case.tag] = R.Reference(case)
+    return _refs[case.tag]
+
+
+@pytest.mark.parametrize('case', _ids(BF16_CASES))
+def test_every_case_is_clear_of_the_kinks(case):
+    """Reference.check_margins in float64, on the CPU: nothing has to be excluded from the comparison below."""
+    assert _reference(case).margins_ok()
+
+
+def _wide_grad(case, products):
+    """One pfa_ppo_wide_grad launch pair under `products` (0 fp32, 1 bf16x6), driven like test_wide_grad_matches_the_float64_gradient,
+    into a NaN-filled gradient buffer and a 0xFF-filled workspace with guard words behind both: (path, gradient + tail16 + guard,
+    workspace + guard, workspace bytes)."""
+    from pufferlib_amd import _lib
+    from test_gpu_ppo_grad_f64 import _Device
+    L = _lib.lib()
+    d = _Device(case)
+    flat = torch.as_tensor(case.flat_params(padded=False)).cuda()
+    count = flat.numel()
+    grads = torch.full((count + 16 + 64,), float('nan'), device='cuda')
+    sizes = [v.size for v in case.split_flat(np.zeros(count, np.float32), padded=False).values()]
+
+    def view(base):
+        ptrs = [base.data_ptr() + 4 * int(o) for o in np.cumsum([0] + sizes[:-1])]
+        return _lib.MlpView(ptrs[0], case.obs_dim, case.obs_dim, case.stride, case.hidden, case.actions, 0, *ptrs[1:])
+    pv, gv = view(flat), view(grads)
+    try:
+        _lib.check(L.pfa_igemm_set_products(products), 'set_products')
+        path = L.pfa_ppo_wide_grad_path(C.byref(pv), case.rows)
+        nbytes = int(L.pfa_ppo_wide_workspace_bytes(C.byref(pv)))
+        ws = torch.full((nbytes + 1024,), 0xFF, dtype=torch.uint8, device='cuda')
+        _lib.check(L.pfa_ppo_wide_grad(C.byref(d.exp), case.B, case.mb, C.byref(pv), C.byref(gv), grads.data_ptr() + 4 * count, C.byref(d.hp),
+                                       d.stats.data_ptr(), case.rows, ws.data_ptr(), None), 'ppo_wide_grad')
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(L.pfa_igemm_set_products(0), 'set_products')
+    return path, grads.cpu().numpy(), ws.cpu().numpy(), nbytes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', _ids(BF16_CASES))
+def test_wide_grad_bf16x6_matches_the_float64_gradient(case):
+    """All six tensors, the loss sums and the clipped count of ppo_wide_grad_bf16_kernel; W1's padding columns exactly zero (the view's
+    rows are obs_dim wide: nothing lands between them); nothing written behind the gradient's tail, behind the workspace, or into the
+    partial slots of workgroups that were not launched."""
+    ref = _reference(case)
+    path, g, ws, nbytes = _wide_grad(case, 1)
+    assert path == 1
+    count = g.size - 80
+    got = case.split_flat(g[:count], padded=False)
+    got['encoder.weight'] = np.pad(got['encoder.weight'], ((0, 0), (0, case.stride - case.obs_dim)))
+    bad = ref.failures(got)
+    assert bad == [], f'{case.tag}: {bad} beyond max(4 e32, 1e-5 max|f64|) of the float64 gradient (figures printed above)'
+    ref.check_sums(g[count:count + 16])
+    assert np.isnan(g[count + 16:]).all(), 'written behind the 16-float tail'
+    col = case.stride == 64 and case.obs_dim == 49                                  # wide_layout (csrc/ppo_wide.hpp)
+    ktm, mt = (3 if col else case.stride // 16), case.hidden // 16
+    partial = ktm * mt * 256 + (case.hidden if col else 0) + mt * 256 + case.hidden + 16 + 8
+    used = 4 * partial * (case.rows // 32)
+    assert used <= nbytes and (ws[used:] == 0xFF).all(), 'written outside the launched workgroups\' partials'
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', _ids(FP32_CASES))
+def test_shapes_outside_the_bf16x6_form_keep_the_fp32_kernel_bit_for_bit(case):
+    path1, g1, _, _ = _wide_grad(case, 1)
+    path0, g0, _, _ = _wide_grad(case, 0)
+    assert (path1, path0) == (0, 0)
+    assert np.array_equal(g1.view(np.uint32), g0.view(np.uint32))
+    assert np.isfinite(g0[:g0.size - 64]).all()
