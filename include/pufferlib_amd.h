@@ -737,7 +737,19 @@ int pfa_rollout_lstm_acrobot(void *state, const pfa_acrobot_config *cfg, const f
  * init_slot: where the carried-in state is read — 0: slot 0 of hs / cs as it is; k in 1..steps: slot k (the previous minibatch's final
  * state, clean_pufferl.py:188-191), copied into slot 0 by the kernel; < 0: zero state (lstm_state = None, :176), slot 0 zeroed.
  * backward with gate_bias_grad = enc_bias_grad = NULL leaves the per-workgroup column sums in `workspace` ([ceil(rows / 32)][640])
- * for the caller's own reduction (pfa_reduce_multi, kind 1). */
+ * for the caller's own reduction (pfa_reduce_multi, kind 1).
+ * The opt-in bf16x6 product form (pfa_igemm_set_products(1); csrc/lstm_seq_bf16.hip): pfa_lstm_seq_path — host state only, like
+ * pfa_ppo_mlp_grad_path — says which of the two kernels take it for a shape: bit 0 the forward, bit 1 the backward, 0 whenever the
+ * switch is off or the shape is not one pfa_lstm_seq_forward takes.  A direction whose bit is set READS ITS PACK ARGUMENT IN THE SPLIT
+ * FORM: three bf16 planes in A-fragment order, pfa_lstm_pack_split_bytes() bytes, 16-byte aligned; a direction whose bit is clear
+ * reads the fp32 pack as before.  Today only bit 0 is ever set (the backward kernel of the form measured slower than the fp32 one and
+ * is not built), so pfa_lstm_pack_split writes the forward's split pack alone and wpack_bwd is always an fp32 pack.  pfa_lstm_pack,
+ * pfa_lstm_pack_bwd and pfa_lstm_pack_both write fp32 packs whatever the switch says, and the rollout kernels always read those.
+ * Every other argument, buffer layout and the workspace keep their meaning; results agree with the fp32 kernels to the tests' bound
+ * against float64, not bit for bit (xe, the encoder output, does). */
+int pfa_lstm_seq_path(const pfa_mlp_dims *dims, int64_t rows);
+size_t pfa_lstm_pack_split_bytes(void);
+int pfa_lstm_pack_split(const float *params, const pfa_mlp_dims *dims, void *wsplit, pfa_stream_t stream);
 int pfa_lstm_pack_bwd(const float *params, const pfa_mlp_dims *dims, void *wpack_bwd, pfa_stream_t stream);
 int pfa_lstm_pack_both(const float *params, const pfa_mlp_dims *dims, void *wpack, void *wpack_bwd, pfa_stream_t stream);
 int pfa_lstm_seq_forward(const float *obs_tm, int64_t rows, int32_t steps, const float *params, const pfa_mlp_dims *dims,

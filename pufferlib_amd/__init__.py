@@ -51,7 +51,10 @@ def set_matrix_products(form):
     products on the bf16 matrix path with fp32 accumulation — the conv / linear rows form (csrc/igemm.hip), the fused 128-wide
     gradient step on 7x7-grid rows (csrc/ppo_bf16.hpp) and the fused gradient step of Default(hidden_size=256) on rows of 32 / 64
     floats with minibatches of whole 32-row tiles (csrc/ppo_wide_bf16.hip: 93 us per launch against 116 on the bench shape; hidden 64 /
-    512, 16-float rows and other minibatch sizes keep their fp32 kernel).  Results agree to the tests' 1e-5, not bit for bit.  Also settable with the
+    512, 16-float rows and other minibatch sizes keep their fp32 kernel), and the recurrent training kernels of LSTMWrapper(Default) at
+    128 / 128 (csrc/lstm_seq_bf16.hip: the K = 256 gate product of the forward over the bptt steps, 306 us per launch against 387 on the c3
+    bench shape; pfa_lstm_seq_path says which kernel takes the form — the BPTT kernel measured slower in it and stays fp32, as do the
+    encoder, the rollout and the weight-gradient contractions).  Results agree to the tests' 1e-5, not bit for bit.  Also settable with the
     environment variable PFA_MATRIX_PRODUCTS before the library is first used."""
     from . import _lib
     if form not in ('fp32', 'bf16x6'):

@@ -13,16 +13,14 @@
 // Roofline: fp32 MFMA, 2*256*512 flop per row and step in each direction (+ 2*64*128 for the encoder forward).
 #include "common.hpp"
 #include "lane_ops.hpp"
+#include "lstm_seq.hpp"
 #include "lstm_tile.hpp"
 #include "mlp_tile.hpp"
 
 namespace pfa {
 
-constexpr int kSeqRT = 2;                 // row tiles per workgroup
-constexpr int kSeqRows = 16 * kSeqRT;
 constexpr int kDGS = kLG + 4;             // LDS row stride of a dG tile (floats)
 constexpr int kDGTile = 16 * kDGS;
-constexpr int kBiasCols = kLG + kLH;      // per-workgroup partial column sums: dG (512) then dxe (128)
 
 template <int DP>
 struct SeqFwdLds {
@@ -353,26 +351,6 @@ __global__ void __launch_bounds__(256) lstm_bias_final_kernel(const float *__res
     }
 }
 
-static int check_seq_dims(const pfa_mlp_dims *d) {
-    PFA_REQUIRE(d != nullptr, "lstm_seq: null dims");
-    PFA_REQUIRE(d->hidden == kHidden, "lstm_seq: hidden must be %d (got %d)", kHidden, d->hidden);
-    PFA_REQUIRE(d->obs_stride == 16 || d->obs_stride == 32 || d->obs_stride == 64 || d->obs_stride == 96 || d->obs_stride == 128 ||
-                    d->obs_stride == 160,
-                "lstm_seq: obs_stride must be one of 16/32/64/96/128/160 (got %d)", d->obs_stride);
-    PFA_REQUIRE(d->num_actions >= 1 && d->num_actions <= 15, "lstm_seq: num_actions must be in 1..15 (got %d)", d->num_actions);
-    return 0;
-}
-
-#define PFA_SEQ_DISPATCH_DP(dp, CALL)             \
-    switch (dp) {                                 \
-        case 16: { constexpr int DP = 16; CALL; } break;   \
-        case 32: { constexpr int DP = 32; CALL; } break;   \
-        case 64: { constexpr int DP = 64; CALL; } break;   \
-        case 96: { constexpr int DP = 96; CALL; } break;   \
-        case 160: { constexpr int DP = 160; CALL; } break; \
-        default: { constexpr int DP = 128; CALL; } break;  \
-    }
-
 }  // namespace pfa
 
 using namespace pfa;
@@ -404,6 +382,9 @@ extern "C" int pfa_lstm_seq_forward(const float *obs_tm, int64_t rows, int32_t s
     PFA_REQUIRE(init_slot <= steps, "lstm_seq_forward: init_slot %d out of range (-1 = zero state, 0 .. steps)", init_slot);
     const unsigned grid = (unsigned)((rows + kSeqRows - 1) / kSeqRows);
     ScopedKernelTimer timer("lstm_seq_fwd", (hipStream_t)stream);
+    if (lstm_seq_bf16_bits() & 1)   // opt-in product form (pfa_igemm_set_products(1)): csrc/lstm_seq_bf16.hip; wpack is a pfa_lstm_pack_split pack
+        return lstm_seq_fwd_bf16_launch((hipStream_t)stream, obs_tm, (long long)rows, (int)steps, params, dims, wpack, xe, gates_act, hs, cs,
+                                        (int)(init_slot < 0 ? -1 : init_slot));
     PFA_SEQ_DISPATCH_DP(dims->obs_stride,
                         hipLaunchKernelGGL(lstm_seq_fwd_kernel<DP>, dim3(grid), dim3(kLstmThreads), 0, (hipStream_t)stream, obs_tm,
                                            (long long)rows, (int)steps, params, dims->num_actions, (const float4 *)wpack, xe,

@@ -249,7 +249,7 @@ __global__ void __launch_bounds__(kTapeThreads) squared_tape_kernel(SquaredView 
 // ---------------------------------------------------------------------------------------------
 constexpr int kMtStep = kMtN - kMtM;        // 227
 constexpr int kTapeLin = 12288;             // words of LDS the raw stream slides through (48 KB)
-constexpr int kSelWords = 16;               // consecutive words per thread in the parallel passes
+constexpr int kSelWords = 8;              // consecutive words per thread in the parallel passes
 constexpr int kSelThreads = 256;
 constexpr int kSelChunk = kSelWords * kSelThreads;
 
@@ -386,16 +386,22 @@ __global__ void __launch_bounds__(kSelThreads) squared_tape_select_kernel(Square
         total += s_wave[q];
     }
     long long pos = before + wave_base + incl - mine;
+    // draw `pos` goes to env pos % n of round first_round + pos / n: divided once per thread and stepped from there (two 64-bit
+    // divisions per accepted word made this pass twice as long as the count pass over the same words)
+    int env = (int)(pos % v.n);
+    int slot = (int)((job.first_round + pos / v.n) % v.tape_rounds);
 #pragma unroll
     for (int i = 0; i < kSelWords; ++i) {
         if ((mask >> i) & 1u) {
             if (pos < job.need) {
-                const long long round = job.first_round + pos / v.n;
-                const int env = (int)(pos % v.n);
-                v.tape[(size_t)(round % v.tape_rounds) * v.n + env] = (uint16_t)perimeter_cell((int)cand[i], v.g);
+                v.tape[(size_t)slot * v.n + env] = (uint16_t)perimeter_cell((int)cand[i], v.g);
                 if (pos == job.need - 1) s_last = p0 + i;
             }
             ++pos;
+            if (++env == v.n) {
+                env = 0;
+                if (++slot == v.tape_rounds) slot = 0;
+            }
         }
     }
     __syncthreads();

@@ -5,7 +5,7 @@ hand-written fp32 MFMA kernel behind the C ABI; this module only sequences them:
   policy_step      encode_observations -> one nn.LSTM step -> decode_actions + sample_logits, one kernel   (protocol path)
   Engine.rollout   clean_pufferl.evaluate for a Squared vecenv: ONE persistent kernel for all T steps (csrc/lstm_fused.hip)
   Engine.update    one minibatch of clean_pufferl.train: gather -> fused forward over the bptt_horizon steps with the carried,
-                   detached state (clean_pufferl.py:186-191; csrc/lstm_seq.hip) -> heads + PPO loss (csrc/lstm.hip) -> fused
+                   detached state (clean_pufferl.py:186-191; csrc/lstm_seq.hip, or csrc/lstm_seq_bf16.hip under the bf16x6 switch) -> heads + PPO loss (csrc/lstm.hip) -> fused
                    BPTT (csrc/lstm_seq.hip) -> weight-gradient contractions over the rows (csrc/gemm.hip) -> flat gradient
 
 Row order inside a minibatch is TIME-MAJOR (row t*R + k = segment mb + k*nmb at step t) so that every per-step slice is
@@ -57,6 +57,7 @@ class Engine:
         self.lstm_c = torch.zeros(1, N, H, device=dev)
         self.wpack = torch.empty(_lib.lib().pfa_lstm_pack_bytes() // 4, device=dev)
         self.wpack_bwd = torch.empty_like(self.wpack)
+        self.wsplit = None                                  # the bf16x6 form's forward pack (csrc/lstm_seq_bf16.hip), allocated on first use
         M, Th = experience.minibatch_size, experience.bptt_horizon
         self.M, self.Th, self.R = M, Th, M // Th
         R = self.R
@@ -157,7 +158,15 @@ class Engine:
         init_slot = -1 if (mb == 0 or self.state is None) else Th
         # both re-tilings of the gate matrix in one launch (the weights changed in the previous optimizer step)
         _lib.check(L.pfa_lstm_pack_both(_lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(self.wpack), _lib.ptr(self.wpack_bwd), stream), 'lstm_pack_both')
-        _lib.check(L.pfa_lstm_seq_forward(_lib.ptr(self.obs_tm), R, Th, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(self.wpack),
+        # under set_matrix_products('bf16x6') the library says per call which kernel reads a split pack instead (bit 0: the forward;
+        # bit 1, the backward, is never set today): the switch may change while the engine lives
+        wfwd = self.wpack
+        if L.pfa_lstm_seq_path(C.byref(fp.dims), R) & 1:
+            if self.wsplit is None:
+                self.wsplit = torch.empty(L.pfa_lstm_pack_split_bytes(), dtype=torch.uint8, device=fp.flat.device)
+            _lib.check(L.pfa_lstm_pack_split(_lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(self.wsplit), stream), 'lstm_pack_split')
+            wfwd = self.wsplit
+        _lib.check(L.pfa_lstm_seq_forward(_lib.ptr(self.obs_tm), R, Th, _lib.ptr(fp.flat), C.byref(fp.dims), _lib.ptr(wfwd),
                                           _lib.ptr(self.xe), _lib.ptr(self.gates), _lib.ptr(self.Hs), _lib.ptr(self.Cs), init_slot, stream),
                    'lstm_seq_forward')
         self.state = True

@@ -1,0 +1,119 @@
+"""The recurrent training kernels in the opt-in bf16x6 product form (csrc/lstm_seq_bf16.hip) under set_matrix_products('bf16x6'): which
+path a shape takes (host state), the whole recurrent gradient and the carried state against float64 with test_gpu_lstm_grad_f64's
+driver and bound, and two create -> evaluate -> train iterations against the oracle trainer."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import lstm_grad_reference as LR
+
+CASES = ('s64-small', 's16-md', 's64-3mb', 's64-bptt1', 's160', 's64-long')
+
+
+def test_lstm_seq_path_follows_the_switch_on_the_host():
+    """pfa_lstm_seq_path launches nothing: non-zero (bit 0 forward, bit 1 backward) for every row width and row count under the switch,
+    0 without it."""
+    import pufferlib_amd
+    from pufferlib_amd import _lib
+    L = _lib.lib()
+    shapes = [(_lib.MlpDims(s - 3, s, 128, 7, 0), rows) for s in (16, 64, 160) for rows in (7, 32, 40)]
+    try:
+        pufferlib_amd.set_matrix_products('bf16x6')
+        assert all(1 <= L.pfa_lstm_seq_path(C.byref(d), rows) <= 3 for d, rows in shapes)
+    finally:
+        pufferlib_amd.set_matrix_products('fp32')
+    assert all(L.pfa_lstm_seq_path(C.byref(d), rows) == 0 for d, rows in shapes)
+    assert L.pfa_lstm_pack_split_bytes() == 3 * L.pfa_lstm_pack_bytes() // 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('tag', CASES)
+def test_recurrent_gradient_matches_float64_in_the_bf16x6_form(tag):
+    """test_engine_update_matches_the_float64_gradient under the switch, on the smallest shapes at which the new kernels can go wrong: an
+    empty second row tile (7 rows), one row past a workgroup (33), state carried twice (40 rows), no recurrence inside the call
+    (bptt 1), full workgroups at the widest observation tile (160 floats), both buffer parities many times (96 rows x 16 steps).  The ten
+    gradient tensors and h / c left for the next minibatch — which hold the forward — within max(4 e32, 1e-5 max|f64|) of float64, e32
+    being what the restatement's own fp32 run loses: a bound from the reference.  It sees a lost 2^-8 term (hi.mid, mid.hi) by orders
+    of magnitude; at K = 256 / 512 it does not reliably see a lost 2^-16 term (docs/next-steps.md).  Every buffer, the split pack
+    included, holds NaN before each call; the sequence twice gives the same bits; against the switch-off run of the same engine xe is
+    bit-identical (the encoder is untouched) and dW_hh is not (the new kernels ran)."""
+    import pufferlib_amd
+    from pufferlib_amd import _lib
+    from test_gpu_lstm_grad_f64 import _Engine, _reference, _same_bits
+    case = next(c for c in LR.cases() if c.tag == 'lstm-' + tag)
+    ref = _reference(case)
+    dev = _Engine(case)
+    count = dev.fp.count
+    _, g_fp32, *_ = dev.sequence()
+    xe_fp32 = dev.eng.xe.clone()
+    poison = dev.poison
+
+    def poison_all():
+        poison()
+        if dev.eng.wsplit is not None:
+            dev.eng.wsplit.view(torch.float32).fill_(float('nan'))
+    dev.poison = poison_all
+    try:
+        pufferlib_amd.set_matrix_products('bf16x6')
+        assert _lib.lib().pfa_lstm_seq_path(C.byref(dev.fp.dims), case.R) != 0
+        g0, g, hT, cT, g0_next = first = dev.sequence()
+        assert dev.eng.wsplit is not None and _same_bits(dev.eng.xe, xe_fp32)
+        again = dev.sequence()
+    finally:
+        pufferlib_amd.set_matrix_products('fp32')
+    flat = g.cpu().numpy()
+    assert np.isfinite(flat).all() and torch.isfinite(hT).all() and torch.isfinite(cT).all() and torch.isfinite(g0_next).all()
+    got = case.split_flat(flat[:count])
+    got.update(h_final=hT.cpu().numpy(), c_final=cT.cpu().numpy())
+    bad = ref.failures(got, names=LR.NAMES + LR.STATE)
+    assert bad == [], f'{tag}: {bad} beyond max(4 e32, 1e-5 max|f64|) of the float64 reference (figures printed above)'
+    ref.check_sums(flat[count:], rows=case.rows)
+    assert (got['encoder.weight'][:, case.obs_dim:] == 0).all()
+    assert all(_same_bits(a, b) for a, b in zip(first, again))
+    whh = lambda v: case.split_flat(v.cpu().numpy()[:count])['recurrent.weight_hh_l0']      # noqa: E731
+    assert not np.array_equal(whh(g).view(np.int32), whh(g_fp32).view(np.int32))
+
+
+@pytest.mark.gpu
+def test_recurrent_policy_trains_against_the_oracle_in_the_bf16x6_form():
+    """test_update_branches_vs_oracle_trainer's recurrent leg with default flags under the switch (the combination that test skips): 128
+    envs x 32 steps, 2 minibatches, bptt 8, 3 epochs, two iterations, the contract tolerance.  The rollout is not part of the form: its
+    first actions are the fp32 run's."""
+    import pufferlib_amd
+    from pufferlib_amd import clean_pufferl
+    from test_gpu_parity_full import _build, _compare, _oracle_policy, _oracle_trainer
+    from test_gpu_ppo import _config
+    n, horizon, nmb, bptt, epochs = 128, 32, 2, 8, 3
+    hp = [1e-3, 0.97, 0.9, 0.2, 0.5, 0.2, 0.5, 0.02]
+    B = n * horizon
+
+    def first_rollout():
+        vec, pol = _build(n, True, seed_w=5)
+        data = clean_pufferl.create(_config(n, horizon, B // nmb, bptt, epochs, B * 6, hp), vec, pol)
+        clean_pufferl.evaluate(data)
+        return pol, data
+    _, data = first_rollout()
+    actions_fp32 = data.experience.actions.clone()
+    try:
+        pufferlib_amd.set_matrix_products('bf16x6')
+        pol, data = first_rollout()
+        assert torch.equal(data.experience.actions, actions_fp32)
+        opol = _oracle_policy(pol, True)
+        tr = None
+        for it in range(2):
+            if it:
+                clean_pufferl.evaluate(data)
+            tr_new = _oracle_trainer(opol, data, n, horizon, nmb, bptt, epochs, hp, B * 6)
+            if tr is not None:               # one optimizer / lr schedule across the two updates
+                tr_new.opt, tr_new.epoch = tr.opt, tr.epoch
+                for g in tr_new.opt.param_groups:
+                    g['params'] = opol.params
+            tr = tr_new
+            Lo = tr.train()
+            clean_pufferl.train(data)
+            _compare(pol, opol, data, Lo, True, tr, f'bf16x6 update {it}')
+        assert data.lstm_engine.wsplit is not None
+    finally:
+        pufferlib_amd.set_matrix_products('fp32')
