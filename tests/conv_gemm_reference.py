@@ -16,8 +16,8 @@ Weight-form results are compared in torch's parameter layout through `perm`; the
 and S.  The module imports neither the package under test nor the oracle."""
 import numpy as np
 
-from dense_gemm_reference import (BF16_128x32, BF16_128x64, F32, F64, FP32_128x32, FP32_128x64, FP32_256x16, Expected, _scales, bf16x6_rows,
-                                  chain_rows, chain_weights)
+from dense_gemm_reference import (BF16_128x32, BF16_128x64, F32, F64, FP32_128x32, FP32_128x64, FP32_256x16, PROBE_STEP, Expected, _scales,
+                                  bf16x6_rows, bf16x6_single, chain_rows, chain_weights)
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_MASK, EPI_BIAS_ADD, EPI_BIAS_ADD_RELU, EPI_MASK_ADD = range(7)
 DENSE, IM2COL_F32, IM2COL_U8, COL2IM, IM2COL_U8S, IM2COL_PAD, IM2COL_U8P = range(7)
@@ -230,15 +230,15 @@ class ConvRows(_Case):
         assert self.K % 16 == 0 and self.N % 16 == 0
         self.tiles = -(-self.M_plan // kernel[1])
 
-    def make_B(self, W):
-        """[P][N][K] from torch-layout weights, in W's precision."""
+    def make_B(self, W, div=True):
+        """[P][N][K] from torch-layout weights, in W's precision.  div=False: the layout alone, without the `/ 255` of the byte modes."""
         L = self.layer
         if self.mode == COL2IM:
             return dx_phase_layout(W, L.S)
         if self.kind == 'dx':
             return dx_flipped_layout(W)[None]
         order = 'ckk' if self.mode == IM2COL_U8 else 'kkc'
-        return fwd_layout(W, order, self.mode in BYTE_MODES, self.K)[None]
+        return fwd_layout(W, order, div and self.mode in BYTE_MODES, self.K)[None]
 
     def _materialise(self, rs):
         L, M, N = self.layer, self.M, self.N
@@ -280,6 +280,45 @@ class ConvRows(_Case):
         if self.epi in WITH_ADDEND:
             S = S + np.abs(self.addend.astype(F64))
         return S
+
+
+class ConvProbe(ConvRows):
+    """A ConvRows case under products = 1 whose WEIGHTS hold one non-zero tap per row of B (per output channel; col2im: per phase and
+    input channel), at k(p, n) = (5 n + shift + 7 p) mod K_true — the operand A is gathered from a dense image and cannot be made
+    one-hot.  Every output is then the single product A[m][k] B[n][k]: the dense probe of tests/dense_gemm_reference.py from the other
+    side.  The dense weights of ConvRows are masked in torch's layout, so B still comes out of `make_B`; biases are zero; the epilogue
+    (ReLU, the dX mask) is the case's own.  `sets` cases with shifts 5 N j cover the K_true taps between them."""
+    FIELDS = ConvRows.FIELDS + ('taps',)
+
+    def __init__(self, tag, mode, kernel, layer, frames, shift=0, **kw):
+        ConvRows.__init__(self, tag, mode, kernel, layer, frames, products=1, **kw)
+        self.shift, self.made_from = shift, (mode, kernel, layer, frames, shift, {k: v for k, v in kw.items() if k != 'seed'})
+        assert mode not in (IM2COL_PAD, IM2COL_U8P) and self.K == self.K_true and self.epi in (EPI_BIAS_RELU, EPI_MASK)
+
+    def _materialise(self, rs):
+        ConvRows._materialise(self, rs)
+        P, N, K = self.phases, self.N, self.K
+        self.taps = (PROBE_STEP * np.arange(N)[None, :] + self.shift + 7 * np.arange(P)[:, None]) % K             # [P][N]
+        pattern = np.zeros((P, N, K), bool)
+        pattern[np.arange(P)[:, None], np.arange(N)[None, :], self.taps] = True
+        # where each element of B sits in torch's layout: the layout of the positions themselves
+        position = self.make_B(np.arange(self.W.size).reshape(self.W.shape), div=False)
+        keep = np.zeros(self.W.size, bool)
+        keep[position[pattern]] = True
+        self.W = np.where(keep.reshape(self.W.shape), self.W, F32(0))
+        self.B = self.make_B(self.W)
+        assert np.array_equal(self.B != 0, pattern)
+        self.bias = np.zeros(N, F32)
+
+    def gathered(self):
+        """(A[m][k(phase(m), n)], B[phase(m)][n][k(phase(m), n)]), both [M][N]: the two factors of every output."""
+        taps = self.taps[self.phase]                                                                              # [M][N]
+        b = np.take_along_axis(self.B, self.taps[:, :, None], 2)[:, :, 0]                                         # [P][N]
+        return np.take_along_axis(self.A, taps, 1), b[self.phase]
+
+    def reseeded(self, seed):
+        mode, kernel, layer, frames, shift, kw = self.made_from
+        return ConvProbe(f'{self.tag}-seed{seed}', mode, kernel, layer, frames, shift=shift, seed=seed, **kw)
 
 
 class ConvWeights(_Case):
@@ -360,6 +399,17 @@ class RowsReference:
         self.out = Masked(c.epilogue(self.acc64), c.epilogue_S(self.S_product), c.epilogue(c.product(chain_rows, c.A, c.B, F32)))
 
 
+class ProbeReference:
+    """RowsReference read through the one tap of every output instead of summed over K: want = a b in float64 (then the epilogue), S =
+    |a b|, the fp32 chain the single rounded product.  Padding taps and zero bytes give S = 0: expected as exactly +0.0 (`Masked`)."""
+
+    def __init__(self, c):
+        a, b = c.gathered()
+        self.acc64 = a.astype(F64) * b.astype(F64)
+        self.S_product = np.abs(self.acc64)
+        self.out = Masked(c.epilogue(self.acc64), c.epilogue_S(self.S_product), c.epilogue(a * b))
+
+
 class WeightReference:
     def __init__(self, c):
         A64, D64 = c.A.astype(F64), c.D.astype(F64)
@@ -378,16 +428,21 @@ def reference(case):
     if case.tag not in _refs:
         while len(_refs) >= 4:
             _refs.pop(next(iter(_refs)))
-        _refs[case.tag] = (RowsReference if isinstance(case, ConvRows) else WeightReference)(case)
+        kind = ProbeReference if isinstance(case, ConvProbe) else RowsReference if isinstance(case, ConvRows) else WeightReference
+        _refs[case.tag] = kind(case)
     return _refs[case.tag]
-
-
 
 
 def six_term(case, drop=None):
     """The product as igemm_rows_split_kernel forms it (float operands: six terms per 32-deep slab; byte operands: three)."""
     a_int = case.mode in BYTE_MODES
     return case.product(lambda a, b: bf16x6_rows(a, b, drop=drop, a_int=a_int), case.A, case.B, F32)
+
+
+def six_term_single(case, drop=None):
+    """`six_term` of a probe case from its gathered factors."""
+    a, b = case.gathered()
+    return bf16x6_single(a, b, drop=drop, a_int=case.mode in BYTE_MODES)
 
 
 # --------------------------------------------------------------------------------------------------------------------- the tables
@@ -436,8 +491,8 @@ def rows_cases():
         add(f'm5-{name}', IM2COL_PAD, kernel, L, n, M=M, relu_in=relu)
         L, n, M, b = m6[tn]
         add(f'm6-{name}', IM2COL_U8P, kernel, L, n, M=M, bytes=b)
-    # the six-term kernels: per-phase contractions of 32 and 64 only (tests/test_conv_gemm_reference_cpu.py: beyond 64 the bound does
-    # not reliably see a lost term)
+    # the six-term kernels with dense weights: per-phase contractions of 32 and 64 only (tests/test_conv_gemm_reference_cpu.py: beyond 64
+    # the bound no longer sees a lost term behind the accumulation error; `probe_cases` carries the check to K = 256 .. 576)
     add('bf16x6-m1-128x64-K32', IM2COL_F32, BF16_128x64, Layer(8, 6, 5, 64, 2, 2), 11, products=1)
     add('bf16x6-m1-128x32-K64', IM2COL_F32, BF16_128x32, Layer(8, 9, 6, 32, 4, 2, S=2), 20, M=175, products=1)
     add('bf16x6-m2-128x64-K32', IM2COL_U8, BF16_128x64, Layer(2, 12, 16, 64, 4, 4, S=4), 15, products=1)
@@ -471,6 +526,33 @@ def rows_cases():
         bytes=Bytes('chw', 1, 3))
     assert len({x.tag for x in c}) == len(c)
     return c
+
+
+def probe_cases():
+    """The split kernels of modes 1 - 4 at the per-phase contractions the engines run them at: 256 (NatureCNN conv1 as bytes: 8 x 8 x 4;
+    conv2's dX: 2 x 2 taps x 64 per phase), 512 (conv2: 4 x 4 x 32), 576 (conv3 and its dX: 3 x 3 x 64), on a few small frames — ~180 rows, two
+    row tiles with a ragged last one.  N is as wide as K (a few column tiles) so that one weight set reaches every tap, except
+    `m1-128x64-K576`, whose 512 channels take two.  -> the cases, grouped: [[the sets of one probe], ...]."""
+    groups = []
+
+    def add(tag, mode, kernel, layer, frames, **kw):
+        K = (layer.KH // layer.S) * (layer.KW // layer.S) * layer.OC if mode == COL2IM else layer.KH * layer.KW * layer.IC
+        N = layer.IC if mode == COL2IM else layer.OC
+        sets = -(-K // N)
+        groups.append([ConvProbe(f'probe-{tag}' + (f'-set{j}' if sets > 1 else ''), mode, kernel, layer, frames, shift=PROBE_STEP * N * j,
+                                 seed=3000 + 10 * len(groups) + j, **kw) for j in range(sets)])
+
+    add('m1-128x64-K512', IM2COL_F32, BF16_128x64, Layer(32, 6, 8, 512, 4, 4, S=2), 30, M=175)
+    add('m1-128x64-K576', IM2COL_F32, BF16_128x64, Layer(64, 5, 4, 512, 3, 3), 30)
+    add('m1-128x32-K256', IM2COL_F32, BF16_128x32, Layer(16, 7, 6, 288, 4, 4), 15, M=175)
+    add('m2-128x32-K256', IM2COL_U8, BF16_128x32, Layer(4, 12, 16, 288, 8, 8, S=4), 30, M=177)
+    add('m2-128x64-K512', IM2COL_U8, BF16_128x64, Layer(8, 12, 16, 512, 8, 8, S=4), 30)
+    add('m3-128x32-K256', COL2IM, BF16_128x32, Layer(288, 9, 7, 64, 4, 4, S=2), 9, kind='dx')       # ragged phases, uncovered pixels
+    add('m3-128x64-K576', COL2IM, BF16_128x64, Layer(576, 5, 4, 64, 3, 3), 9, kind='dx')
+    add('m4-128x64-K256', IM2COL_U8S, BF16_128x64, Layer(4, 9, 10, 256, 8, 8), 30, bytes=HWC)
+    add('m4-128x32-K576', IM2COL_U8S, BF16_128x32, Layer(4, 13, 14, 608, 12, 12), 30, M=178, bytes=Bytes('chw', 2, 3))
+    assert len({c.tag for g in groups for c in g}) == sum(len(g) for g in groups)
+    return groups
 
 
 def weight_cases():

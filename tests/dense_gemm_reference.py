@@ -15,7 +15,15 @@ mask of epilogue 3 is an input: where mask <= 0 the expected output is exactly +
 
 `bf16x6_rows` emulates the opt-in six-term product form of the rows kernels (three bf16 pieces per fp32 operand, the six partial
 products above 2^-24 per 32-deep slab, fp32 accumulation), optionally with one term left out: tests/test_dense_gemm_reference_cpu.py
-uses it to show that the bound sees a lost term."""
+uses it to show that the bound sees a lost term.
+
+Probe cases (`probe_cases`) are a second kind, for the contraction lengths at which the dense cases can no longer see a lost term (with
+dense operands e32s grows with K faster than one 2^-16 term does).  A has ONE non-zero per row, at k(m) = (5 m + seed) mod K, so every
+output is a single product: e32s is one rounding whatever K is, a lost term stands out by the same factor at every K, and the result
+names the one k that was multiplied — a slab read from the wrong offset is wrong by orders of magnitude.  Their reference is a gather
+(`ProbeReference`), not a chain over K."""
+import math
+
 import numpy as np
 import torch
 
@@ -63,6 +71,42 @@ class RowsCase:
         if self.epi == EPI_MASK:
             acc = np.where(self.mask > 0, acc, 0).astype(acc.dtype)
         return acc
+
+
+PROBE_STEP = 5        # k(m) advances by this per row: coprime to every K of the table, so M >= K rows hit every k
+
+
+class ProbeCase(RowsCase):
+    """Mode 0 under products = 1, no epilogue: A [M][K] holds one non-zero per row, `a[m]` at column `k[m]` = (5 m + seed) mod K; B is
+    dense.  Values and 2^j row scales come from the generator of RowsCase, so all three bf16 pieces of both operands are populated.  `A`
+    (the materialised operand, what the device reads) is built when first read: 50 MB at K = 3136."""
+
+    def __init__(self, tag, kernel, M, K, N, seed=0):
+        RowsCase.__init__(self, tag, kernel, M, K, N, epi=EPI_NONE, products=1, seed=seed)
+        assert M >= K and math.gcd(PROBE_STEP, K) == 1
+
+    def __getattr__(self, name):
+        if name not in ('A', 'B', 'a', 'k', 'bias', 'mask'):
+            raise AttributeError(name)
+        M, K, N = self.M, self.K, self.N
+        if name == 'A':
+            self.A = np.zeros((M, K), F32)
+            self.A[np.arange(M), self.k] = self.a
+            return self.A
+        rs = np.random.RandomState(self.seed)
+        sb = _scales(rs, N)
+        self.a = (rs.standard_normal(M).astype(F32) * _scales(rs, M)).astype(F32)
+        self.B = (rs.standard_normal((N, K)).astype(F32) * sb[:, None]).astype(F32)
+        self.k = (PROBE_STEP * np.arange(M) + self.seed) % K
+        self.bias = self.mask = None
+        return self.__dict__[name]
+
+    def gathered(self):
+        """(a [M][1], B[n][k(m)] as [M][N]): the two factors of every output."""
+        return self.a[:, None], np.ascontiguousarray(self.B[:, self.k].T)
+
+    def reseeded(self, seed):
+        return ProbeCase(f'{self.tag}-seed{seed}', self.kernel, self.M, self.K, self.N, seed=seed)
 
 
 class WeightCase:
@@ -145,6 +189,18 @@ def bf16x6_rows(A, B, drop=None, a_int=False):
     return acc.numpy()
 
 
+def bf16x6_single(a, b, drop=None, a_int=False):
+    """bf16x6_rows for outputs that are ONE product a b (arrays that broadcast against each other): the other 31 products of the slab and
+    all other slabs contribute exact zeros, so the accumulator sees the six (three) exact partial products of this one, in order."""
+    pa, pb = _split3(torch.from_numpy(np.ascontiguousarray(a))), _split3(torch.from_numpy(np.ascontiguousarray(b)))
+    assert not a_int or bool((pa['hi'] == torch.from_numpy(np.ascontiguousarray(a))).all())
+    acc = torch.zeros(np.broadcast_shapes(a.shape, b.shape))
+    for ta, tb in (INT_TERMS if a_int else TERMS):
+        if (ta, tb) != drop:
+            acc = acc + pa[ta] * pb[tb]
+    return acc.numpy()
+
+
 class Expected:
     """want, S (float64) and the fp32 chain's own scaled error of one output tensor.  prefill (accumulating launches): what the output
     held before; it joins `want` after e32s is taken, and one ulp of it is allowed per element on top of the bound."""
@@ -177,6 +233,17 @@ class RowsReference:
         self.out = Expected(case.epilogue(A64 @ B64.T), S, case.epilogue(chain_rows(case.A, case.B)))
 
 
+class ProbeReference:
+    """want = a[m] B[n][k(m)] in float64, S = |want|, and the fp32 chain is the single rounded product (the chain's other terms are
+    zeros) — read through k(m), never summed over K."""
+
+    def __init__(self, case):
+        a, b = case.gathered()
+        want = a.astype(F64) * b.astype(F64)
+        self.case = case
+        self.out = Expected(want, np.abs(want), a * b)
+
+
 class WeightReference:
     def __init__(self, case):
         A64, D64 = case.A.astype(F64), case.D.astype(F64)
@@ -203,7 +270,8 @@ def reference(case):
     if case.tag not in _refs:
         while len(_refs) >= 4:
             _refs.pop(next(iter(_refs)))
-        _refs[case.tag] = (RowsReference if isinstance(case, RowsCase) else WeightReference)(case)
+        kind = ProbeReference if isinstance(case, ProbeCase) else RowsReference if isinstance(case, RowsCase) else WeightReference
+        _refs[case.tag] = kind(case)
     return _refs[case.tag]
 
 
@@ -238,6 +306,16 @@ def rows_cases():
     # products = 1 where the split kernels do not apply: a contraction that is no multiple of 32, 16-column tiles
     c.append(RowsCase('bf16x6-asks-128x64-K48', FP32_128x64, 3970, 48, 512, products=1, seed=len(c)))
     c.append(RowsCase('bf16x6-asks-256x16-K16', FP32_256x16, 3850, 16, 272, products=1, seed=len(c)))
+    assert len({x.tag for x in c}) == len(c)
+    return c
+
+
+def probe_cases():
+    """The contraction lengths the engines run in the six-term form — 256 (recurrent gates, wide heads), 512 and 576 (NatureCNN conv2,
+    conv3), 3136 (NatureCNN fc) — on the two split kernels, at the row counts of the bf16x6 rows of `rows_cases` (32 tiles of 128 with 2
+    rows in the last; 18 with 4).  M >= K: every k is multiplied by some row."""
+    c = [ProbeCase(f'probe-128x64-K{K}', BF16_128x64, 3970, K, 512, seed=300 + i) for i, K in enumerate((256, 576, 3136))]
+    c.append(ProbeCase('probe-128x32-K512', BF16_128x32, 2180, 512, 480, seed=300 + len(c)))
     assert len({x.tag for x in c}) == len(c)
     return c
 

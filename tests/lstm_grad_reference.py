@@ -101,6 +101,61 @@ class Case(R.Case):
         return out
 
 
+class GateProbe(Case):
+    """The `s64-bptt1` shape (3 rows, one step, the state carried from minibatch 0) with ONE non-zero in every gate row of [W_ih | W_hh],
+    at column (5 r + seed) mod 256: the 512 rows reach each of the 256 positions of [xe | h] twice, and every gate pre-activation is one
+    product plus its biases, whatever the contraction length of lstm_seq_fwd is.  The kept weights are drawn at standard deviation 1
+    (sqrt(H) times the dense cases'): a 2^-16 term of a product of that size still shows behind the gate non-linearities, which a
+    product of size 1 / sqrt(H) does not on every seed (docs/lab-notebook.md)."""
+
+    def __init__(self, seed):
+        super().__init__(f'lstm-gate-probe-seed{seed}', 49, 64, 8, 0, 3, 1, 2, 1, seed=seed)
+
+    def more_params(self, rs):
+        super().more_params(rs)
+        W = np.concatenate([self.params['recurrent.weight_ih_l0'], self.params['recurrent.weight_hh_l0']], 1) * np.float32(np.sqrt(H))
+        self.taps = (5 * np.arange(4 * H) + self.seed) % (2 * H)
+        keep = np.zeros(W.shape, bool)
+        keep[np.arange(4 * H), self.taps] = True
+        W = np.where(keep, W, np.float32(0))
+        self.params['recurrent.weight_ih_l0'] = np.ascontiguousarray(W[:, :H])
+        self.params['recurrent.weight_hh_l0'] = np.ascontiguousarray(W[:, H:])
+
+
+def state_six_term(case, product):
+    """(h_final, c_final) of minibatch case.mb in fp32 with the gate product [xe | h] [W_ih | W_hh]^T formed by `product(A, B)` (numpy
+    fp32 -> fp32: dense_gemm_reference.bf16x6_rows, complete or with one term left out); the encoder stays an fp32 Linear, as on the
+    device."""
+    p = {k: torch.as_tensor(v) for k, v in case.params.items()}
+    W = torch.cat([p['recurrent.weight_ih_l0'], p['recurrent.weight_hh_l0']], 1).numpy()
+    bias = p['recurrent.bias_ih_l0'] + p['recurrent.bias_hh_l0']
+    h, c = torch.zeros(case.R, H), torch.zeros(case.R, H)
+    for m in range(case.mb + 1):
+        obs = torch.as_tensor(case.obs)[torch.as_tensor(case.rows_index(m))]
+        x = torch.relu(F.linear(obs, p['encoder.weight'], p['encoder.bias']))
+        for t in range(case.horizon):
+            pre = torch.from_numpy(product(torch.cat([x[t * case.R:(t + 1) * case.R], h], 1).numpy(), W)) + bias
+            i, f, g, o = pre.chunk(4, dim=1)
+            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+            h = torch.sigmoid(o) * torch.tanh(c)
+    return {'h_final': h.double().numpy(), 'c_final': c.double().numpy()}
+
+
+class StateReference:
+    """The float64 final state of a case and what the restatement's own fp32 run loses on it (max norm per tensor); the bound is
+    4 e32 with NO floor — the 1e-5 max|f64| floor of `Reference.bound` is 2^-16.6, the very size of the term a probe is to see."""
+
+    def __init__(self, case):
+        r64, r32 = run(case, torch.float64), run(case, torch.float32)
+        self.want = {k: r64[k] for k in STATE}
+        self.e32 = {k: float(np.abs(r32[k] - r64[k]).max()) for k in STATE}
+        assert all(e > 0 for e in self.e32.values())
+
+    def of_bound(self, got):
+        """name -> max |got - f64| / (4 e32)."""
+        return {k: float(np.abs(np.asarray(got[k], np.float64) - self.want[k]).max()) / (4.0 * self.e32[k]) for k in STATE}
+
+
 def run(case, dtype, wrong=None):
     """The minibatch step of `case` at `dtype`: the ten gradients, the loss sums, the final state and what the kinks sit on."""
     assert wrong is None or wrong in WRONG

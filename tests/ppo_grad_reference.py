@@ -29,14 +29,49 @@ def head_sizes(actions, heads):
     return out
 
 
-def _policy_rows(p, obs, acts, sizes, hidden=None):
-    """(pre-activation, hidden, new log-probability, entropy, new value) per row; `hidden` given: the heads alone."""
+class _Product(torch.autograd.Function):
+    """x W^T whose three products — forward, d x = g W, d W = g^T x — are each formed by hook(site, A, B) = A B^T (sites `site`,
+    `site`.dx, `site`.dw)."""
+
+    @staticmethod
+    def forward(ctx, x, W, hook, site):
+        ctx.save_for_backward(x, W)
+        ctx.hook, ctx.site = hook, site
+        return hook(site, x, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W = ctx.saved_tensors
+        dx = ctx.hook(ctx.site + '.dx', g, W.t()) if ctx.needs_input_grad[0] else None
+        return dx, ctx.hook(ctx.site + '.dw', g.t(), x.t()), None, None
+
+
+# the product sites of a gradient step, as `run(product=...)` names them: X W1^T, dW1 = dpre^T X, hidden [W2; wv]^T, dh = dout [W2; wv],
+# d[W2; wv] = dout^T hidden
+SITES = ('encoder', 'encoder.dw', 'heads', 'heads.dx', 'heads.dw')
+
+
+def _policy_rows(p, obs, acts, sizes, hidden=None, product=None, keep=None):
+    """(pre-activation, hidden, new log-probability, entropy, new value) per row; `hidden` given: the heads alone.  product: None (the
+    plain F.linear) or hook(site, A, B) -> A B^T for every product of SITES; the two heads are then ONE product against [W2; wv], as
+    the fused kernels form them.  keep: a dict that receives `logits` and `value` (their gradients retained)."""
     pre = None
     if hidden is None:
-        pre = F.linear(obs, p['encoder.weight'], p['encoder.bias'])
+        if product is None:
+            pre = F.linear(obs, p['encoder.weight'], p['encoder.bias'])
+        else:
+            pre = _Product.apply(obs, p['encoder.weight'], product, 'encoder') + p['encoder.bias']
         hidden = torch.relu(pre)
-    logits = F.linear(hidden, p['decoder.weight'], p['decoder.bias'])
-    value = F.linear(hidden, p['value_head.weight'], p['value_head.bias']).view(-1)
+    if product is None:
+        logits = F.linear(hidden, p['decoder.weight'], p['decoder.bias'])
+        value = F.linear(hidden, p['value_head.weight'], p['value_head.bias']).view(-1)
+    else:
+        both = _Product.apply(hidden, torch.cat([p['decoder.weight'], p['value_head.weight']]), product, 'heads')
+        logits, value = both[:, :-1] + p['decoder.bias'], both[:, -1] + p['value_head.bias']
+    if keep is not None:
+        logits.retain_grad()
+        value.retain_grad()
+        keep.update(logits=logits, value=value)
     logprob, entropy, o = 0.0, 0.0, 0
     for h, n in enumerate(sizes):              # cleanrl.py:25-47 with the stored actions: per head, summed over heads
         nl = torch.log_softmax(logits[:, o:o + n], dim=-1)
@@ -144,14 +179,17 @@ class Case:
         return np.array([[a[self.rows_index(m)].sum(), (a[self.rows_index(m)] ** 2).sum()] for m in range(self.nmb)])
 
 
-def run(case, dtype):
-    """The minibatch step of `case` at `dtype`: gradients, loss sums, d loss / d hidden and the per-row quantities the kinks sit on."""
+def run(case, dtype, product=None):
+    """The minibatch step of `case` at `dtype`: gradients, loss sums, d loss / d hidden and the per-row quantities the kinks sit on.
+    product: see `_policy_rows` (default: the plain matmuls)."""
     idx = torch.as_tensor(case.rows_index())
     t = lambda x: torch.as_tensor(x)[idx].to(dtype)     # noqa: E731
     p = {k: torch.as_tensor(v).to(dtype).clone().requires_grad_(True) for k, v in case.params.items()}
     acts = torch.as_tensor(case.acts)[idx]
     hid_in = torch.as_tensor(case.h).to(dtype).clone().requires_grad_(True) if case.heads_only else None
-    pre, hidden, newlogprob, entropy, newvalue = _policy_rows(p, None if case.heads_only else t(case.obs), acts, case.sizes, hidden=hid_in)
+    keep = {}
+    pre, hidden, newlogprob, entropy, newvalue = _policy_rows(p, None if case.heads_only else t(case.obs), acts, case.sizes, hidden=hid_in,
+                                                              product=product, keep=keep)
     if not case.heads_only:
         hidden.retain_grad()
     old_lp, val, adv, ret = t(case.logprobs), t(case.values), t(case.advantages), t(case.returns)
@@ -174,7 +212,8 @@ def run(case, dtype):
     grads = {k: d(v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in p.items()}     # (heads_only: no encoder)
     return dict(grads=grads, dh=d((hid_in if case.heads_only else hidden).grad),
                 sums=np.array([d(x).sum() for x in (pg, v_rows, entropy, -logratio, (ratio - 1) - logratio, clipped)]),
-                pre=None if pre is None else d(pre), ratio=d(ratio), newvalue=d(newvalue), val=d(val), ret=d(ret))
+                pre=None if pre is None else d(pre), ratio=d(ratio), newvalue=d(newvalue), val=d(val), ret=d(ret),
+                hidden=d(hid_in if case.heads_only else hidden), dout=np.concatenate([d(keep['logits'].grad), d(keep['value'].grad)[:, None]], 1))
 
 
 def kink_margins(r64, r32, case):
@@ -330,3 +369,129 @@ def heads_cases():
 
 def all_cases():
     return mlp_cases() + bf16_cases() + wide_cases() + heads_cases()
+
+
+# ------------------------------------------------------------------------------------------------------- exact-product probe cases
+# The fused gradient kernels take experience and parameters, not operands; their products become single-term through the inputs.
+PROBE_KINDS = ('obs', 'heads')
+
+
+class ProbeCase(Case):
+    """One 32-row tile, obs_dim = stride (hidden 128: the 49 of 64 columns its bf16x6 form exists for), 8 actions.  kind 'obs': every observation row holds ONE non-zero (its own standard normal draw)
+    at column (5 r + shift) mod obs_dim, no two rows the same column: X W1^T and dW1 = dpre^T X are single products against a dense W1.
+    kind 'heads': every row of decoder.weight and value_head.weight holds one non-zero at unit (29 a + shift) mod hidden, no two rows
+    the same unit: the heads product (K = hidden) and dh = dout [W2; wv] are single products on the connected units.  The kept head
+    weights are scaled by sqrt(hidden) to standard deviation 1, the size a logit of the dense cases has."""
+
+    def __init__(self, hidden, stride, kind, shift, seed):
+        assert kind in PROBE_KINDS
+        self.kind, self.shift = kind, shift
+        dim = stride if hidden == 256 else 49
+        super().__init__(f'probe-h{hidden}-d{dim}of{stride}-{kind}-shift{shift}-seed{seed}', dim, stride, 8, 0, rows=32, seed=seed, hidden=hidden)
+
+    def more_params(self, rs):
+        if self.kind == 'obs':
+            self.cols = (5 * np.arange(self.B) + self.shift) % self.obs_dim
+            assert len(set(self.cols)) == self.B
+            keep = np.zeros(self.obs.shape, bool)
+            keep[np.arange(self.B), self.cols] = True
+            self.obs = np.where(keep, self.obs, np.float32(0))
+        else:
+            self.units = (29 * np.arange(self.actions + 1) + self.shift) % self.hidden
+            assert len(set(self.units)) == self.actions + 1
+            for name, units in (('decoder.weight', self.units[:-1]), ('value_head.weight', self.units[-1:])):
+                W = self.params[name] * np.float32(np.sqrt(self.hidden))
+                keep = np.zeros(W.shape, bool)
+                keep[np.arange(len(units)), units] = True
+                self.params[name] = np.where(keep, W, np.float32(0))
+
+    def reseeded(self, seed):
+        return ProbeCase(self.hidden, self.stride, self.kind, self.shift, seed)
+
+
+def six_term_product(site=None, drop=None):
+    """A `product` hook for `run`: every site in the six-term bf16 form (dense_gemm_reference.bf16x6_rows: 32-deep slabs, fp32
+    accumulation), the term `drop` left out at `site`."""
+    from dense_gemm_reference import bf16x6_rows
+
+    def product(at, A, B):
+        return torch.from_numpy(bf16x6_rows(A.detach().contiguous().numpy(), B.detach().contiguous().numpy(), drop=drop if at == site else None))
+    return product
+
+
+class ProbeReference:
+    """Element-wise measure of the six gradient tensors: |got - f64| / S, S the float64 backward pass on absolute values from d loss /
+    d (logits, value) on — S(dh) = |dout| |[W2; wv]|, S(dpre) = S(dh) [pre > 0], S(dW1) = S(dpre)^T |X|, S(db1) = its column sums,
+    S(dW2, dwv) = |dout|^T |hidden|, S(db2, dbv) = the column sums of |dout| — over the elements with S > 0.  The bound of a tensor is
+    4 x what the restatement's own fp32 run loses under the same measure; NO 1e-5 max floor (2^-16.6: the size of the term a probe is
+    to see).  clear: every row keeps the kink margins of `Reference`."""
+
+    def __init__(self, case):
+        self.case = case
+        r64, r32 = run(case, torch.float64), run(case, torch.float32)
+        self.clear = all(gap > MARGIN * err for gap, err in kink_margins(r64, r32, case).values())
+        A = case.actions
+        X = np.abs(case.obs[case.rows_index()].astype(np.float64))
+        W2v = np.abs(np.concatenate([case.params['decoder.weight'], case.params['value_head.weight']]).astype(np.float64))
+        dout, hid = np.abs(r64['dout']), np.abs(r64['hidden'])
+        s_dpre = (dout @ W2v) * (r64['pre'] > 0)
+        both = dout.T @ hid
+        self.S = {'encoder.weight': s_dpre.T @ X, 'encoder.bias': s_dpre.sum(0), 'decoder.weight': both[:A], 'decoder.bias': dout.sum(0)[:A],
+                  'value_head.weight': both[A:], 'value_head.bias': dout.sum(0)[A:]}
+        self.want = r64['grads']
+        self.e32s = self.scaled_err(r32['grads'])
+        assert all(e > 0 for e in self.e32s.values())
+
+    def scaled_err(self, got):
+        out = {}
+        for k in NAMES:
+            live = self.S[k] > 0
+            g = np.asarray(got[k], np.float64).reshape(self.want[k].shape)
+            assert live.any() and np.isfinite(g).all()
+            out[k] = float((np.abs(g - self.want[k])[live] / self.S[k][live]).max())
+        return out
+
+    def of_bound(self, got):
+        """name -> scaled error / (4 e32s)."""
+        return {k: v / (4.0 * self.e32s[k]) for k, v in self.scaled_err(got).items()}
+
+
+def probe_cases(hidden):
+    """hidden 256 (ppo_wide_grad_bf16_kernel): rows of 32 and 64 floats; hidden 128 (csrc/ppo_bf16.hpp): 64.  Two column shifts per
+    stride for the one-hot observations, four unit shifts for the one-tap heads."""
+    out = []
+    for stride in ((32, 64) if hidden == 256 else (64,)):
+        out += [ProbeCase(hidden, stride, 'obs', shift, 1) for shift in (0, 3)]
+        out += [ProbeCase(hidden, stride, 'heads', shift, 1) for shift in (0, 7, 70, 111)]
+    return out
+
+
+WITNESSES = tuple(k for k in NAMES if k != 'value_head.bias')     # value_head.bias: the complete six-term form itself is at 2.2 - 2.4 of
+# its bound on some seeds (a 32-term sum of d value with almost no fp32 error of its own), so it cannot witness a lost term
+
+
+def probe_seeds(base, count=12):
+    """The first `count` of seeds 1, 2, 3, ... at which the float64 reference of the probe is clear of every kink."""
+    out, seed = [], 0
+    while len(out) < count:
+        seed += 1
+        case = base.reseeded(seed)
+        ref = ProbeReference(case)
+        if ref.clear:
+            out.append((case, ref))
+    return out
+
+
+def probe_figures(base):
+    """From the reference and the emulator alone, over 12 seeds and the tensors of WITNESSES, in bounds: ('complete', worst) and, per
+    site, the smallest over seeds and droppable terms of the largest tensor figure with that term lost at that site."""
+    from dense_gemm_reference import DROPPABLE
+    worst, least = 0.0, {s: np.inf for s in SITES}
+    for case, ref in probe_seeds(base):
+        full = ref.of_bound(run(case, torch.float32, product=six_term_product())['grads'])
+        worst = max(worst, max(full[k] for k in WITNESSES))
+        for site in SITES:
+            for drop in DROPPABLE:
+                lost = ref.of_bound(run(case, torch.float32, product=six_term_product(site, drop))['grads'])
+                least[site] = min(least[site], max(lost[k] for k in WITNESSES))
+    return dict(complete=round(worst, 2), **{s: round(v, 2) for s, v in least.items()})

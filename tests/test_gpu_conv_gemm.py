@@ -3,7 +3,8 @@ and 8 six-term rows-form kernels, the weight form at every tile height a mode's 
 float64, one launch per case.  The operand of a case is materialised on the CPU by plain indexing (tests/conv_gemm_reference.py, which
 tests/test_conv_gemm_reference_cpu.py shows to be torch's convolution and its gradients) and compared under the row-scaled bound of
 tests/dense_gemm_reference.py: max |got - f64| / (|A| |B|^T) <= 4 e32s, no absolute floor.  Each case first asserts through the plan
-queries that it runs the kernel it is named for.
+queries that it runs the kernel it is named for.  The dense six-term cases stop at K = 64, where that bound still sees a lost term; the
+probe cases (single-product outputs) carry the same check to the split kernels' per-phase K = 256, 512 and 576.
 
 Buffers: float inputs sit between NaN guard frames and byte inputs between guard frames of 255, and every input element the case does
 not read (the rest of a frame M ends in, pixels no window reaches, stride gaps) is NaN / 255 as well; B, mask, addend and D have NaN
@@ -65,8 +66,8 @@ def _guarded_input(case):
     return dev, dev[g:]
 
 
-@pytest.mark.parametrize('case', _ids(R.rows_cases()))
-def test_rows_form_matches_float64(case):
+def _rows_form(case):
+    """One launch of pfa_igemm_rows / pfa_igemm_rows_add on `case` (a ConvRows or a ConvProbe), compared under the case's own bound."""
     from pufferlib_amd import _lib
     L = _lib.lib()
     ref = R.reference(case).out
@@ -106,6 +107,19 @@ def test_rows_form_matches_float64(case):
         off = case.mask <= 0
         assert np.array_equal(_bits(got[off]), _bits(case.addend[off])), 'mask <= 0: the addend bit for bit'
     assert err <= ref.bound, f'{case.tag}: {err:.3e} beyond 4 e32s = {ref.bound:.3e}'
+
+
+@pytest.mark.parametrize('case', _ids(R.rows_cases()))
+def test_rows_form_matches_float64(case):
+    _rows_form(case)
+
+
+@pytest.mark.parametrize('case', _ids([c for group in R.probe_cases() for c in group]))
+def test_split_kernels_keep_every_term_at_the_engines_contraction_lengths(case):
+    """The probe cases (weights with one non-zero tap per output channel, per-phase K = 256, 512, 576: NatureCNN's conv layers on a few
+    small frames): every output is one product, so a six-term kernel that loses a 2^-16 term in any k-slab, or gathers a slab from
+    the wrong tap, is 24 or more bounds away (tests/test_conv_gemm_reference_cpu.py).  Padding taps and zero bytes: +0.0 by bits."""
+    _rows_form(case)
 
 
 @pytest.mark.parametrize('case', _ids(R.weight_cases()))

@@ -2,7 +2,8 @@
 (tn, tile height) weight-form tiles) against float64, one launch per case.  Each case first asserts through pfa_igemm_rows_plan /
 pfa_igemm_weights_plan that it runs the kernel it is named for, then compares under the scaled bound of tests/dense_gemm_reference.py:
 max |got - f64| / (|A| |B|^T) <= 4 e32s, e32s the sequential fp32 chain's own figure, no absolute floor — a bound that
-tests/test_dense_gemm_reference_cpu.py shows to fail a six-term bf16 kernel that loses one term.
+tests/test_dense_gemm_reference_cpu.py shows to fail a six-term bf16 kernel that loses one term: with dense operands up to K = 96, and
+at K = 256, 512, 576 and 3136 through the probe cases, whose outputs are single products.
 
 Buffers: every leading dimension is wider than its matrix, the padding columns and two extra rows of A and D are NaN, and the outputs
 sit inside NaN-filled buffers whose guard elements must still be the same NaN bits afterwards.  pfa_rows_perm (csrc/general.hip), whose
@@ -44,8 +45,8 @@ def _report(tag, err, exp):
     print(f'[dense gemm f64] {tag:32s} err {err:.3e}  e32s {exp.e32s:.3e}  err/bound {err / exp.bound:.3f}')
 
 
-@pytest.mark.parametrize('case', _ids(R.rows_cases()))
-def test_rows_form_matches_float64(case):
+def _rows_form(case):
+    """One launch of pfa_igemm_rows on `case` (a RowsCase or a ProbeCase) into a guarded buffer, compared under the case's own bound."""
     from pufferlib_amd import _lib
     L = _lib.lib()
     ref = R.reference(case).out
@@ -75,6 +76,19 @@ def test_rows_form_matches_float64(case):
         off = case.mask <= 0
         assert not got[off].view(np.uint32).any(), 'mask <= 0 (0.0, -0.0, negative) must give exactly +0.0'
     assert err <= ref.bound, f'{case.tag}: {err:.3e} beyond 4 e32s = {ref.bound:.3e}'
+
+
+@pytest.mark.parametrize('case', _ids(R.rows_cases()))
+def test_rows_form_matches_float64(case):
+    _rows_form(case)
+
+
+@pytest.mark.parametrize('case', _ids(R.probe_cases()))
+def test_split_kernels_keep_every_term_at_the_engines_contraction_lengths(case):
+    """The probe cases (one non-zero per row of A at k(m) = (5 m + seed) mod K, K = 256 .. 3136): every output is one product, the bound
+    is four roundings of it, and a six-term kernel that loses a 2^-16 term in any k-slab, or reads a slab from the wrong offset, is 25
+    or more bounds away (tests/test_dense_gemm_reference_cpu.py)."""
+    _rows_form(case)
 
 
 @pytest.mark.parametrize('case', _ids(R.weight_cases()))

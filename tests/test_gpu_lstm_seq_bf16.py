@@ -36,7 +36,8 @@ def test_recurrent_gradient_matches_float64_in_the_bf16x6_form(tag):
     (bptt 1), full workgroups at the widest observation tile (160 floats), both buffer parities many times (96 rows x 16 steps).  The ten
     gradient tensors and h / c left for the next minibatch — which hold the forward — within max(4 e32, 1e-5 max|f64|) of float64, e32
     being what the restatement's own fp32 run loses: a bound from the reference.  It sees a lost 2^-8 term (hi.mid, mid.hi) by orders
-    of magnitude; at K = 256 / 512 it does not reliably see a lost 2^-16 term (docs/next-steps.md).  Every buffer, the split pack
+    of magnitude; a lost 2^-16 term it does not reliably see at K = 256 / 512 — the forward's gate product, the one product that runs in
+    the form, has the gate probe below for that.  Every buffer, the split pack
     included, holds NaN before each call; the sequence twice gives the same bits; against the switch-off run of the same engine xe is
     bit-identical (the encoder is untouched) and dW_hh is not (the new kernels ran)."""
     import pufferlib_amd
@@ -74,6 +75,34 @@ def test_recurrent_gradient_matches_float64_in_the_bf16x6_form(tag):
     assert all(_same_bits(a, b) for a, b in zip(first, again))
     whh = lambda v: case.split_flat(v.cpu().numpy()[:count])['recurrent.weight_hh_l0']      # noqa: E731
     assert not np.array_equal(whh(g).view(np.int32), whh(g_fp32).view(np.int32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('seed', [1, 2])
+def test_gate_product_keeps_every_term_in_the_bf16x6_form(seed):
+    """lstm_seq_fwd_bf16_kernel on LR.GateProbe: one non-zero in every gate row of [W_ih | W_hh] (K = 256), so each gate pre-activation
+    is one product and h / c after update(0), update(1) — the carried state went through the same product — must be within 4 e32 of the
+    float64 cell, e32 the restatement's own fp32 loss, with NO floor.  tests/test_lstm_grad_reference_cpu.py shows on 12 seeds that
+    the complete six-term form is at <= 0.32 of that bound and a lost lo.hi, hi.lo or mid.mid term at >= 1.6.
+    What this does NOT cover: the emulation drops the term in all eight k-slabs at once and the measure is a max norm per tensor, so a
+    term lost in ONE slab (about 64 of the 512 gate rows, half of whose xe taps are exact zeros after the ReLU) may pass; the kept
+    weights have standard deviation 1, sqrt(H) times what the engine runs (at that scale the emulation does not meet the condition);
+    the case has 3 rows, and only seeds 1 and 2 run here.  A probe on the gate pre-activations would close this (docs/next-steps.md)."""
+    import pufferlib_amd
+    from pufferlib_amd import _lib
+    from test_gpu_lstm_grad_f64 import _Engine
+    case = LR.GateProbe(seed)
+    ref = LR.StateReference(case)
+    dev = _Engine(case)
+    try:
+        pufferlib_amd.set_matrix_products('bf16x6')
+        assert _lib.lib().pfa_lstm_seq_path(C.byref(dev.fp.dims), case.R) & 1
+        _, _, hT, cT, _ = dev.sequence()
+    finally:
+        pufferlib_amd.set_matrix_products('fp32')
+    of_bound = ref.of_bound(dict(h_final=hT.cpu().numpy(), c_final=cT.cpu().numpy()))
+    print(f'[lstm gate probe] seed {seed}  e32 {ref.e32}  err / (4 e32) {of_bound}')
+    assert all(v <= 1.0 for v in of_bound.values()), of_bound
 
 
 @pytest.mark.gpu

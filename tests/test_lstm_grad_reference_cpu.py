@@ -88,3 +88,26 @@ def test_bound_accepts_the_fp32_run_and_rejects_four_wrong_restatements(referenc
                 assert missed == ['recurrent.weight_hh_l0']
             if wrong == 'dbhh_zero':
                 assert missed == ['recurrent.bias_hh_l0']
+
+
+def test_gate_probe_bound_passes_the_six_term_gate_product_and_fails_it_with_one_term_lost_on_twelve_seeds():
+    """What test_gpu_lstm_seq_bf16's gate probe stands on, from the reference and the emulator alone: with one non-zero per gate row
+    the final state of the emulated six-term form is inside 4 e32 (no floor) and every lost 2^-16 term of the gate product is outside it,
+    on both state tensors and on 12 seeds.  Measured: complete <= 0.32; smallest lost term 1.62 (mid.mid, c_final; lo.hi 1.87, hi.lo 1.92) — a small multiple,
+    the gate non-linearities attenuate it.  The taps of a case cover all 256 positions of [xe | h]."""
+    import dense_gemm_reference as D
+    worst, least = 0.0, {}
+    for seed in range(1, 13):
+        case = LR.GateProbe(seed)
+        W = np.concatenate([case.params['recurrent.weight_ih_l0'], case.params['recurrent.weight_hh_l0']], 1)
+        assert ((W != 0).sum(1) == 1).all() and sorted(set(case.taps)) == list(range(2 * LR.H)) and (case.R, case.horizon, case.mb) == (3, 1, 1)
+        ref = LR.StateReference(case)
+        full = ref.of_bound(LR.state_six_term(case, D.bf16x6_rows))
+        worst = max(worst, *full.values())
+        assert all(v <= 1.0 for v in full.values()), (seed, full)
+        for drop in D.DROPPABLE:
+            lost = ref.of_bound(LR.state_six_term(case, lambda a, b: D.bf16x6_rows(a, b, drop=drop)))
+            for k, v in lost.items():
+                least[drop, k] = min(least.get((drop, k), np.inf), v)
+            assert all(v > 1.0 for v in lost.values()), (seed, drop, lost)
+    print(f'[lstm gate probe cpu] six terms <= {worst:.2f}  ' + '  '.join(f'{d[0]}.{d[1]} {k} >= {v:.2f}' for (d, k), v in least.items()))
