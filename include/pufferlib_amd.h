@@ -822,6 +822,13 @@ int pfa_gemm_tn2_partial_f32(const float *a, int64_t lda, const float *b0, int64
 int pfa_reduce_multi(const pfa_reduce_job *jobs, int32_t njobs, pfa_stream_t stream);
 int pfa_gemm_tn2_f32(const float *a, int64_t lda, const float *b0, int64_t ldb0, const float *b1, int64_t ldb1, float *c0, int64_t ldc0,
                      float *c1, int64_t ldc1, int32_t mo, int64_t k, void *workspace, pfa_stream_t stream);
+/* The opt-in bf16x6 product form (pfa_igemm_set_products(1); csrc/gemm_bf16.hip) of these products: the four entry points above form
+ * the split partials of the two-operand 128 x 256 tile and of the single-operand 128 x 128, 128 x 64 and 128 x 160 tiles with every
+ * fp32 product as six bf16 partial products, fp32 accumulation; the 16 x 128, 128 x 32 and 128 x 16 tiles keep fp32.  Arguments,
+ * workspace size (the queries above do not depend on the switch) and the f64 reduction are unchanged; results agree with the fp32
+ * kernels to the tests' bound against float64, not bit for bit.  pfa_gemm_tn_path — host state only, nothing is launched — is 1 when
+ * a call of that shape (two_operand: pfa_gemm_tn2_*, no = 256) would run the bf16x6 kernel now, 0 otherwise. */
+int pfa_gemm_tn_path(int32_t mo, int32_t no, int64_t k, int32_t two_operand);
 /* Scatter into the flat gradient vector (MLP block + LSTM block layout): g16 [16][128] = dout^T h (rows < A ->
  * decoder.weight, row A -> value_head.weight), bsum16 = column sums of dout (-> decoder.bias, value_head.bias), and
  * d bias_hh_l0 = d bias_ih_l0 (already in place). */

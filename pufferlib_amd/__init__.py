@@ -54,7 +54,11 @@ def set_matrix_products(form):
     512, 16-float rows and other minibatch sizes keep their fp32 kernel), and the recurrent training kernels of LSTMWrapper(Default) at
     128 / 128 (csrc/lstm_seq_bf16.hip: the K = 256 gate product of the forward over the bptt steps, 306 us per launch against 387 on the c3
     bench shape; pfa_lstm_seq_path says which kernel takes the form — the BPTT kernel measured slower in it and stays fp32, as do the
-    encoder, the rollout and the weight-gradient contractions).  Results agree to the tests' 1e-5, not bit for bit.  Also settable with the
+    encoder and the rollout) and its weight-gradient contractions over the minibatch rows (csrc/gemm_bf16.hip; pfa_gemm_tn_path says
+    which tile takes the form: dW_ih | dW_hh in one pass, 198 us per launch against 305 at 131 072 rows, and the 128-row tiles of the
+    single products — dW_enc at 160-float rows 37 against 54, at 64-float rows 20 against 26, the 128 x 128 tile 101 against 165; the
+    16 x 128 head product and the 128 x 32 / 128 x 16 tiles are HBM- or latency-bound and keep fp32).  Results agree to the tests' 1e-5,
+    not bit for bit.  Also settable with the
     environment variable PFA_MATRIX_PRODUCTS before the library is first used."""
     from . import _lib
     if form not in ('fp32', 'bf16x6'):

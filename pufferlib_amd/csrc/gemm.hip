@@ -11,6 +11,7 @@
 // Roofline: fp32 MFMA (2*mo*no flop per k row) for the wide products, HBM (reading A and B once) for the
 // 16-row head product.
 #include "common.hpp"
+#include "gemm_bf16.hpp"
 #include "mlp_tile.hpp"
 
 namespace pfa {
@@ -254,6 +255,13 @@ static bool gemm_tn_plan(int mo, int no, long long K, GemmTnPlan &p) {
     return true;
 }
 
+// The same plan for the bf16x6 kernel (csrc/gemm_bf16.hip): its slab is 32 rows, so the split size is rounded up once more — never more
+// splits than the fp32 plan, which is what the workspace queries size for whatever the switch says.
+static int gemm_tn_bf16_splits(long long K, long long &per) {
+    per = (per + kGemmBfBK - 1) / kGemmBfBK * kGemmBfBK;
+    return (int)((K + per - 1) / per);
+}
+
 }  // namespace pfa
 
 using namespace pfa;
@@ -270,8 +278,13 @@ static int gemm_tn_launch_partial(const float *a, int64_t lda, const float *b, i
     PFA_REQUIRE(lda >= mo && ldb >= no && lda % 4 == 0 && ldb % 4 == 0, "gemm_tn: row strides must cover the tile and be 16-byte multiples");
     PFA_REQUIRE(((uintptr_t)a | (uintptr_t)b) % 16 == 0, "gemm_tn: operands must be 16-byte aligned");
     PFA_REQUIRE(gemm_tn_plan(mo, no, k, p), "gemm_tn: supported shapes are (128a x 16b) and (16a x 128b)");
-    const dim3 grid((unsigned)p.tiles, (unsigned)p.splits);
     float *partial = (float *)workspace;
+    if (gemm_tn_bf16_takes(p.cfg)) {
+        p.splits = gemm_tn_bf16_splits(k, p.k_per_split);
+        return gemm_tn_bf16_launch(p.cfg, st, (unsigned)p.tiles, (unsigned)p.splits, a, (long long)lda, b, (long long)ldb, mo, no, (long long)k,
+                                   p.k_per_split, partial, nullptr, 0, 0);
+    }
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.splits);
     if (p.cfg == 0)
         hipLaunchKernelGGL((gemm_tn_partial_kernel<2, 2, 4, 4>), grid, dim3(kGemmThreads), 0, st, a, (long long)lda, b, (long long)ldb,
                            mo, no, (long long)k, p.k_per_split, partial);
@@ -329,6 +342,14 @@ extern "C" size_t pfa_gemm_tn2_workspace_bytes(int32_t mo, int64_t k) {
     if (!gemm_tn_plan(mo, 128, k, p)) return 0;     // (the same split count as the 128 x 128 tiling: tiles = mo / 128)
     return (size_t)p.splits * mo * 256 * sizeof(float);
 }
+// Host only: 1 when the call would run the bf16x6 kernel under the products switch as it stands, 0 otherwise (switch off, a tile that
+// keeps fp32, an unsupported shape).  The launchers above and below take their choice from the same gemm_tn_bf16_takes.
+extern "C" int pfa_gemm_tn_path(int32_t mo, int32_t no, int64_t k, int32_t two_operand) {
+    if (mo <= 0 || no <= 0 || k <= 0) return 0;
+    if (two_operand) return mo % 128 == 0 && no == 256 && gemm_tn_bf16_takes(6);
+    GemmTnPlan p;
+    return gemm_tn_plan(mo, no, k, p) && gemm_tn_bf16_takes(p.cfg);
+}
 static int gemm_tn2_launch_partial(const float *a, int64_t lda, const float *b0, int64_t ldb0, const float *b1, int64_t ldb1, int32_t mo, int64_t k,
                                    void *workspace, int *splits_out, hipStream_t st) {
     PFA_REQUIRE(a && b0 && b1 && workspace && mo > 0 && mo % 128 == 0 && k > 0, "gemm_tn2: bad arguments (mo must be a multiple of 128)");
@@ -342,8 +363,13 @@ static int gemm_tn2_launch_partial(const float *a, int64_t lda, const float *b0,
     if (want < 1) want = 1;
     long long per = (k + want - 1) / want;
     per = (per + kGemmBK - 1) / kGemmBK * kGemmBK;
-    const int splits = (int)((k + per - 1) / per);
+    const bool bf16 = gemm_tn_bf16_takes(6);
+    const int splits = bf16 ? gemm_tn_bf16_splits(k, per) : (int)((k + per - 1) / per);
     PFA_REQUIRE((size_t)splits * mo * no * sizeof(float) <= pfa_gemm_tn2_workspace_bytes(mo, k), "gemm_tn2: split plan exceeds the workspace");
+    *splits_out = splits;
+    if (bf16)
+        return gemm_tn_bf16_launch(6, st, (unsigned)tiles, (unsigned)splits, a, (long long)lda, b0, (long long)ldb0, mo, no, (long long)k, per,
+                                   (float *)workspace, b1, (long long)ldb1, 128);
     hipLaunchKernelGGL((gemm_tn_partial_kernel<2, 2, 4, 8>), dim3((unsigned)tiles, (unsigned)splits), dim3(kGemmThreads), 0, st, a, (long long)lda, b0,
                        (long long)ldb0, mo, no, (long long)k, per, (float *)workspace, b1, (long long)ldb1, 128);
     PFA_LAUNCH_CHECK();

@@ -6,7 +6,8 @@ hand-written fp32 MFMA kernel behind the C ABI; this module only sequences them:
   Engine.rollout   clean_pufferl.evaluate for a Squared vecenv: ONE persistent kernel for all T steps (csrc/lstm_fused.hip)
   Engine.update    one minibatch of clean_pufferl.train: gather -> fused forward over the bptt_horizon steps with the carried,
                    detached state (clean_pufferl.py:186-191; csrc/lstm_seq.hip, or csrc/lstm_seq_bf16.hip under the bf16x6 switch) -> heads + PPO loss (csrc/lstm.hip) -> fused
-                   BPTT (csrc/lstm_seq.hip) -> weight-gradient contractions over the rows (csrc/gemm.hip) -> flat gradient
+                   BPTT (csrc/lstm_seq.hip) -> weight-gradient contractions over the rows (csrc/gemm.hip; under the switch the library
+                   routes dW_ih | dW_hh and dW_enc to csrc/gemm_bf16.hip per call) -> flat gradient
 
 Row order inside a minibatch is TIME-MAJOR (row t*R + k = segment mb + k*nmb at step t) so that every per-step slice is
 a contiguous [R][...] block.
