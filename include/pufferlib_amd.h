@@ -175,6 +175,40 @@ int pfa_pixel_squared_send(void *state, const pfa_squared_config *cfg, const pfa
                            float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PixelCatch vecenv — Catch (csrc/catch_env.hpp) as a time stack of uint8 frames (csrc/pixel_catch.hip).  A ball falls through a
+ * rows x cols grid, one row per send, moving vx columns sideways and bouncing off the side walls (where c + vx leaves the grid, vx
+ * flips first); the paddle on the bottom row moves by action - 1 (0 left, 1 stay, 2 right), clamped.  On the send that brings the
+ * ball to row rows - 1 the reward is +1 when ball and paddle share a column, else -1, terminal is set, infos' score is 1 / 0, and
+ * the next episode begins inside the same send (no auto-reset row); every other reward is 0.  Start state of (env, episode): ball
+ * column w0 % cols, vx = w1 % 3 - 1, paddle column w2 % cols, ball row 0, with (w0, w1, w2, _) = Philox4x32-10(counter =
+ * (env_offset + env, episode, 0, 0), key = (seed lo, 0x5043 ^ seed hi)).
+ * Frames: pixel (y, x) shows cell (y*rows / height, x*cols / width): 0 empty, 255 the ball, 128 the paddle.  Channel k shows the
+ * state framestack-1-k sends ago, never older than the episode's start state (after a reset all channels are equal).  obs is
+ * [N][framestack][height][width] u8, or [N][height][width][framestack] with channels_last.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t num_envs;
+    int32_t rows, cols;       /* >= 3, >= 2; rows * cols <= 65536 */
+    int32_t framestack;       /* 1..4 */
+    int32_t height, width;    /* rows <= height <= 1024, cols <= width <= 1024; framestack * height * width a multiple of 16 */
+    int32_t channels_last;
+    int32_t reserved;
+    uint64_t seed;
+    int64_t env_offset;       /* global index of local env 0 (sharding) */
+} pfa_pixel_catch_config;
+size_t pfa_pixel_catch_state_bytes(const pfa_pixel_catch_config *cfg);
+int pfa_pixel_catch_async_reset(void *state, const pfa_pixel_catch_config *cfg, uint8_t *obs, float *rewards, uint8_t *terminals,
+                                uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* one send of every env and a repaint of every channel of every frame, one launch */
+int pfa_pixel_catch_send(void *state, const pfa_pixel_catch_config *cfg, const int64_t *actions, uint8_t *obs, float *rewards,
+                         uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_pixel_catch_episode_stats(void *state, const pfa_pixel_catch_config *cfg, double *out4, int32_t reset, pfa_stream_t stream);
+int pfa_pixel_catch_last_infos(void *state, const pfa_pixel_catch_config *cfg, uint8_t *finished, double *episode_return,
+                               int32_t *episode_length, double *score, pfa_stream_t stream);
+/* test introspection: out16[e] = {(ball row, ball column, paddle column) now, 1, 2 and 3 sends ago, vx, episode, ep_length, 0} */
+int pfa_pixel_catch_debug_states(void *state, const pfa_pixel_catch_config *cfg, int32_t *out16, pfa_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MLP policy — pufferlib.models.Default (models.py:24-62) wrapped by frameworks.cleanrl.Policy
  * (cleanrl.py:50-66) with sample_logits (cleanrl.py:25-47): one Discrete head, or the MultiDiscrete branch (models.py:29-35,
  * 55-58: one decoder Linear per head; cleanrl.py:31-44: one multinomial per head, log-probabilities and entropies summed).

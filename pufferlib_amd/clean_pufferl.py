@@ -44,7 +44,7 @@ from . import dist as pdist
 from .cleanrl import Policy, RecurrentPolicy, _weights_changed, reads_frames, route
 from .models import FlatParams  # noqa: F401  (re-exported: callers of create() type-check the trainer's parameter buffer against it)
 from .namespace import namespace
-from .vector import Frames, PixelSquared, Spaces, Squared, Stochastic, _DeviceVecEnv
+from .vector import Frames, PixelCatch, PixelSquared, Spaces, Squared, Stochastic, _DeviceVecEnv
 
 
 def seed_everything(seed, torch_deterministic=True):
@@ -324,6 +324,8 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
         raise NotImplementedError('vector.Frames shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
     if isinstance(vecenv, PixelSquared) and not conv:
         raise NotImplementedError('vector.PixelSquared shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
+    if isinstance(vecenv, PixelCatch) and not conv:
+        raise NotImplementedError('vector.PixelCatch shows uint8 frame observations: use models.Convolutional or models.ProcgenResnet')
     if recurrent and isinstance(vecenv, Stochastic):
         raise NotImplementedError('the device-resident Stochastic vecenv has a fused rollout for the MLP policy only '
                                   '(ocean.Stochastic: "do not use a policy with memory", ocean.py:534)')

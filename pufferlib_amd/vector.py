@@ -75,8 +75,8 @@ def make_squared(distance_to_target=3, num_targets=1, **kwargs):
 def env_creator(name='squared'):
     """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only; plus pixel_squared, this package's frame
     rendering of it, tabular, the creator of a user-given TabularMDP (the reference has no such names), cartpole, the device
-    restatement of environments.classic_control's env (make_cartpole's max_steps=0 is that creator's env: no time limit), and
-    acrobot, gymnasium's Acrobot-v1 (the reference binds no such env)."""
+    restatement of environments.classic_control's env (make_cartpole's max_steps=0 is that creator's env: no time limit),
+    acrobot, gymnasium's Acrobot-v1 (the reference binds no such env), and pixel_catch, Catch as time-stacked frames."""
     if name == 'squared':
         return make_squared
     if name == 'pixel_squared':
@@ -87,6 +87,8 @@ def env_creator(name='squared'):
         return make_cartpole
     if name == 'acrobot':
         return make_acrobot
+    if name == 'pixel_catch':
+        return make_pixel_catch
     raise ValueError('Invalid environment name')
 
 
@@ -1397,6 +1399,79 @@ class Acrobot(_ControlVecEnv):
                                                        _lib.ptr(self.obs_buf), _lib.ptr(self.terminals_u8), _lib.stream_handle()),
                    'debug_set_states')
         torch.cuda.current_stream().synchronize()       # st and cn are freed on return
+
+
+def make_pixel_catch(rows=10, cols=8, framestack=4, height=84, width=84, channels_last=False, **kwargs):
+    """Env creator token of Catch as a time stack of frames: vector.make(make_pixel_catch, backend=PixelCatch, ...).  A ball falls
+    diagonally through a rows x cols grid, the paddle on the bottom row must be under it when it lands; the observation is the last
+    `framestack` states as the channels of a uint8 (framestack, height, width) frame — (height, width, framestack) with
+    channels_last —, oldest first."""
+    return PixelCatchSpec(rows, cols, framestack, height, width, channels_last)
+
+
+class PixelCatchSpec(_SimpleSpec):
+    """What ``driver_env`` exposes for PixelCatch: Box(0, 255, frame shape, uint8) and Discrete(3) (left, stay, right).  Pixel (y, x)
+    shows grid cell (y*rows // height, x*cols // width): 0 empty, 255 the ball, 128 the paddle.  Channel k shows the state
+    framestack-1-k sends ago within the episode: the ball's horizontal velocity is invisible in one channel and visible in the stack."""
+    MAX_FRAMESTACK = 4
+
+    def __init__(self, rows=10, cols=8, framestack=4, height=84, width=84, channels_last=False):
+        super().__init__(0, 255, 3)
+        self.rows, self.cols, self.framestack = int(rows), int(cols), int(framestack)
+        self.height, self.width, self.channels_last = int(height), int(width), bool(channels_last)
+        if self.rows < 3 or self.cols < 2:
+            raise APIUsageError(f'a {self.rows} x {self.cols} grid: Catch needs at least 3 rows and 2 columns')
+        if self.height < self.rows or self.width < self.cols:
+            raise APIUsageError(f'frames of {self.height} x {self.width} pixels cannot show a {self.rows} x {self.cols} grid: height must be at '
+                                f'least {self.rows} and width at least {self.cols}')
+        if not 1 <= self.framestack <= self.MAX_FRAMESTACK:
+            raise APIUsageError(f'framestack {self.framestack}: the env keeps the last 1..{self.MAX_FRAMESTACK} states')
+        self.shape = (self.height, self.width, self.framestack) if self.channels_last else (self.framestack, self.height, self.width)
+        if (self.height * self.width * self.framestack) % 16 != 0:
+            raise APIUsageError(f'frames of shape {self.shape}: the device env writes rows of a multiple of 16 bytes')
+        self.single_observation_space = spaces.Box(low=0, high=255, shape=self.shape, dtype=np.uint8)
+        self.observation_space = self.single_observation_space
+        self.emulated = namespace(observation_dtype=np.dtype(np.uint8),
+                                  emulated_observation_dtype=np.dtype((np.uint8, self.shape)))
+
+
+class PixelCatch(_CounterSeededVecEnv):
+    """Device-resident vecenv of N Catch envs shown as time-stacked uint8 frames (csrc/catch_env.hpp, csrc/pixel_catch.hip): the one
+    device task whose channel axis carries time.  The start states are counter-based — Philox keyed by (seed, global env, episode) —
+    so there is no tape and envs `env_offset ..` of a larger vecenv are reproduced exactly.  The send that lands the ball reports
+    the reward and the terminal and already shows the next episode's start frames: there is no auto-reset row, every episode is
+    rows - 1 sends.  It has no fused rollout: a conv policy's step is many launches, so the trainer steps it (policy step + store +
+    send)."""
+    FAMILY = 'pixel_catch'
+    ABI = 'pfa_pixel_catch'
+    NAMES = ('rows', 'cols', 'framestack', 'height', 'width', 'channels_last')
+    DEFAULTS = (10, 8, 4, 84, 84, False)
+    CONFIG_NAME = 'PixelCatch '
+    OBS_U8 = True
+    ROLLOUT_LSTM = None
+    fused_rollout_mlp = None
+
+    def _spec(self, rows, cols, framestack, height, width, channels_last):
+        spec = PixelCatchSpec(rows, cols, framestack, height, width, channels_last)
+        self.obs_stride = spec.height * spec.width * spec.framestack            # bytes per row
+        return spec
+
+    def _config(self):
+        sp = self.driver_env
+        self.obs_dim = self.obs_stride
+        self.observations = self.obs_buf.view(self.num_agents, *sp.shape)
+        self.episode_len = sp.rows - 1
+        return _lib.PixelCatchConfig(self.num_agents, sp.rows, sp.cols, sp.framestack, sp.height, sp.width, 1 if sp.channels_last else 0, 0, 0,
+                                     self.env_offset)
+
+    def debug_states(self):
+        """([N][framestack][3] int32: (ball row, ball column, paddle column) now, 1, ... sends ago — what the channels show, newest
+        first; [N][3] int32: vx, episode, ep_length) — test introspection."""
+        import torch
+        out = torch.zeros(self.num_agents, 16, dtype=torch.int32, device=self.device)
+        _lib.check(self._entry('_debug_states')(*self._state_args(), _lib.ptr(out), _lib.stream_handle()), 'debug_states')
+        out = out.cpu().numpy()
+        return out[:, :3 * self.driver_env.framestack].reshape(self.num_agents, -1, 3), out[:, 12:15]
 
 
 def make_bandit(num_actions=10, reward_scale=1, reward_noise=1, **kwargs):
