@@ -209,6 +209,37 @@ int pfa_pixel_catch_last_infos(void *state, const pfa_pixel_catch_config *cfg, u
 int pfa_pixel_catch_debug_states(void *state, const pfa_pixel_catch_config *cfg, int32_t *out16, pfa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Catch vecenv — the same task as flat float32 rows (csrc/catch_row_env.hpp, csrc/catch.hip): dynamics, rewards, terminals, episode
+ * statistics and start draws exactly as PixelCatch above (same counter, same key), so equal (rows, cols, seed, env_offset) and equal
+ * actions walk the same episodes.  Observation rows of obs_stride floats, zero behind the real values:
+ *   PFA_CATCH_OBS_GRID    rows * cols values: 1 at cell (ball row) * cols + ball column and at cell (rows - 1) * cols + paddle column,
+ *                         0 elsewhere; the ball's horizontal velocity shows only in two consecutive rows
+ *   PFA_CATCH_OBS_COORDS  (ball row / (rows - 1), ball column / (cols - 1), paddle column / (cols - 1)), each one IEEE f32 division of
+ *                         the two integers, and — velocities != 0 — vx in {-1, 0, 1}
+ * Protocol and live buffers as the other device envs.
+ * ------------------------------------------------------------------------------------------ */
+enum { PFA_CATCH_OBS_GRID = 0, PFA_CATCH_OBS_COORDS = 1 };
+typedef struct {
+    int32_t num_envs;
+    int32_t rows, cols;       /* >= 3, >= 2; rows * cols <= 160 */
+    int32_t obs_form;         /* PFA_CATCH_OBS_* */
+    int32_t velocities;       /* coords only: 0 hides vx (the observation then has three values) */
+    int32_t obs_stride;       /* floats per row: 16 / 32 / 64 / 96 / 128 / 160, >= rows * cols for the grid form */
+    uint64_t seed;
+    int64_t env_offset;       /* global index of local env 0 (sharding) */
+} pfa_catch_config;
+size_t pfa_catch_state_bytes(const pfa_catch_config *cfg);
+int pfa_catch_async_reset(void *state, const pfa_catch_config *cfg, float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations,
+                          uint8_t *masks, pfa_stream_t stream);
+int pfa_catch_send(void *state, const pfa_catch_config *cfg, const int64_t *actions, float *obs, float *rewards, uint8_t *terminals,
+                   uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+int pfa_catch_episode_stats(void *state, const pfa_catch_config *cfg, double *out4, int32_t reset, pfa_stream_t stream);
+int pfa_catch_last_infos(void *state, const pfa_catch_config *cfg, uint8_t *finished, double *episode_return, int32_t *episode_length,
+                         double *score, pfa_stream_t stream);
+/* test introspection: out6[e] = {ball row, ball column, paddle column, vx, episode, ep_length} of env e */
+int pfa_catch_debug_states(void *state, const pfa_catch_config *cfg, int32_t *out6, pfa_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MLP policy — pufferlib.models.Default (models.py:24-62) wrapped by frameworks.cleanrl.Policy
  * (cleanrl.py:50-66) with sample_logits (cleanrl.py:25-47): one Discrete head, or the MultiDiscrete branch (models.py:29-35,
  * 55-58: one decoder Linear per head; cleanrl.py:31-44: one multinomial per head, log-probabilities and entropies summed).
@@ -575,6 +606,17 @@ int pfa_rollout_mlp_view_acrobot(void *state, const pfa_acrobot_config *cfg, con
                                  const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
                                  uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 
+/* clean_pufferl.evaluate's loop for a Catch vecenv (pfa_catch_*, above) and the MLP policy, one persistent kernel: the flat 128-wide
+ * buffer (dims->obs_stride == cfg->obs_stride in 16 / 32 / 64 / 96 / 128, dims->obs_dim == the form's value count,
+ * dims->num_actions == 3) ... */
+int pfa_rollout_mlp_catch(void *state, const pfa_catch_config *cfg, const float *params, const pfa_mlp_dims *dims, const pfa_experience *exp,
+                          const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
+                          uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* ... or a pfa_mlp_view of hidden 64 / 128 / 256 / 512 on rows of up to 64 floats (same row and head). */
+int pfa_rollout_mlp_view_catch(void *state, const pfa_catch_config *cfg, const pfa_mlp_view *view, const pfa_experience *exp,
+                               const float *noise, const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards,
+                               uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Structured-observation unpack — replaces pufferlib.pytorch.nativize_tensor
  * (pufferlib/pytorch.py:96-145): flat emulated rows [num_rows][row_bytes] (device, 16-byte aligned) -> one dense tensor
@@ -760,6 +802,10 @@ int pfa_rollout_lstm_acrobot(void *state, const pfa_acrobot_config *cfg, const f
                              const void *wpack, float *h, float *c, const pfa_experience *exp, const float *noise,
                              const pfa_noise_key *key, int64_t env_offset, float *obs, float *rewards, uint8_t *terminals,
                              uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
+/* ... and over the Catch vecenv (pfa_catch_*): observation rows of 16 .. 160 floats, one Discrete(3) head. */
+int pfa_rollout_lstm_catch(void *state, const pfa_catch_config *cfg, const float *params, const pfa_mlp_dims *dims, const void *wpack,
+                           float *h, float *c, const pfa_experience *exp, const float *noise, const pfa_noise_key *key, int64_t env_offset,
+                           float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations, uint8_t *masks, pfa_stream_t stream);
 /* --- the recurrent policy in training mode (csrc/lstm_seq.hip): forward over the `steps` (= bptt_horizon) time steps
  * of a minibatch of `rows` independent segments and back-propagation through time (clean_pufferl.py:186-193, :244).
  * Time-major buffers: obs_tm [steps][rows][obs_stride], xe / dh_heads / dxe [steps][rows][128], gates_act / dgates

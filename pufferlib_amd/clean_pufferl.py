@@ -44,7 +44,7 @@ from . import dist as pdist
 from .cleanrl import Policy, RecurrentPolicy, _weights_changed, reads_frames, route
 from .models import FlatParams  # noqa: F401  (re-exported: callers of create() type-check the trainer's parameter buffer against it)
 from .namespace import namespace
-from .vector import Frames, PixelCatch, PixelSquared, Spaces, Squared, Stochastic, _DeviceVecEnv
+from .vector import Catch, Frames, PixelCatch, PixelSquared, Spaces, Squared, Stochastic, _DeviceVecEnv
 
 
 def seed_everything(seed, torch_deterministic=True):
@@ -306,6 +306,9 @@ def create(config, vecenv, policy, optimizer=None, wandb=None):
     from .models import conv_geometry_of, set_conv_obs_shape, set_resnet_obs_shape
     kind = route(policy.policy, recurrent)              # (refuses LSTMWrapper over models.ProcgenResnet and its action sets beyond 15)
     conv = reads_frames(policy.policy, recurrent)       # a conv encoder on any route: experience rows are uint8 frames
+    if isinstance(vecenv, Catch):
+        from .models import decoder_heads, find_mlp
+        vecenv.check_policy(conv=conv, multidiscrete=not conv and len(decoder_heads(find_mlp(policy.policy))) > 1)
     if conv:
         space = vecenv.single_observation_space
         name, layout = ('models.ProcgenResnet', ' (H, W, C)') if kind == 'resnet' else ('models.Convolutional', '')

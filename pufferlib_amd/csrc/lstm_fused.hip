@@ -20,6 +20,7 @@
 #include "tabular_env.hpp"
 #include "cartpole_env.hpp"
 #include "acrobot_env.hpp"
+#include "catch_row_env.hpp"
 
 namespace pfa {
 
@@ -369,4 +370,18 @@ extern "C" int pfa_rollout_lstm_acrobot(void *state, const pfa_acrobot_config *c
                                         uint8_t *truncations, uint8_t *masks, pfa_stream_t stream) {
     return rollout_lstm_control<AcrobotRollEnv>("rollout_lstm_acrobot", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset,
                                                 obs, rewards, terminals, truncations, masks, stream);
+}
+
+extern "C" int pfa_rollout_lstm_catch(void *state, const pfa_catch_config *cfg, const float *params, const pfa_mlp_dims *dims, const void *wpack,
+                                      float *h, float *c, const pfa_experience *exp, const float *noise, const pfa_noise_key *key,
+                                      int64_t env_offset, float *obs, float *rewards, uint8_t *terminals, uint8_t *truncations,
+                                      uint8_t *masks, pfa_stream_t stream) {
+    if (int rc = check_lstm_dims(dims)) return rc;
+    if (int rc = check_catch_config(cfg)) return rc;
+    PFA_REQUIRE(dims->num_actions == 3 && dims->heads == 0, "rollout_lstm_catch: the policy must have one Discrete(3) head (got %d actions)",
+                dims->num_actions);
+    PFA_REQUIRE(dims->obs_stride == cfg->obs_stride, "rollout_lstm_catch: env obs_stride %d != policy obs_stride %d", cfg->obs_stride,
+                dims->obs_stride);
+    return launch_rollout_lstm<CatchRowEnv>("rollout_lstm_catch", state, cfg, params, dims, wpack, h, c, exp, noise, key, env_offset, obs,
+                                            rewards, terminals, truncations, masks, stream);
 }

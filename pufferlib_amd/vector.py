@@ -76,7 +76,8 @@ def env_creator(name='squared'):
     """pufferlib.environments.ocean.env_creator (ocean/environment.py:6-26), squared only; plus pixel_squared, this package's frame
     rendering of it, tabular, the creator of a user-given TabularMDP (the reference has no such names), cartpole, the device
     restatement of environments.classic_control's env (make_cartpole's max_steps=0 is that creator's env: no time limit),
-    acrobot, gymnasium's Acrobot-v1 (the reference binds no such env), and pixel_catch, Catch as time-stacked frames."""
+    acrobot, gymnasium's Acrobot-v1 (the reference binds no such env), pixel_catch, Catch as time-stacked frames, and catch, the same
+    task as flat rows."""
     if name == 'squared':
         return make_squared
     if name == 'pixel_squared':
@@ -89,6 +90,8 @@ def env_creator(name='squared'):
         return make_acrobot
     if name == 'pixel_catch':
         return make_pixel_catch
+    if name == 'catch':
+        return make_catch
     raise ValueError('Invalid environment name')
 
 
@@ -1472,6 +1475,99 @@ class PixelCatch(_CounterSeededVecEnv):
         _lib.check(self._entry('_debug_states')(*self._state_args(), _lib.ptr(out), _lib.stream_handle()), 'debug_states')
         out = out.cpu().numpy()
         return out[:, :3 * self.driver_env.framestack].reshape(self.num_agents, -1, 3), out[:, 12:15]
+
+
+def make_catch(rows=10, cols=8, obs='grid', velocities=True, **kwargs):
+    """Env creator token of Catch as flat float32 rows: vector.make(make_catch, backend=Catch, ...).  The task and its episodes are
+    PixelCatch's (a ball falls diagonally through a rows x cols grid, the paddle on the bottom row must be under it when it lands).
+    obs='grid': rows * cols values, 1 at the ball's and at the paddle's cell — the ball's horizontal velocity shows only in two
+    consecutive rows, so the task needs one step of memory.  obs='coords': (ball row / (rows - 1), ball column / (cols - 1), paddle
+    column / (cols - 1)) and, with velocities, the velocity itself in {-1, 0, 1}: solvable without memory."""
+    return CatchSpec(rows, cols, obs, velocities)
+
+
+class CatchSpec(_SimpleSpec):
+    """What ``driver_env`` exposes for Catch: Box(0, 1, (rows * cols,), float32) for the grid form, Box(-1, 1, (4,) — (3,) without
+    velocities —, float32) for the coords form, and Discrete(3) (left, stay, right)."""
+    MAX_CELLS = 160      # the widest row of the recurrent tier
+    MAX_SIDE = 256       # coords form: a row and two columns travel in a byte each
+
+    def __init__(self, rows=10, cols=8, obs='grid', velocities=True):
+        super().__init__(0, 1, 3)
+        self.rows, self.cols, self.obs, self.velocities = int(rows), int(cols), obs, bool(velocities)
+        if self.rows < 3 or self.cols < 2:
+            raise APIUsageError(f'vector.Catch: a {self.rows} x {self.cols} grid: Catch needs at least 3 rows and 2 columns')
+        if obs not in _lib.CATCH_OBS_FORMS:
+            raise APIUsageError(f'vector.Catch: obs={obs!r} is not one of {_lib.CATCH_OBS_FORMS}')
+        if obs == 'grid' and self.rows * self.cols > self.MAX_CELLS:
+            raise APIUsageError(f'vector.Catch: a {self.rows} x {self.cols} grid is a row of {self.rows * self.cols} values; the widest row '
+                                f'(the recurrent policy\'s) holds {self.MAX_CELLS}, the feed-forward kernels\' 128: use obs=\'coords\'')
+        if max(self.rows, self.cols) > self.MAX_SIDE:
+            raise APIUsageError(f'vector.Catch: a {self.rows} x {self.cols} grid: the sides may be at most {self.MAX_SIDE}')
+        values = self.rows * self.cols if obs == 'grid' else (4 if self.velocities else 3)
+        self.single_observation_space = spaces.Box(low=0.0 if obs == 'grid' else -1.0, high=1.0, shape=(values,), dtype=np.float32)
+        self.observation_space = self.single_observation_space
+        self.emulated = namespace(observation_dtype=np.dtype(np.float32), emulated_observation_dtype=np.dtype((np.float32, (values,))))
+
+    def text(self, r, c, p):
+        """The grid as text: 'o' the ball, '=' the paddle, '.' an empty cell."""
+        lines = [['.'] * self.cols for _ in range(self.rows)]
+        lines[self.rows - 1][int(p)] = '='
+        lines[int(r)][int(c)] = 'o'
+        return '\n'.join(''.join(line) for line in lines)
+
+
+class Catch(_CounterSeededVecEnv):
+    """Device-resident vecenv of N Catch envs shown as flat float32 rows (csrc/catch_row_env.hpp, csrc/catch.hip): PixelCatch's flat
+    twin — equal (rows, cols, seed, env_offset) and equal actions give equal rewards, terminals and episode statistics — with integer
+    dynamics and a row that the kernels compute from three small integers (no table).  The start states are counter-based — Philox
+    keyed by (seed, global env, episode) — so there is no tape and envs `env_offset ..` of a larger vecenv are reproduced exactly.  The
+    send that lands the ball reports the reward and the terminal and already shows the next episode's start row: there is no
+    auto-reset row, every episode is rows - 1 sends.  It has a fused rollout kernel for the recurrent policy (rows of up to 160
+    floats), for Default(128) (up to 128) and for Default at the other tile widths (64 / 256 / 512: up to 64)."""
+    FAMILY = 'catch'
+    ABI = 'pfa_catch'
+    NAMES = ('rows', 'cols', 'obs', 'velocities')
+    DEFAULTS = (10, 8, 'grid', True)
+    CONFIG_NAME = 'Catch '
+    ROLLOUT_LSTM = 'pfa_rollout_lstm_catch'
+    ROLLOUT_MLP_VIEW = True
+
+    @staticmethod
+    def check_policy(conv=False, multidiscrete=False):
+        """What clean_pufferl.create refuses of a policy for this family (no GPU needed to ask)."""
+        if conv:
+            raise NotImplementedError('vector.Catch shows flat float32 rows: use models.Default, alone or under LSTMWrapper (vector.PixelCatch '
+                                      'shows the same task as frames for models.Convolutional and models.ProcgenResnet)')
+        if multidiscrete:
+            raise NotImplementedError('vector.Catch takes one Discrete(3) action: a MultiDiscrete policy does not fit it')
+
+    def _spec(self, rows, cols, obs, velocities):
+        from .cleanrl import RECURRENT_STRIDES
+        spec = CatchSpec(rows, cols, obs, velocities)
+        values = spec.single_observation_space.shape[0]
+        self.obs_stride = next(s for s in RECURRENT_STRIDES if values <= s)     # (160: the recurrent tier only)
+        return spec
+
+    def _config(self):
+        sp = self.driver_env
+        self.obs_dim = sp.single_observation_space.shape[0]
+        self.observations = self.obs_buf[:, :self.obs_dim]
+        self.episode_len = sp.rows - 1
+        return _lib.CatchConfig(self.num_agents, sp.rows, sp.cols, _lib.CATCH_OBS_FORMS.index(sp.obs), 1 if sp.velocities else 0,
+                                self.obs_stride, 0, self.env_offset)
+
+    def debug_states(self):
+        """[N][6] int32: (ball row, ball column, paddle column, vx, episode, ep_length) of every env — test introspection."""
+        import torch
+        out = torch.zeros(self.num_agents, 6, dtype=torch.int32, device=self.device)
+        _lib.check(self._entry('_debug_states')(*self._state_args(), _lib.ptr(out), _lib.stream_handle()), 'debug_states')
+        return out.cpu().numpy()
+
+    def render(self, env=0):
+        """Env `env` as text (CatchSpec.text)."""
+        r, c, p = self.debug_states()[env, :3]
+        return self.driver_env.text(r, c, p)
 
 
 def make_bandit(num_actions=10, reward_scale=1, reward_noise=1, **kwargs):
